@@ -5,7 +5,7 @@ N=1024, TFHE default 128-bit parameters (n=630, l=3, Bgbit=7, t=8, basebit=2), o
 A "step" is one pass of the hot path (gate pre-combination + blind rotation + sample extract +
 keyswitch) over one batch of 65,536 ciphertext pairs that are already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--gates G] [--params default128|redsec_small_v2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--gates G] [--params default128|redsec_small_v2] [--full] [--dump-outputs DIR]
 
 N > 1 is launched by torch.distributed.run (one rank per GPU, RCCL); `python bench.py --gpus N` alone starts
 that launcher itself as a child process. The gates of a batch are independent, so ranks shard them with full key
@@ -13,7 +13,10 @@ replicas: "weak" (default) = every rank runs its own 65,536 gates, "--scaling st
 evenly. The outputs are all-gathered over RCCL inside the timed region (the north star's "final RCCL gather"),
 overlapped with the next step's kernels on RCCL's own stream; its un-overlapped cost is reported separately.
 
-Rank 0 prints ONE JSON line. `roofline` prices the dominant kernel (blind rotation) against the HBM
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times exactly K steps and prints the headline: `value`
+(bootstraps/s over the K steps), `ms_per_step` (their mean), the per-step spread and the HIP-event kernel times of the timed
+launches. `--dump-outputs DIR` writes the output ciphertexts of the last timed step (a seeded sample of rows; dump_rows).
+Everything else below runs with `--full` only, after the timed steps, and adds its keys to the same line. `roofline` prices the dominant kernel (blind rotation) against the HBM
 roofline as the contract asks; `roofline_valu` prices it against the FP64 vector-ALU issue rate,
 which is what actually bounds it. `cpu_baseline` is the exact-integer CPU
 oracle (kind "port": TFHE itself is not available) timed on the host cores on a bounded sample of
@@ -31,6 +34,30 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
 FP64_VALU_PEAK_GOPS = 256 * 4 * 16 * 2.4   # CUs x SIMDs x fp64 lanes/clk x GHz = 39,322 G lane-ops/s
+DUMP_BYTES = 48 << 20            # --dump-outputs: at most this many bytes of output (a seeded sample of rows beyond it)
+DUMP_SEED = 20251016
+
+
+def dump_rows(G, W, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Row indices of a [G][W] output that --dump-outputs writes as float64: all of them when they fit in `budget` bytes, else a
+    fixed seeded sample (the same for every run with the same G and W), ascending."""
+    import numpy as np
+    rows = min(G, max(1, budget // (8 * W)))
+    if rows == G:
+        return np.arange(G, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(G, rows, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, out):
+    """What the timed path returned in its last step -- the output ciphertexts `out` [G][W] int32 on the device -- to
+    DIR/nand_out.npy as float64 (exact for every 32-bit word), rows chosen by dump_rows."""
+    import numpy as np
+    import torch
+    idx = dump_rows(int(out.shape[0]), int(out.shape[1]))
+    sample = out.index_select(0, torch.from_numpy(idx).to(out.device)).cpu().numpy().astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "nand_out.npy"), sample)
+    return sample.shape
 
 
 def fp64_ops_per_bootstrap(n, l, fwd_red, inv_red, fused_ops):
@@ -561,7 +588,18 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0xC0FFEE)
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) and run the output all-gather also at ONE rank: "
                     "walks the N > 1 code path on a one-GPU box (tools/scale_sweep.sh checks it against the plain run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline: the checks of the timed output, the other arithmetic "
+                         "modes, the rooflines and their rocprofv3 --pmc child runs, the CPU baseline, the legs on the REDsec parameter set "
+                         "(MNIST, CIFAR, NANDs), the CIFAR batch and the un-overlapped gather. The --no-* switches and --cifar-batch narrow "
+                         "this set; without --full the run times its steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output ciphertexts of the last timed step (rank 0) to DIR/nand_out.npy as "
+                         "float64 [rows][n + 1] (every int32 torus word exact): all rows when they fit in %d MB, else a fixed seeded "
+                         "sample of rows in ascending order" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -679,6 +717,8 @@ def main():
     last_ks = sum(ks_ms) / len(ks_ms)
     launch = be.last_launch()           # kernel form of the timed launches (the exact-mode leg below launches another)
     out = outs[(args.steps - 1) % len(outs)][:G]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     gather_ms = None
     if dist_on:
@@ -686,7 +726,7 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-        if gather:                                  # the same collective alone, un-overlapped, for the record
+        if gather and args.full:                    # the same collective alone, un-overlapped, for the record
             barrier(); torch.cuda.synchronize()
             t1 = time.perf_counter()
             h, _ = pipe.launch(outs[0]); pipe.wait(h)
@@ -701,11 +741,12 @@ def main():
         dist.all_gather_object(every, kernels_per_rank[0])
         kernels_per_rank = every
 
-    # ---- correctness of the timed output: every gate decrypts to NAND(a, b) ----
-    got = out.cpu().numpy()
-    decrypt_ok = bool(np.array_equal(sk.decrypt_bits(got), 1 - (bits_a & bits_b)))
+    # ---- everything below the headline runs with --full only ----
+    # correctness of the timed output: every gate decrypts to NAND(a, b)
+    got = out.cpu().numpy() if args.full else None
+    decrypt_ok = bool(np.array_equal(sk.decrypt_bits(got), 1 - (bits_a & bits_b))) if args.full else None
     gather_ok = None
-    if gather:
+    if gather and args.full:
         # what arrived from the other ranks: this rank's own block is where it belongs, and (strong scaling, where every
         # rank knows the whole batch's plaintext bits) the WHOLE gathered batch decrypts to the truth table
         full = gathered.cpu().numpy().reshape(world, width_rows, be.W)
@@ -720,7 +761,7 @@ def main():
     all_equal_exact = None
     exact_mode = None
     split_mode = None
-    if args.mode == "fft" and not args.no_exact_check:
+    if args.full and args.mode == "fft" and not args.no_exact_check:
         be.set_mode("exact")
         ref_exact = be.gate("NAND", ca, cb)                      # warm-up + the reference result
         torch.cuda.synchronize()
@@ -762,20 +803,41 @@ def main():
 
     # ---- BASELINE configs[4]: image-parallel CIFAR batch (every rank takes part; own backend on the shipped parameter set) ----
     cifar_batch = None
-    if args.cifar_batch == "on" or (args.cifar_batch == "auto" and world > 1):
+    if args.full and (args.cifar_batch == "on" or (args.cifar_batch == "auto" and world > 1)):
         cifar_batch = cifar_batch_leg(local_rank, rank, world, dist_on, rehearsal, args.cifar_batch_net, args.cifar_batch_images)
 
     # FFT mode: largest distance of any inverse-transform output from an integer over the whole run
     # (exactness needs < 0.5), and how many calls the device recomputed exactly
-    certificate = round(be.rounding_certificate(), 6) if args.mode == "fft" else None
-    recomputed = be.fft_fallbacks() if args.mode == "fft" else None
+    certificate = round(be.rounding_certificate(), 6) if args.full and args.mode == "fft" else None
+    recomputed = be.fft_fallbacks() if args.full and args.mode == "fft" else None
 
     value = total_gates * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
     step_median, step_min, step_max = step_time_stats(stamps)       # this rank's steps (kernel end to kernel end)
 
+    line = None
     if rank == 0:
         p = be.p
+        line = {
+            "metric": "gate bootstraps/sec (N=1024)", "value": round(value, 1), "unit": "bootstraps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "ms_per_step_median": None if step_median is None else round(step_median, 3), "ms_per_step_min_max": None if step_median is None else [round(step_min, 3), round(step_max, 3)],
+            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "int32 torus; ring products in f64 (%s)" % ({"fft": "complex FFT, exact after rounding", "exact": "exact NTT mod a 51-bit prime", "split": "complex FFT on a split key, exact by an a-priori bound"}[args.mode]),
+            "data": "synthetic",
+            "config": {"workload": "%d independent bootstrapped NAND gates per GPU per step, %s (n=%d N=%d l=%d Bgbit=%d t=%d basebit=%d)"
+                                   % (G, args.params, p.n, p.N, p.bk_l, p.bk_Bgbit, p.ks_t, p.ks_basebit),
+                       "gates_per_gpu": G, "total_gates": total_gates, "params": args.params, "mode": args.mode,
+                       "parallelism": "gate-sharded x%d%s" % (world, "" if world == 1 else (", outputs all-gathered over RCCL, overlapped with the next step" if gather else ", no gather"))},
+            "collective": None if not gather else {"op": "all_gather_into_tensor", "bytes_per_rank": int(width_rows * be.W * 4),
+                                                   "bytes_received_per_rank": int(world * width_rows * be.W * 4),
+                                                   "ms_alone_unoverlapped": None if gather_ms is None else round(gather_ms, 3), "inside_timed_region": True,
+                                                   "backend": "gloo (one-GPU rehearsal)" if rehearsal else "nccl (RCCL)"},
+            "kernels_ms": {"blind_rotate": round(last_br, 3), "keyswitch": round(last_ks, 3)},
+            "kernels_ms_per_rank": kernels_per_rank,
+            "setup_s": round(setup_s, 1),
+            "full": bool(args.full),
+        }
+    if rank == 0 and args.full:
         info = be.info()
         # ---- HBM roofline of the dominant kernel (blind rotation), per launch ----
         # algorithmic bytes: key swept once per R resident ciphertexts (R as the launcher
@@ -949,32 +1011,17 @@ def main():
         }
         mnist, redsec_nands, cifar = redsec_set_legs(local_rank, G, not args.no_cifar, args.cpu_sample != 0) if (world == 1 and not args.no_mnist and args.params == "default128") else (None, None, None)
 
-        line = {
-            "metric": "gate bootstraps/sec (N=1024)", "value": round(value, 1), "unit": "bootstraps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "ms_per_step_median": None if step_median is None else round(step_median, 3), "ms_per_step_min_max": None if step_median is None else [round(step_min, 3), round(step_max, 3)],
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "int32 torus; ring products in f64 (%s)" % ({"fft": "complex FFT, exact after rounding", "exact": "exact NTT mod a 51-bit prime", "split": "complex FFT on a split key, exact by an a-priori bound"}[args.mode]),
-            "data": "synthetic",
-            "config": {"workload": "%d independent bootstrapped NAND gates per GPU per step, %s (n=%d N=%d l=%d Bgbit=%d t=%d basebit=%d)"
-                                   % (G, args.params, p.n, p.N, p.bk_l, p.bk_Bgbit, p.ks_t, p.ks_basebit),
-                       "gates_per_gpu": G, "total_gates": total_gates, "params": args.params, "mode": args.mode,
-                       "parallelism": "gate-sharded x%d%s" % (world, "" if world == 1 else (", outputs all-gathered over RCCL, overlapped with the next step" if gather else ", no gather"))},
+        line.update({
             "roofline": roofline, "roofline_step": roofline_step, "roofline_valu": roofline_valu, "roofline_lds": roofline_lds, "cpu_baseline": cpu, "exact_mode": exact_mode, "split_mode": split_mode,
             "mnist_sign1024x1": mnist, "cifar_binarynet": cifar, "cifar_batch": cifar_batch, "redsec_params_nands": redsec_nands,
-            "collective": None if not gather else {"op": "all_gather_into_tensor", "bytes_per_rank": int(width_rows * be.W * 4),
-                                                   "bytes_received_per_rank": int(world * width_rows * be.W * 4),
-                                                   "ms_alone_unoverlapped": round(gather_ms, 3), "inside_timed_region": True,
-                                                   "backend": "gloo (one-GPU rehearsal)" if rehearsal else "nccl (RCCL)"},
-            "kernels_ms": {"blind_rotate": round(last_br, 3), "keyswitch": round(last_ks, 3)},
-            "kernels_ms_per_rank": kernels_per_rank,
             "exactness": exactness,
             "checks": {"all_outputs_decrypt_to_nand": decrypt_ok, "bit_exact_vs_oracle_on_sample": parity,
                        "oracle_sample_gates": {"exact_path": int(sample) if args.cpu_sample != 0 else 0},
                        "all_words_equal_exact_ntt_mode_full_batch": all_equal_exact,
                        "fft_rounding_certificate": certificate, "calls_recomputed_exactly_on_device": recomputed,
                        "gathered_batch_ok": gather_ok},
-            "setup_s": round(setup_s, 1),
-        }
+        })
+    if rank == 0:
         print(json.dumps(line), flush=True)
     barrier()
     be.close()

@@ -201,43 +201,6 @@ def build_layers(force=False, verbose=False):
         lock.close()
 
 
-REF = "/root/reference"
-REFNETS_DIR = os.path.join(ROOT, "build", "refnets")
-
-
-def build_reference_drivers(verbose=False):
-    """Compile the reference's OWN, UNMODIFIED sources -- nets/mnist/{sign,relu}1024x{1,2,3}/{net,main}.cpp, nets/cifar/binarynet{,_small}/{net,main}.cpp and
-    client/{gen_secure_keyset,encrypt_image,decrypt_image}.cpp -- with -DENCRYPTED against the shim
-    headers and link them to libredsec_layers.so. Only possible where /root/reference exists; the
-    binaries land in build/refnets/ (git-ignored, shipped to the GPU box with the snapshot)."""
-    if not os.path.isdir(os.path.join(REF, "nets")):
-        return None
-    build_layers(verbose=verbose)
-    os.makedirs(REFNETS_DIR, exist_ok=True)
-    cxx = shutil.which("g++")
-    common = ["-O1", "-w", "-DENCRYPTED", "-fopenmp", "-I" + HOST, "-L" + HERE, "-lredsec_layers", "-lredsec_hip",
-              "-Wl,-rpath," + HERE]
-    built = []
-    for family, net in (("mnist", "sign1024x1"), ("mnist", "sign1024x2"), ("mnist", "sign1024x3"),
-                        ("mnist", "relu1024x1"), ("mnist", "relu1024x2"), ("mnist", "relu1024x3"),
-                        ("cifar", "binarynet"), ("cifar", "binarynet_small")):
-        d = os.path.join(REF, "nets", family, net)
-        out = os.path.join(REFNETS_DIR, "%s_%s_enc.out" % (family, net))
-        cmd = [cxx, os.path.join(d, "net.cpp"), os.path.join(d, "main.cpp"), "-I" + d, "-I" + os.path.join(REF, "lib")] + common + ["-o", out]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        built.append(out)
-    for tool in ("gen_secure_keyset", "encrypt_image", "decrypt_image"):
-        out = os.path.join(REFNETS_DIR, "client_%s.out" % tool)
-        cmd = [cxx, os.path.join(REF, "client", tool + ".cpp")] + common + ["-o", out]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        built.append(out)
-    return built
-
-
 def build_all(force=False, verbose=False):
     return build_hip(force, verbose), build_emulator(force, verbose), build_layers(force, verbose)
 

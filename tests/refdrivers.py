@@ -1,5 +1,5 @@
-"""Helpers to run the reference's own UNMODIFIED drivers (built by redsec_amd.build.build_reference_drivers
-into build/refnets/) inside a scratch tree that reproduces the relative paths they hard-code
+"""Helpers to run the reference's own UNMODIFIED drivers (built by oracle/Makefile, from build(),
+into oracle/_ref/refnets/) inside a scratch tree that reproduces the relative paths they hard-code
 (nets/mnist/sign1024x1/net.cpp:53 "../../../client/eval.key", main.cpp:55,73)."""
 import os
 import shutil
@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFNETS = os.path.join(ROOT, "build", "refnets")
+REFNETS = os.path.join(ROOT, "oracle", "_ref", "refnets")
 GOLD = os.path.join(ROOT, "tests", "golden")
 HEADER = struct.Struct("<I7i4d")   # redsec_amd/host/tfhe_shim.cpp ParamHeader
 

@@ -81,3 +81,21 @@ def test_sign_agreement_on_a_simulated_bootstrap():
     assert t["trivial_inputs"] == 4 and t["bootstrap_agree"] == 0.75 and t["bootstrap_agree_predicted"] == 0.75
     assert "h = %d" % int(key.sum()) in res["predicted_from"]
     assert 0.0 < res["agree"] <= 1.0 and res["hidden_units"] == 2 * B + 4
+
+
+def test_dump_outputs_writes_a_fixed_exact_sample(tmp_path):
+    """--dump-outputs: the rows it keeps are the same for every run of one shape, within the byte budget and inside the batch,
+    and the int32 torus words come back exactly from the float64 file."""
+    import torch
+    G, W = 65536, 631                                            # the headline batch: 330 MB as float64, so a sample
+    idx = bench.dump_rows(G, W)
+    assert np.array_equal(idx, bench.dump_rows(G, W))
+    assert 0 < len(idx) < G and len(idx) * W * 8 <= bench.DUMP_BYTES <= 64 << 20
+    assert idx.min() >= 0 and idx.max() < G and np.all(np.diff(idx) > 0)
+    assert np.array_equal(bench.dump_rows(100, W), np.arange(100))    # a batch that fits is written whole
+    rng = np.random.default_rng(3)
+    out = torch.from_numpy(rng.integers(-2**31, 2**31, (3000, 17), dtype=np.int64).astype(np.int32))
+    shape = bench.dump_outputs(str(tmp_path / "d"), out)
+    got = np.load(str(tmp_path / "d" / "nand_out.npy"))
+    assert got.dtype == np.float64 and got.shape == shape == (3000, 17)
+    assert np.array_equal(got.astype(np.int64), out.numpy().astype(np.int64))

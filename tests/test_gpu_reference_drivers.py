@@ -1,5 +1,5 @@
 """`make cpu-encrypt` of the reference, on the MI355X backend: the reference's own net.cpp/main.cpp
-and client tools -- compiled UNMODIFIED (build/refnets) and linked to libredsec_layers.so -- run
+and client tools -- compiled UNMODIFIED (oracle/_ref/refnets) and linked to libredsec_layers.so -- run
 keygen -> encrypt image -> encrypted inference on the GPU -> decrypt, end to end through files."""
 import os
 import re
@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def test_unmodified_sign1024x1_driver_end_to_end(tmp_path):
     if not rd.available():
-        pytest.skip("build/refnets not shipped")
+        pytest.skip("oracle/_ref/refnets not shipped")
     client, netdir = rd.make_tree(str(tmp_path))
     assert rd.run("client_gen_secure_keyset.out", client).returncode == 0
     labels, pixels = pm.load_images()
@@ -50,7 +50,7 @@ def test_unmodified_cifar_binarynet_small_driver(tmp_path, maxpool, monkeypatch)
     (DESIGN.md "Max-pool semantics": one bootstrap per window / bootsOR chain)."""
     import shutil
     if not os.path.exists(os.path.join(rd.REFNETS, "cifar_binarynet_small_enc.out")):
-        pytest.skip("build/refnets not shipped")
+        pytest.skip("oracle/_ref/refnets not shipped")
     monkeypatch.setenv("REDSEC_MAXPOOL", maxpool)   # one-bootstrap OR of the window (default) / bootsOR chain
     client = str(tmp_path / "client")
     netdir = str(tmp_path / "nets" / "cifar" / "binarynet_small")
@@ -85,7 +85,7 @@ def test_unmodified_cifar_binarynet_full_driver(tmp_path):
     import shutil
     import time
     if not os.path.exists(os.path.join(rd.REFNETS, "cifar_binarynet_enc.out")):
-        pytest.skip("build/refnets not shipped")
+        pytest.skip("oracle/_ref/refnets not shipped")
     client = str(tmp_path / "client")
     netdir = str(tmp_path / "nets" / "cifar" / "binarynet")
     os.makedirs(client); os.makedirs(netdir)
@@ -131,7 +131,7 @@ def test_driver_sharded_over_several_contexts_equals_single_device(tmp_path, mon
     from redsec_amd import client
     exe = "%s_%s_enc.out" % (family, net)
     if not os.path.exists(os.path.join(rd.REFNETS, exe)):
-        pytest.skip("build/refnets not shipped")
+        pytest.skip("oracle/_ref/refnets not shipped")
     cdir = str(tmp_path / "client")
     netdir = str(tmp_path / "nets" / family / net)
     os.makedirs(cdir); os.makedirs(netdir)

@@ -135,7 +135,7 @@ def test_unmodified_relu_driver_equals_python_chain(tmp_path, name):
     import redsec_amd
     from redsec_amd import client, nets
     if not os.path.exists(os.path.join(rd.REFNETS, "mnist_%s_enc.out" % name)):
-        pytest.skip("build/refnets not shipped")
+        pytest.skip("oracle/_ref/refnets not shipped")
     cdir, netdir = rd.make_tree(str(tmp_path), name)
     assert rd.run("client_gen_secure_keyset.out", cdir).returncode == 0
     keys = client.read_tfhe_keyset(open(os.path.join(cdir, "secret.key"), "rb"), secret=True)

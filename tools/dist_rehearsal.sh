@@ -6,7 +6,7 @@
 # Timings of (2) say nothing about scaling.
 set -o pipefail
 OUT="${1:-gpurun_out/rehearsal}"; mkdir -p "$OUT"
-COMMON="--steps 2 --warmup 1 --cpu-sample 0 --no-mnist --no-live-traffic --no-exact-check"
+COMMON="--full --steps 2 --warmup 1 --cpu-sample 0 --no-mnist --no-live-traffic --no-exact-check"
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 $COMMON --force-dist --cifar-batch on > "$OUT/rccl_world1.json" 2> "$OUT/rccl_world1.err" || { tail -5 "$OUT/rccl_world1.err"; exit 1; }
 for MODE in weak strong; do
   REDSEC_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 2 $COMMON --scaling $MODE --gates 16384 --cifar-batch-net binarynet_small \

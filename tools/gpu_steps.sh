@@ -22,7 +22,7 @@ for step in "$@"; do
     tests) timeout -k 10 900 python -m pytest $arg -m gpu -x -q --durations=10 > $OUT/$tag.log 2>&1; rc=$?; tail -15 $OUT/$tag.log;;
     bench) timeout -k 10 600 python bench.py $arg > $OUT/$tag.log 2> $OUT/$tag.err; rc=$?; tail -1 $OUT/$tag.log > $OUT/$tag.json; tail -c 3000 $OUT/$tag.json; echo; tail -3 $OUT/$tag.err;;
     mnist) if [ -n "$arg" ]; then env $arg timeout -k 10 300 python tools/mnist_latency.py > $OUT/$tag.txt 2>&1; else timeout -k 10 300 python tools/mnist_latency.py > $OUT/$tag.txt 2>&1; fi; rc=$?; cat $OUT/$tag.txt;;
-    prof) rm -rf /tmp/prof_$LABEL; (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$LABEL -- python3 $OLDPWD/bench.py --cpu-sample 0 --no-live-traffic --no-cifar $arg > $OLDPWD/$OUT/$tag.log 2>&1); rc=$?
+    prof) rm -rf /tmp/prof_$LABEL; (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$LABEL -- python3 $OLDPWD/bench.py --full --cpu-sample 0 --no-live-traffic --no-cifar $arg > $OLDPWD/$OUT/$tag.log 2>&1); rc=$?
           f=$(find /tmp/prof_$LABEL -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $OUT/${LABEL}_kernel_stats.csv && head -12 $OUT/${LABEL}_kernel_stats.csv;;
     pmc) # pmc:COUNTERS[/COUNTERS...]:script+args -- one rocprofv3 --pmc run per '/'-separated counter group (counters only)
           groups="${arg%%:*}"; cmd="${arg#*:}"; rc=0
