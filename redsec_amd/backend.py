@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "rs_set_timing", "rs_last_kernel_ms", "rs_info", "rs_set_mode", "rs_get_mode", "rs_rounding_certificate", "rs_fft_fallbacks",
     "rs_bootstrap_lut_dev", "rs_set_certificate_limit", "rs_certify", "rs_reserve_stream", "rs_last_kernel_ms_stream", "rs_last_launch", "rs_copy_dev_to_dev",
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
-    "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys",
+    "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -87,6 +87,8 @@ def load_library(path=None):
     L.rs_destroy.argtypes = [vp]
     L.rs_load_keys.argtypes = [vp, _i32p, _i32p]
     L.rs_load_synthetic_keys.argtypes = [vp, C.c_uint64]
+    L.rs_load_keys_dev.argtypes = [vp, vp, vp]
+    L.rs_keygen_dev.argtypes = [vp, vp, vp, _i32p, _i32p, C.c_char_p, C.c_double, C.c_double]
     L.rs_reserve.argtypes = [vp, C.c_size_t]
     L.rs_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_bootstrap.argtypes = [vp, _i32p, _i32p, C.c_int32, C.c_size_t]
@@ -217,6 +219,33 @@ class Backend:
         assert bk.size == p.n * 2 * p.bk_l * 2 * p.N, "bk has the wrong size"
         assert ksk.size == p.N * p.ks_t * (1 << p.ks_basebit) * (p.n + 1), "ksk has the wrong size"
         _check(self.L, self.L.rs_load_keys(self.h, pbk, pksk))
+
+    def _key_sizes(self):
+        p = self.p
+        return p.n * 2 * p.bk_l * 2 * p.N, p.N * p.ks_t * (1 << p.ks_basebit) * (p.n + 1)
+
+    def load_keys_dev(self, bk, ksk):
+        """rs_load_keys from int32 CUDA tensors on this context's device (device-to-device; the tensors are not modified)."""
+        nb, nk = self._key_sizes()
+        assert bk.numel() == nb, "bk has the wrong size"
+        assert ksk.numel() == nk, "ksk has the wrong size"
+        _check(self.L, self.L.rs_load_keys_dev(self.h, self._ck_dev(bk), self._ck_dev(ksk)))
+
+    def keygen(self, lwe_key, tlwe_key, seed, bk_stdev, ks_stdev, bk=None, ksk=None):
+        """Evaluation key generated on the device (rs_keygen_dev) -> (bk [n][2l][2][N], ksk [N][t][2^basebit][n+1]) int32 CUDA
+        tensors (or into the given ones). lwe_key / tlwe_key: 0/1 arrays of length n / N; seed: 32 bytes. Does not load the key."""
+        p = self.p
+        lwe, plwe = _np_i32(lwe_key)
+        tlwe, ptlwe = _np_i32(tlwe_key)
+        assert lwe.size == p.n and tlwe.size == p.N, "secret keys have the wrong size"
+        seed = bytes(seed)
+        assert len(seed) == 32, "seed must be 32 bytes"
+        bk = self.empty(p.n, 2 * p.bk_l, 2, p.N) if bk is None else bk
+        ksk = self.empty(p.N, p.ks_t, 1 << p.ks_basebit, p.n + 1) if ksk is None else ksk
+        nb, nk = self._key_sizes()
+        assert bk.numel() == nb and ksk.numel() == nk, "key tensors have the wrong size"
+        _check(self.L, self.L.rs_keygen_dev(self.h, self._ck_dev(bk), self._ck_dev(ksk), plwe, ptlwe, seed, float(bk_stdev), float(ks_stdev)))
+        return bk, ksk
 
     def load_synthetic_keys(self, seed):
         """A key of pseudo-random words generated ON THE DEVICE (rs_load_synthetic_keys; client.synthetic_key_words restates the

@@ -111,6 +111,22 @@ class SecretKeySet:
         ksk[:, :, 1:, n] = _wrap32(mess + Ek.view(np.uint32).astype(np.uint64) + dot)
         self.ksk = np.ascontiguousarray(ksk)
 
+    @classmethod
+    def from_secret(cls, name, lwe_key, tlwe_key):
+        """The secret keys alone (encrypt / decrypt / phase / classify), no evaluation key (bk = ksk = None): the client half of
+        a key whose evaluation key was generated elsewhere (redsec_amd.keygen, on the device). The LWE dimension is len(lwe_key)."""
+        (_, N, k, l, Bgbit, t, basebit, _, _) = PARAM_SETS[name]
+        self = cls.__new__(cls)
+        self.name = name
+        self.lwe_key = np.ascontiguousarray(lwe_key, np.int32)
+        self.tlwe_key = np.ascontiguousarray(tlwe_key, np.int32)
+        assert self.tlwe_key.size == N, "tlwe_key must have N = %d words" % N
+        self.n = int(self.lwe_key.size)
+        self.N, self.k, self.l, self.Bgbit, self.t, self.basebit = N, k, l, Bgbit, t, basebit
+        self.W = self.n + 1
+        self.bk = self.ksk = None
+        return self
+
     # lweSymEncrypt on a batch of torus32 messages -> int32 [B][n+1]
     def encrypt_torus(self, mu, alpha=SECALPHA, seed=1):
         mu = np.asarray(mu).astype(np.int64).ravel()

@@ -515,56 +515,133 @@ int rs_destroy(rs_ctx* c) {
   return rc;
 }
 
-// bk / ksk: host arrays, or both null for the synthetic key of `seed` generated on the device (rs_load_synthetic_keys)
-static int load_keys_impl(rs_ctx* c, const int32_t* bk, const int32_t* ksk, uint64_t seed) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  const bool synthetic = !bk && !ksk;
-  if (!synthetic && (!bk || !ksk)) return fail(RS_ERR_INVALID, "null key pointer");
-  const rs_params& p = c->p;
-  const size_t n_polys = (size_t)p.n * (size_t)(2 * p.bk_l) * 2;
-  const size_t bk_words = n_polys * (size_t)p.N;
-  const size_t ksk_words = (size_t)p.N * p.ks_t * ((size_t)1 << p.ks_basebit) * (size_t)(p.n + 1);
+// where load_keys_impl takes the key words from
+enum class KeySource { kHost, kDevice, kSynthetic };
+
+// drops every key buffer of the context (a failed load leaves no half-built transform key behind)
+static void free_keys(rs_ctx* c) {
+  c->keys = false;
   if (c->d_bk_ntt) { (void)hipFree(c->d_bk_ntt); c->d_bk_ntt = nullptr; }
   if (c->d_bk_fft) { (void)hipFree(c->d_bk_fft); c->d_bk_fft = nullptr; }
   if (c->d_bk_gen) { (void)hipFree(c->d_bk_gen); c->d_bk_gen = nullptr; }
   if (c->d_ksk) { (void)hipFree(c->d_ksk); c->d_ksk = nullptr; }
-  c->keys = false;
-  int32_t* d_bk = nullptr;
-  RS_HIP(hipMalloc(&d_bk, bk_words * sizeof(int32_t)));
-  if (synthetic) RS_HIP(rs::launch_synthetic_words(d_bk, seed, bk_words, nullptr));
-  else RS_HIP(hipMemcpy(d_bk, bk, bk_words * sizeof(int32_t), hipMemcpyHostToDevice));
-  c->bk_bytes = 0;
-  if (!c->general) {
-    // both transform domains are kept resident (62 + 62 MB default-128, 115 + 115 MB REDsec): the FFT mode's
-    // gated exact recomputation needs the NTT-domain key, and the mode can be switched per call
-    RS_HIP(hipMalloc(&c->d_bk_ntt, bk_words * sizeof(double)));
-    RS_HIP(hipMalloc(&c->d_bk_fft, bk_words * sizeof(double)));
-    RS_HIP(rs::launch_bk_transform(c->cfg, 0, d_bk, c->d_bk_ntt, c->d_tw, c->tables.f, c->tables.ninv, (long)n_polys, nullptr));
-    RS_HIP(rs::launch_bk_transform(c->cfg, 1, d_bk, c->d_bk_fft, c->d_tw_fft, c->tables.f, 0.0, (long)n_polys, nullptr));
-    c->bk_bytes = bk_words * sizeof(double);
+  c->bk_bytes = c->ksk_bytes = 0;
+}
+
+// bk / ksk: host arrays, device arrays, or unused for the synthetic key of `seed` generated on the device (rs_load_synthetic_keys)
+static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int32_t* ksk, uint64_t seed) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (src != KeySource::kSynthetic && (!bk || !ksk)) return fail(RS_ERR_INVALID, "null key pointer");
+  const rs_params& p = c->p;
+  const size_t n_polys = (size_t)p.n * (size_t)(2 * p.bk_l) * 2;
+  const size_t bk_words = n_polys * (size_t)p.N;
+  const size_t ksk_words = (size_t)p.N * p.ks_t * ((size_t)1 << p.ks_basebit) * (size_t)(p.n + 1);
+  free_keys(c);
+  int32_t* d_bk = nullptr;   // staging copy of the key words (freed on every path)
+  auto body = [&]() -> int {
+    RS_HIP(hipMalloc(&d_bk, bk_words * sizeof(int32_t)));
+    if (src == KeySource::kSynthetic) RS_HIP(rs::launch_synthetic_words(d_bk, seed, bk_words, nullptr));
+    else RS_HIP(hipMemcpy(d_bk, bk, bk_words * sizeof(int32_t), src == KeySource::kHost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+    if (!c->general) {
+      // both transform domains are kept resident (62 + 62 MB default-128, 115 + 115 MB REDsec): the FFT mode's
+      // gated exact recomputation needs the NTT-domain key, and the mode can be switched per call
+      RS_HIP(hipMalloc(&c->d_bk_ntt, bk_words * sizeof(double)));
+      RS_HIP(hipMalloc(&c->d_bk_fft, bk_words * sizeof(double)));
+      RS_HIP(rs::launch_bk_transform(c->cfg, 0, d_bk, c->d_bk_ntt, c->d_tw, c->tables.f, c->tables.ninv, (long)n_polys, nullptr));
+      RS_HIP(rs::launch_bk_transform(c->cfg, 1, d_bk, c->d_bk_fft, c->d_tw_fft, c->tables.f, 0.0, (long)n_polys, nullptr));
+      c->bk_bytes = bk_words * sizeof(double);
+    }
+    if (c->d_tw_gen) {
+      // the split key: two transformed halves per polynomial (twice the bytes of one domain)
+      RS_HIP(hipMalloc(&c->d_bk_gen, 2 * bk_words * sizeof(double)));
+      RS_HIP(rs::launch_gen_bk_transform(c->logn, d_bk, c->d_bk_gen, c->d_tw_gen, (long)n_polys, c->num_cus, nullptr));
+      if (c->general) c->bk_bytes = 2 * bk_words * sizeof(double);
+    }
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipFree(d_bk));
+    d_bk = nullptr;
+    RS_HIP(hipMalloc(&c->d_ksk, ksk_words * sizeof(int32_t)));
+    if (src == KeySource::kSynthetic) { RS_HIP(rs::launch_synthetic_words(c->d_ksk, seed ^ 0x6b73ull, ksk_words, nullptr)); RS_HIP(hipDeviceSynchronize()); }
+    else if (src == KeySource::kHost) RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyHostToDevice));
+    else { RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyDeviceToDevice)); RS_HIP(hipDeviceSynchronize()); }
+    c->ksk_bytes = ksk_words * sizeof(int32_t);
+    return RS_OK;
+  };
+  rc = body();
+  if (rc != RS_OK) {
+    (void)hipDeviceSynchronize();
+    if (d_bk) (void)hipFree(d_bk);
+    free_keys(c);
+    return rc;
   }
-  if (c->d_tw_gen) {
-    // the split key: two transformed halves per polynomial (twice the bytes of one domain)
-    RS_HIP(hipMalloc(&c->d_bk_gen, 2 * bk_words * sizeof(double)));
-    RS_HIP(rs::launch_gen_bk_transform(c->logn, d_bk, c->d_bk_gen, c->d_tw_gen, (long)n_polys, c->num_cus, nullptr));
-    if (c->general) c->bk_bytes = 2 * bk_words * sizeof(double);
-  }
-  RS_HIP(hipDeviceSynchronize());
-  RS_HIP(hipFree(d_bk));
-  RS_HIP(hipMalloc(&c->d_ksk, ksk_words * sizeof(int32_t)));
-  if (synthetic) { RS_HIP(rs::launch_synthetic_words(c->d_ksk, seed ^ 0x6b73ull, ksk_words, nullptr)); RS_HIP(hipDeviceSynchronize()); }
-  else RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyHostToDevice));
-  c->ksk_bytes = ksk_words * sizeof(int32_t);
   c->keys = true;
   return RS_OK;
 }
 
 int rs_load_keys(rs_ctx* c, const int32_t* bk, const int32_t* ksk) {
   if (!bk || !ksk) return fail(RS_ERR_INVALID, "null key pointer");
-  return load_keys_impl(c, bk, ksk, 0);
+  return load_keys_impl(c, KeySource::kHost, bk, ksk, 0);
 }
-int rs_load_synthetic_keys(rs_ctx* c, uint64_t seed) { return load_keys_impl(c, nullptr, nullptr, seed); }
+int rs_load_keys_dev(rs_ctx* c, const int32_t* bk, const int32_t* ksk) {
+  if (!bk || !ksk) return fail(RS_ERR_INVALID, "null key pointer");
+  return load_keys_impl(c, KeySource::kDevice, bk, ksk, 0);
+}
+int rs_load_synthetic_keys(rs_ctx* c, uint64_t seed) { return load_keys_impl(c, KeySource::kSynthetic, nullptr, nullptr, seed); }
+
+int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
+                  double bk_stdev, double ks_stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!bk || !ksk || !lwe_key || !tlwe_key || !seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (((uintptr_t)bk & 15u) != 0) return fail(RS_ERR_INVALID, "bk must be 16-byte aligned");
+  if (!(std::isfinite(bk_stdev) && bk_stdev >= 0.0) || !(std::isfinite(ks_stdev) && ks_stdev >= 0.0))
+    return fail(RS_ERR_INVALID, "noise deviations must be finite and non-negative (bk %g, ks %g)", bk_stdev, ks_stdev);
+  if (!c->d_tw_gen) return fail(RS_ERR_INVALID, "split-key product not offered for this set: a-priori bound %.3g", c->split_bound);
+  const rs_params& p = c->p;
+  for (int i = 0; i < p.n; ++i)
+    if (lwe_key[i] != 0 && lwe_key[i] != 1) return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", i, lwe_key[i]);
+  for (int i = 0; i < p.N; ++i)
+    if (tlwe_key[i] != 0 && tlwe_key[i] != 1) return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", i, tlwe_key[i]);
+  // private device copy of the secret key [n + N] plus the rounding-distance flag; zeroed and freed before returning
+  const size_t key_bytes = ((size_t)(p.n + p.N) * sizeof(int32_t) + 15) & ~(size_t)15;
+  const size_t bytes = key_bytes + sizeof(unsigned long long);
+  char* d_sec = nullptr;
+  RS_HIP(hipMalloc(&d_sec, bytes));
+  rs::KeygenArgs a{};
+  a.bk = bk; a.ksk = ksk;
+  a.lwe_key = reinterpret_cast<const int32_t*>(d_sec);
+  a.tlwe_key = a.lwe_key + p.n;
+  for (int k = 0; k < 8; ++k)
+    a.seed[k] = (uint32_t)seed[4 * k] | ((uint32_t)seed[4 * k + 1] << 8) | ((uint32_t)seed[4 * k + 2] << 16) | ((uint32_t)seed[4 * k + 3] << 24);
+  a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
+  a.bk_sigma = bk_stdev; a.ks_sigma = ks_stdev;
+  a.dev_flag = reinterpret_cast<unsigned long long*>(d_sec + key_bytes);
+  unsigned long long flag = 0;
+  auto body = [&]() -> int {
+    RS_HIP(hipMemcpy(d_sec, lwe_key, (size_t)p.n * sizeof(int32_t), hipMemcpyHostToDevice));
+    RS_HIP(hipMemcpy(d_sec + (size_t)p.n * sizeof(int32_t), tlwe_key, (size_t)p.N * sizeof(int32_t), hipMemcpyHostToDevice));
+    RS_HIP(hipMemset(a.dev_flag, 0, sizeof(unsigned long long)));
+    RS_HIP(rs::launch_keygen_bk(c->logn, a, c->d_tw_gen, c->num_cus, nullptr));
+    RS_HIP(rs::launch_keygen_ksk(a, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipMemcpy(&flag, a.dev_flag, sizeof flag, hipMemcpyDeviceToHost));
+    return RS_OK;
+  };
+  rc = body();
+  // the secret leaves the device before the call returns, on the error paths too
+  (void)hipDeviceSynchronize();
+  const hipError_t ez = hipMemset(d_sec, 0, bytes);
+  const hipError_t es = hipDeviceSynchronize();
+  (void)hipFree(d_sec);
+  if (rc != RS_OK) return rc;
+  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
+  double dist = 0.0;
+  memcpy(&dist, &flag, sizeof dist);
+  if (!(dist < rs::kSplitBoundEnforce))
+    return fail(RS_ERR_INEXACT, "key generation: a rounding distance of %.3g was observed in the a*S products (limit 1/4)", dist);
+  return RS_OK;
+}
 
 int rs_reserve(rs_ctx* c, size_t max_batch) { return rs_reserve_stream(c, max_batch, nullptr); }
 

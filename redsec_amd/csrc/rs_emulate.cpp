@@ -12,6 +12,7 @@
 
 #include "rs_general.h"
 #include "rs_host.h"
+#include "rs_keygen.h"
 #include "rs_lds_plan.h"
 #include "rs_ntt.h"
 
@@ -1118,5 +1119,18 @@ long rs_emu_gen_digit_mismatches(int l, int bgbit, uint32_t start, uint32_t step
   }
   return bad;
 }
+
+// the random streams of key generation (rs_keygen.h), for the bit-exact comparison with redsec_amd/keygen.py
+void rs_emu_chacha_block(const uint32_t* key8, uint32_t domain, uint64_t row, uint32_t block, uint32_t* out16) {
+  uint32_t key[8], out[16];
+  for (int k = 0; k < 8; ++k) key[k] = key8[k];
+  rs::kg_chacha_block(key, domain, row, block, out);
+  for (int k = 0; k < 16; ++k) out16[k] = out[k];
+}
+void rs_emu_keygen_uniforms(const uint32_t* w4, double* u1u2) {
+  u1u2[0] = rs::kg_u1(w4[0], w4[1]);
+  u1u2[1] = rs::kg_u2(w4[2], w4[3]);
+}
+int32_t rs_emu_keygen_noise(const uint32_t* w4, double sigma) { return rs::kg_noise32(w4[0], w4[1], w4[2], w4[3], sigma); }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 //   gen_blind_rotate_kernel    gate pre-combination + modswitch + n CMUX steps + sample extract
 //                              (tfhe_bootstrap_woKS_FFT / tfhe_blindRotateAndExtract_FFT; REDsec: lib/BinOps_enc.cpp:185,191)
 //   gen_polymul_kernel         debug/parity tap through the same transform path
+//   gen_keygen_bk_kernel       evaluation-key generation: TGSW rows of the bootstrapping key, b = a*S + e through the same product
+//   keygen_ksk_kernel          evaluation-key generation: keyswitching-key samples (integer stream work)
 //
 // One workgroup of T = N/16 threads owns one ciphertext: its TRLWE accumulator (2 x N int32) and the two exchange
 // planes live in LDS (17 N bytes), every thread keeps 8 complex values of the transform in flight and the
@@ -16,6 +18,7 @@
 
 #include "rs_diag.h"
 #include "rs_general.h"
+#include "rs_keygen.h"
 #include "rs_kernels.h"
 
 namespace rs {
@@ -381,6 +384,154 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_polymul_kernel(const int32_t
   gen_publish(dev, dev_flag);
 }
 
+// TGSW rows of the bootstrapping key (rs_keygen_dev): row = i 2l + p, p = c l + j, written as (a, b) with b = a*S + e and the gadget
+// term s_i 2^(32 - (j+1) Bgbit) on coefficient 0 of component c. A workgroup transforms S once; per row the T threads generate the
+// mask in its own stream (thread t: ChaCha block t = words 16t .. 16t+15, i.e. the whole row) and the noise (blocks 4t .. 4t+3),
+// exchange both through LDS into the transform layout, and form a*S by gen_polymul_kernel's split product with the roles swapped:
+// the torus operand (the mask) is split into 16-bit halves, S is the small one. |half| <= 2^15 and S binary keep every half-product
+// coefficient below N 2^15 -- far inside the products gen_error_bound covers (2l rows of Bg/2-digits times 2^15-halves) -- so
+// rounding is exact; the distances are still published through dev_flag like every other general-ring product.
+template <int LOGN>
+__global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs a, const double* __restrict__ tw) {
+  using G = Gen<LOGN>;
+  constexpr int N = G::N, M = G::M, T = G::T;
+  __shared__ double s_re[G::kPlane], s_im[G::kPlane];
+  __shared__ double s_twn[kGenStageTw<LOGN> ? 2 * kGenTwLds : 2];
+  __shared__ uint32_t s_mask[N], s_noise[N];
+  const int t = threadIdx.x;
+  auto sync = [] { gen_sync<T>(); };
+  auto wsync = [] { gen_wave_sync(); };
+  const double* twn = gen_stage_twiddles<LOGN>(s_twn, tw, t);
+  uint32_t key[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  const bool noisy = a.bk_sigma != 0.0;
+  // S in the transform domain, scaled by 1/M (a power of two: exact); kept in registers for all rows of this workgroup
+  double sx[kRegs];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sx[r] = (double)a.tlwe_key[t + T * r];
+  gen_fft_fwd<LOGN>(sx, t, tw, twn, s_re, s_im, sync, wsync);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sx[r] *= 1.0 / M;
+  double dev = 0.0;
+  const long rows = (long)a.n * 2 * a.l;
+  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    const int i = (int)(row / (2 * a.l)), p = (int)(row % (2 * a.l)), c = p / a.l, j = p % a.l;
+    const uint32_t gadget = a.lwe_key[i] ? (1u << (32 - (j + 1) * a.bgbit)) : 0u;
+    int32_t* pa = a.bk + (size_t)row * 2 * N;
+    int32_t* pb = pa + N;
+    {
+      uint32_t w[16];
+      kg_chacha_block(key, kKgBkMask, (uint64_t)row, (uint32_t)t, w);
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s_mask[16 * t + k] = w[k];
+      // the stored mask of a c = 0 row carries the gadget term on coefficient 0 (added after b is formed from the plain mask)
+      const uint32_t w0 = w[0] + ((t == 0 && c == 0) ? gadget : 0u);
+      int4* dst = reinterpret_cast<int4*>(pa) + 4 * t;
+      dst[0] = make_int4((int)w0, (int)w[1], (int)w[2], (int)w[3]);
+      dst[1] = make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]);
+      dst[2] = make_int4((int)w[8], (int)w[9], (int)w[10], (int)w[11]);
+      dst[3] = make_int4((int)w[12], (int)w[13], (int)w[14], (int)w[15]);
+      if (noisy) {
+#pragma unroll 1
+        for (int g4 = 0; g4 < 4; ++g4) {
+          kg_chacha_block(key, kKgBkNoise, (uint64_t)row, (uint32_t)(4 * t + g4), w);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) s_noise[16 * t + 4 * g4 + q] = (uint32_t)kg_noise32(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], a.bk_sigma);
+        }
+      }
+    }
+    sync();
+    double S[2][kRegs];
+#pragma unroll
+    for (int piece = 0; piece < 2; ++piece) {   // unrolled: S indexed by a run-time piece would live in scratch
+      double x[kRegs];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int32_t lo, hi;
+        gen_split_key((int32_t)s_mask[t + T * r], lo, hi);
+        x[r] = (double)(piece ? hi : lo);
+      }
+      gen_fft_fwd<LOGN>(x, gen_local(t), tw, twn, s_re, s_im, sync, wsync);
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        S[piece][r] = 0.0; S[piece][r + 8] = 0.0;
+        fft_cmac(S[piece][r], S[piece][r + 8], x[r], x[r + 8], sx[r], sx[r + 8]);
+      }
+    }
+    // the two inverse transforms one after the other, the first one's rounded words replacing its 16 doubles before the second
+    // runs: the register peak stays below the 256 VGPRs of a 512-thread workgroup at N = 8192 beside S's transform
+    uint32_t b[kRegs];
+    gen_fft_inv<LOGN>(S[0], gen_local(t), tw, twn, s_re, s_im, sync, wsync);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) b[r] = (uint32_t)fft_round_torus32(S[0][r], dev);
+    gen_fft_inv<LOGN>(S[1], gen_local(t), tw, twn, s_re, s_im, sync, wsync);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int jj = t + T * r;
+      b[r] += ((uint32_t)fft_round_torus32(S[1][r], dev) << 16) + ((jj == 0 && c == 1) ? gadget : 0u);
+      if (noisy) b[r] += s_noise[jj];
+      pb[jj] = (int32_t)b[r];
+    }
+    sync();   // s_mask / s_noise are rewritten for the next row
+  }
+  gen_publish(dev, a.dev_flag);
+}
+
+// Keyswitching-key samples (rs_keygen_dev): one wave per sample s = (i t + j) 2^basebit + v, which is also its row in domains 5 / 6.
+// Lane L generates block 64 m + L of the mask; the words pass through LDS so that the stores and the reads of the LWE key are
+// coalesced, and a wave reduction gives sum a_k s_k mod 2^32. Samples with v = 0 are written as zeros.
+constexpr int kKgWaves = 4;
+__global__ __launch_bounds__(64 * kKgWaves) void keygen_ksk_kernel(KeygenArgs a) {
+  __shared__ uint32_t s_w[kKgWaves][64 * 16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t* buf = s_w[wv];
+  uint32_t key[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  const int base = 1 << a.basebit, W = a.n + 1;
+  const long samples = (long)a.N * a.t * base;
+  for (long s = (long)blockIdx.x * kKgWaves + wv; s < samples; s += (long)gridDim.x * kKgWaves) {
+    int32_t* out = a.ksk + (size_t)s * W;
+    const int v = (int)(s & (base - 1));
+    if (v == 0) {
+      for (int k = lane; k < W; k += 64) out[k] = 0;
+      continue;
+    }
+    const long ij = s >> a.basebit;
+    const int i = (int)(ij / a.t), j = (int)(ij % a.t);
+    uint32_t acc = 0;
+    uint32_t w[16];
+    for (int k0 = 0; k0 < a.n; k0 += 64 * 16) {
+      const int blk = k0 / 16 + lane;
+      if (16 * blk < a.n) kg_chacha_block(key, kKgKsMask, (uint64_t)s, (uint32_t)blk, w);
+      gen_wave_sync();   // this wave's reads of the previous chunk are done
+#pragma unroll
+      for (int q = 0; q < 16; ++q) buf[16 * lane + q] = w[q];
+      gen_wave_sync();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int idx = 64 * q + lane, k = k0 + idx;
+        if (k < a.n) {
+          const uint32_t x = buf[idx];
+          out[k] = (int32_t)x;
+          acc += a.lwe_key[k] ? x : 0u;
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += (uint32_t)__shfl_xor((int)acc, off, 64);
+    if (lane == 0) {
+      uint32_t e = 0;
+      if (a.ks_sigma != 0.0) {
+        kg_chacha_block(key, kKgKsNoise, (uint64_t)s, 0u, w);
+        e = (uint32_t)kg_noise32(w[0], w[1], w[2], w[3], a.ks_sigma);
+      }
+      out[a.n] = (int32_t)(acc + e + (((uint32_t)a.tlwe_key[i] * (uint32_t)v) << (32 - (j + 1) * a.basebit)));
+    }
+  }
+}
+
 // ---- launchers ----
 // persistent grid: as many workgroups as the device keeps resident (asked from the runtime once per kernel)
 template <class K>
@@ -448,6 +599,28 @@ hipError_t launch_gen_polymul(int logn, const int32_t* a_small, const int32_t* b
     case 13: hipLaunchKernelGGL((gen_polymul_kernel<13>), grid, block, 0, st, a_small, b_torus, out, scratch, tw, count, dev_flag); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_keygen_bk(int logn, const KeygenArgs& a, const double* tw, int num_cus, hipStream_t st) {
+  const long rows = (long)a.n * 2 * a.l;
+  if (rows <= 0) return hipSuccess;
+  const dim3 grid((unsigned)gen_grid(logn, rows, num_cus)), block((1u << logn) / 16);
+  switch (logn) {
+    case 10: hipLaunchKernelGGL((gen_keygen_bk_kernel<10>), grid, block, 0, st, a, tw); break;
+    case 11: hipLaunchKernelGGL((gen_keygen_bk_kernel<11>), grid, block, 0, st, a, tw); break;
+    case 12: hipLaunchKernelGGL((gen_keygen_bk_kernel<12>), grid, block, 0, st, a, tw); break;
+    case 13: hipLaunchKernelGGL((gen_keygen_bk_kernel<13>), grid, block, 0, st, a, tw); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_keygen_ksk(const KeygenArgs& a, int num_cus, hipStream_t st) {
+  const long samples = (long)a.N * a.t * (1L << a.basebit);
+  if (samples <= 0) return hipSuccess;
+  const long blocks = std::min<long>((samples + kKgWaves - 1) / kKgWaves, 16L * num_cus);
+  hipLaunchKernelGGL(keygen_ksk_kernel, dim3((unsigned)blocks), dim3(64 * kKgWaves), 0, st, a);
   return hipGetLastError();
 }
 

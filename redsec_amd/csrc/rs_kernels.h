@@ -103,6 +103,17 @@ long gen_resident_ciphertexts(int logn, int num_cus);   // workgroups (= ciphert
 hipError_t launch_gen_bk_transform(int logn, const int32_t* bk, double* bk_x, const double* tw, long n_polys, int num_cus, hipStream_t st);
 hipError_t launch_gen_polymul(int logn, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch, const double* tw,
                               long count, unsigned long long* dev_flag, int num_cus, hipStream_t st);
+// evaluation-key generation (rs_keygen_dev; streams of rs_keygen.h): bk rows [n][2l][2][N] and ksk samples [N][t][2^basebit][n+1]
+struct KeygenArgs {
+  int32_t* bk; int32_t* ksk;
+  const int32_t* lwe_key; const int32_t* tlwe_key;   // device copies, values 0 / 1
+  uint32_t seed[8];
+  int n, N, l, bgbit, t, basebit;
+  double bk_sigma, ks_sigma;
+  unsigned long long* dev_flag;                       // largest rounding distance of the a*S products
+};
+hipError_t launch_keygen_bk(int logn, const KeygenArgs& a, const double* tw, int num_cus, hipStream_t st);
+hipError_t launch_keygen_ksk(const KeygenArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,

@@ -1,0 +1,72 @@
+// rs_keygen.h -- the random streams of evaluation-key generation (rs_keygen_dev, include/redsec_hip.h), shared by the device
+// kernels (rs_general.hip), the lane emulator (rs_emulate.cpp) and restated in numpy by redsec_amd/keygen.py.
+//
+// Stream (domain, row) of a 32-byte seed: word w is word w & 15 of the ChaCha20 block (RFC 8439 section 2.3, 20 rounds, input
+// added back) whose state is
+//     words 0-3    "expand 32-byte k"
+//     words 4-11   the seed as 8 little-endian words
+//     word 12      the block counter w >> 4 within the row
+//     words 13-15  domain, row & 0xffffffff, row >> 32
+// Gaussian g of a row consumes words 4g .. 4g+3:
+//     u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 1) 2^-53   in (0, 1]
+//     u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53       in [0, 1)
+//     z  = sqrt(-2 ln u1) cos(2 pi u2)               (2 pi as the double 6.283185307179586)
+// and the noise word is TFHE's dtot32(sigma z): the fractional part of sigma z (truncated toward zero) times 2^32, converted to
+// int64, wrapped to 32 bits.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#include "rs_ntt.h"
+
+namespace rs {
+
+// domains (the table of include/redsec_hip.h, rs_keygen_dev)
+enum { kKgLweSecret = 1, kKgTlweSecret = 2, kKgBkMask = 3, kKgBkNoise = 4, kKgKsMask = 5, kKgKsNoise = 6 };
+
+RS_HD uint32_t kg_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
+RS_HD void kg_quarter(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) {
+  a += b; d ^= a; d = kg_rotl(d, 16);
+  c += d; b ^= c; b = kg_rotl(b, 12);
+  a += b; d ^= a; d = kg_rotl(d, 8);
+  c += d; b ^= c; b = kg_rotl(b, 7);
+}
+
+// the 16 words of block `block` of stream (domain, row)
+RS_HD void kg_chacha_block(const uint32_t (&key)[8], uint32_t domain, uint64_t row, uint32_t block, uint32_t (&out)[16]) {
+  uint32_t in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7],
+                     block, domain, (uint32_t)row, (uint32_t)(row >> 32)};
+  uint32_t x[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x[i] = in[i];
+#pragma unroll 1
+  for (int r = 0; r < 10; ++r) {
+    kg_quarter(x[0], x[4], x[8], x[12]);
+    kg_quarter(x[1], x[5], x[9], x[13]);
+    kg_quarter(x[2], x[6], x[10], x[14]);
+    kg_quarter(x[3], x[7], x[11], x[15]);
+    kg_quarter(x[0], x[5], x[10], x[15]);
+    kg_quarter(x[1], x[6], x[11], x[12]);
+    kg_quarter(x[2], x[7], x[8], x[13]);
+    kg_quarter(x[3], x[4], x[9], x[14]);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) out[i] = x[i] + in[i];
+}
+
+RS_HD double kg_u1(uint32_t w0, uint32_t w1) {
+  return (double)((((uint64_t)(w0 >> 5)) << 26) + (uint64_t)(w1 >> 6) + 1u) * 0x1p-53;
+}
+RS_HD double kg_u2(uint32_t w2, uint32_t w3) {
+  return (double)((((uint64_t)(w2 >> 5)) << 26) + (uint64_t)(w3 >> 6)) * 0x1p-53;
+}
+// dtot32(sigma z) of the Gaussian made from four stream words; sigma = 0 gives 0 without evaluating anything
+RS_HD int32_t kg_noise32(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, double sigma) {
+  if (sigma == 0.0) return 0;
+  const double z = sqrt(-2.0 * log(kg_u1(w0, w1))) * cos(6.283185307179586 * kg_u2(w2, w3));
+  const double e = sigma * z;
+  return (int32_t)(uint32_t)(uint64_t)(int64_t)((e - trunc(e)) * 4294967296.0);
+}
+
+}  // namespace rs

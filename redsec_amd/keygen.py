@@ -1,0 +1,212 @@
+"""Evaluation-key generation on the device (rs_keygen_dev) and its numpy restatement.
+
+Every word of a generated key is a function of a 32-byte seed, the secret keys and the two noise deviations. The streams
+(specified in include/redsec_hip.h beside rs_keygen_dev and in csrc/rs_keygen.h):
+
+  Stream (domain, row): word w is word w & 15 of the ChaCha20 block of RFC 8439 section 2.3 whose key is the seed as 8
+  little-endian words, word 12 the block counter w >> 4, words 13, 14, 15 = domain, row & 0xffffffff, row >> 32.
+
+  domain 1 LWE secret    row 0                          s_i = word i & 1 (i < n)
+  domain 2 TRLWE secret  row 0                          S_j = word j & 1 (j < N)
+  domain 3 bk mask       row i 2l + p                   the N mask coefficients of TGSW row p = c l + j of s_i
+  domain 4 bk noise      row i 2l + p                   the N Gaussians of that row
+  domain 5 ksk mask      row (i t + j) 2^basebit + v    the n mask words of that sample
+  domain 6 ksk noise     same row                       1 Gaussian
+
+  Gaussian g of a row uses words 4g .. 4g+3: u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 1) 2^-53 in (0, 1],
+  u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53 in [0, 1), z = sqrt(-2 ln u1) cos(2 pi u2); the noise word is TFHE's
+  dtot32(sigma z) (client._gaussian32: fractional part truncated, times 2^32, to int64, wrapped to 32 bits).
+
+  bk row p = c l + j of key bit s_i is (a, b): a = the domain-3 mask, b = a*S + e (mod 2^32, negacyclic); then coefficient 0
+  of component c gains s_i 2^(32 - (j+1) Bgbit) (for c = 0, a[0] changes after b was formed).
+  ksk samples with v = 0 are all zero; v >= 1: a = the domain-5 words, b = sum_k a_k s_k + e + ((S_i v) << (32 - (j+1) basebit)).
+
+The noise words are restated with numpy's log / cos, which may differ from the device's in the last bit of z: a restated
+noise word can then differ by one from the device's in the rare case where sigma z 2^32 lies that close to an integer. Mask
+words, secret keys and noiseless keys are restated exactly.
+"""
+import os
+
+import numpy as np
+
+from . import client
+
+DOMAIN_LWE_SECRET, DOMAIN_TLWE_SECRET, DOMAIN_BK_MASK, DOMAIN_BK_NOISE, DOMAIN_KS_MASK, DOMAIN_KS_NOISE = 1, 2, 3, 4, 5, 6
+_SIGMA = b"expand 32-byte k"
+
+
+def _seed_words(seed):
+    seed = bytes(seed)
+    assert len(seed) == 32, "seed must be 32 bytes"
+    return np.frombuffer(seed, dtype="<u4").astype(np.uint32)
+
+
+def _rotl(v, c):
+    return (v << np.uint32(c)) | (v >> np.uint32(32 - c))
+
+
+def _chacha_blocks(key, domain, rows, blocks):
+    """ChaCha20 blocks for every (row, block) pair of the broadcast arrays `rows` (uint64) and `blocks` (uint32) -> [..., 16]."""
+    rows, blocks = np.broadcast_arrays(np.asarray(rows, np.uint64), np.asarray(blocks, np.uint32))
+    shape = rows.shape
+    const = np.frombuffer(_SIGMA, dtype="<u4").astype(np.uint32)
+    init = [np.full(shape, const[k], np.uint32) for k in range(4)] + [np.full(shape, key[k], np.uint32) for k in range(8)]
+    init += [blocks.astype(np.uint32), np.full(shape, np.uint32(domain & 0xFFFFFFFF), np.uint32),
+             (rows & np.uint64(0xFFFFFFFF)).astype(np.uint32), (rows >> np.uint64(32)).astype(np.uint32)]
+    x = [v.copy() for v in init]
+
+    def qr(a, b, c, d):
+        x[a] += x[b]; x[d] ^= x[a]; x[d] = _rotl(x[d], 16)
+        x[c] += x[d]; x[b] ^= x[c]; x[b] = _rotl(x[b], 12)
+        x[a] += x[b]; x[d] ^= x[a]; x[d] = _rotl(x[d], 8)
+        x[c] += x[d]; x[b] ^= x[c]; x[b] = _rotl(x[b], 7)
+    with np.errstate(over="ignore"):
+        for _ in range(10):
+            qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15)
+            qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
+        return np.stack([x[k] + init[k] for k in range(16)], axis=-1)
+
+
+def chacha20_words(seed, domain, row, count):
+    """Words [0, count) of stream (domain, row) -> uint32 [count], or [len(row)][count] for an array of rows."""
+    key = _seed_words(seed)
+    nblk = (int(count) + 15) // 16
+    rows = np.asarray(row, np.uint64)
+    out = _chacha_blocks(key, domain, rows[..., None], np.arange(nblk, dtype=np.uint32))
+    return out.reshape(rows.shape + (nblk * 16,))[..., :int(count)]
+
+
+def uniforms(w):
+    """(u1, u2) of the Gaussians whose words are w[..., 4g:4g+4] (uint32) -> two float64 arrays [..., G]."""
+    w = np.asarray(w, np.uint32).reshape(np.shape(w)[:-1] + (-1, 4)).astype(np.uint64)
+    u1 = (((w[..., 0] >> np.uint64(5)) << np.uint64(26)) + (w[..., 1] >> np.uint64(6)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53
+    u2 = (((w[..., 2] >> np.uint64(5)) << np.uint64(26)) + (w[..., 3] >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
+    return u1, u2
+
+
+def noise32(w, sigma):
+    """dtot32(sigma z) of the Gaussians made from the words w[..., 4g:4g+4] -> int32 [..., G]."""
+    u1, u2 = uniforms(w)
+    if sigma == 0:
+        return np.zeros(u1.shape, np.int32)
+    e = float(sigma) * (np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2))
+    frac = e - np.trunc(e)
+    return (frac * 4294967296.0).astype(np.int64).astype(np.uint64).astype(np.uint32).view(np.int32)
+
+
+def _shape(name, n=None):
+    (n0, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = client.PARAM_SETS[name]
+    return dict(n=int(n) if n is not None else n0, N=N, l=l, Bgbit=Bgbit, t=t, basebit=basebit, ks_stdev=ks_stdev, bk_stdev=bk_stdev)
+
+
+def set_name(p):
+    """The client.PARAM_SETS name of a parameter set (rs_params; n may be reduced): its ring, gadget and keyswitch shape."""
+    for name, (n0, N, k, l, Bgbit, t, basebit, _, _) in client.PARAM_SETS.items():
+        if (p.N, p.k, p.bk_l, p.bk_Bgbit, p.ks_t, p.ks_basebit) == (N, k, l, Bgbit, t, basebit):
+            return name
+    raise KeyError("no parameter set with N=%d l=%d Bgbit=%d t=%d basebit=%d" % (p.N, p.bk_l, p.bk_Bgbit, p.ks_t, p.ks_basebit))
+
+
+def secret_keys(name, seed, n=None):
+    """(lwe_key int32[n], tlwe_key int32[N]) of domains 1 and 2."""
+    s = _shape(name, n)
+    lwe = (chacha20_words(seed, DOMAIN_LWE_SECRET, 0, s["n"]) & 1).astype(np.int32)
+    tlwe = (chacha20_words(seed, DOMAIN_TLWE_SECRET, 0, s["N"]) & 1).astype(np.int32)
+    return lwe, tlwe
+
+
+def _times_binary(A, tlwe_key):
+    """Rows of A (uint32 [R][N]) times the binary polynomial S, negacyclic mod 2^32 -> uint32 [R][N]."""
+    N = A.shape[-1]
+    if N <= 1024:   # the exact float64 matrix product of client.py (an N x N matrix of 8 MB)
+        return client._mul_by_binary_poly(A.view(np.int32), client._negacyclic_matrix(np.asarray(tlwe_key))).view(np.uint32)
+    out = np.zeros_like(A)
+    with np.errstate(over="ignore"):
+        for m in np.flatnonzero(np.asarray(tlwe_key)):   # X^m a: a shifted up by m, the wrapped part negated
+            out[:, m:] += A[:, :N - m]
+            out[:, :m] -= A[:, N - m:]
+    return out
+
+
+def restate_bk(name, seed, lwe_key, tlwe_key, bk_stdev, rows=None, n=None, chunk=256):
+    """bk rows i 2l + p (all n 2l rows if rows is None) -> int32 [R][2][N]."""
+    s = _shape(name, n if n is not None else len(lwe_key))
+    l, Bgbit, N = s["l"], s["Bgbit"], s["N"]
+    rows = np.arange(s["n"] * 2 * l) if rows is None else np.asarray(rows, np.int64).ravel()
+    lwe = np.asarray(lwe_key).astype(np.uint32)
+    out = np.empty((len(rows), 2, N), np.int32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(rows), chunk):
+            r = rows[lo:lo + chunk]
+            A = chacha20_words(seed, DOMAIN_BK_MASK, r, N)
+            B = _times_binary(A, tlwe_key)
+            if bk_stdev:
+                B += noise32(chacha20_words(seed, DOMAIN_BK_NOISE, r, 4 * N), bk_stdev).view(np.uint32)
+            p = r % (2 * l)
+            c, j = p // l, p % l
+            gadget = lwe[r // (2 * l)] * (np.uint32(1) << (32 - (j + 1) * Bgbit).astype(np.uint32))
+            A[c == 0, 0] += gadget[c == 0]
+            B[c == 1, 0] += gadget[c == 1]
+            out[lo:lo + chunk, 0] = A.view(np.int32)
+            out[lo:lo + chunk, 1] = B.view(np.int32)
+    return out
+
+
+def restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev, rows=None, n=None, chunk=4096):
+    """ksk samples s = (i t + j) 2^basebit + v (all of them if rows is None) -> int32 [R][n+1]."""
+    s = _shape(name, n if n is not None else len(lwe_key))
+    n, N, t, basebit = s["n"], s["N"], s["t"], s["basebit"]
+    base = 1 << basebit
+    rows = np.arange(N * t * base) if rows is None else np.asarray(rows, np.int64).ravel()
+    lwe = np.asarray(lwe_key).astype(np.uint64)
+    tlwe = np.asarray(tlwe_key).astype(np.uint64)
+    out = np.zeros((len(rows), n + 1), np.int32)
+    for lo in range(0, len(rows), chunk):
+        r = rows[lo:lo + chunk]
+        v = r % base
+        live = np.flatnonzero(v != 0)
+        if len(live) == 0:
+            continue
+        rl = r[live]
+        A = chacha20_words(seed, DOMAIN_KS_MASK, rl, n)
+        dot = (A.astype(np.uint64) * lwe).sum(axis=-1)
+        e = noise32(chacha20_words(seed, DOMAIN_KS_NOISE, rl, 4), ks_stdev)[:, 0] if ks_stdev else np.zeros(len(rl), np.int32)
+        ij = rl >> basebit
+        i, j = ij // t, ij % t
+        mess = (tlwe[i] * (rl % base).astype(np.uint64)) << (32 - (j + 1) * basebit).astype(np.uint64)
+        b = (dot + e.view(np.uint32).astype(np.uint64) + mess) & np.uint64(0xFFFFFFFF)
+        out[lo + live, :n] = A.view(np.int32)
+        out[lo + live, n] = b.astype(np.uint32).view(np.int32)
+    return out
+
+
+def restate(name, seed, lwe_key, tlwe_key, bk_stdev, ks_stdev, rows=None):
+    """The key rs_keygen_dev writes, regenerated on the host. rows=None: the whole (bk [n][2l][2][N], ksk [N][t][2^basebit][n+1]);
+    rows=(bk_rows, ksk_rows): only those bk rows ([R][2][N]) and ksk samples ([R'][n+1]); either entry may be None (skipped).
+    The LWE dimension is len(lwe_key)."""
+    s = _shape(name, len(lwe_key))
+    if rows is None:
+        bk = restate_bk(name, seed, lwe_key, tlwe_key, bk_stdev).reshape(s["n"], 2 * s["l"], 2, s["N"])
+        ksk = restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev).reshape(s["N"], s["t"], 1 << s["basebit"], s["n"] + 1)
+        return bk, ksk
+    bk_rows, ksk_rows = rows
+    bk = None if bk_rows is None else restate_bk(name, seed, lwe_key, tlwe_key, bk_stdev, bk_rows)
+    ksk = None if ksk_rows is None else restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev, ksk_rows)
+    return bk, ksk
+
+
+def generate(backend, seed=None, bk_stdev=None, ks_stdev=None, load=True):
+    """Secret keys of domains 1 / 2 of `seed` (default os.urandom(32)) and the evaluation key generated on the backend's device
+    -> (client.SecretKeySet without an evaluation key, bk, ksk as int32 CUDA tensors). Deviations default to the set's
+    (client.PARAM_SETS). load=True also makes it the backend's key (rs_load_keys_dev). Client-side operation: see INTEGRATION.md."""
+    p = backend.p
+    name = set_name(p)
+    s = _shape(name, p.n)
+    seed = os.urandom(32) if seed is None else bytes(seed)
+    bk_stdev = s["bk_stdev"] if bk_stdev is None else bk_stdev
+    ks_stdev = s["ks_stdev"] if ks_stdev is None else ks_stdev
+    lwe, tlwe = secret_keys(name, seed, p.n)
+    bk, ksk = backend.keygen(lwe, tlwe, seed, bk_stdev, ks_stdev)
+    if load:
+        backend.load_keys_dev(bk, ksk)
+    return client.SecretKeySet.from_secret(name, lwe, tlwe), bk, ksk
