@@ -120,6 +120,30 @@ int rs_keygen_dev(rs_ctx* ctx, int32_t* bk, int32_t* ksk, const int32_t* lwe_key
 /* rs_load_keys with DEVICE pointers (no host round trip; the inputs are not modified). */
 int rs_load_keys_dev(rs_ctx* ctx, const int32_t* bk, const int32_t* ksk);
 
+/* Compressed evaluation key: a public 32-byte MASK SEED plus the bodies, 1/8 to 1/6 of the bytes of the
+ * full key. It is another encryption of the same key, with the gadget term of c = 0 rows moved out of the public mask:
+ *   bk row p = c l + j of key bit s_i (row i 2l + p):  a = the domain-3 stream of the mask seed (stored unchanged),
+ *     b = a*S + e + s_i g_j X^0 (c = 1),  b = a*S + e - s_i g_j S (c = 0),  g_j = 2^(32 - (j+1) Bgbit),  e = domain 4 of the noise seed.
+ *     Its phase is that of the rs_keygen_dev row; their difference is -s_i g_j (1, S) for c = 0, an exact encryption of zero.
+ *   ksk sample s = (i t + j) 2^basebit + v:  a = the domain-5 stream of the mask seed, b as in rs_keygen_dev with e = domain 6 of
+ *     the noise seed; samples with v = 0 are all zero (their body word is 0 and is ignored).
+ * The NOISE SEED (domains 1, 2, 4, 6) stays private; equal seeds would publish the noise, hence the secret, and are refused.
+ * Layouts: bk_body int32[n][2l][N], ksk_body int32[N][t][2^basebit], mask_seed 32 bytes.
+ *
+ * rs_keygen_compressed_dev: the bodies, generated on the device under rs_keygen_dev's contract (CLIENT side): lwe_key / tlwe_key
+ * HOST, bk_body / ksk_body DEVICE (bk_body 16-byte aligned); RS_ERR_INVALID as rs_keygen_dev and for equal seeds; RS_ERR_INEXACT
+ * as rs_keygen_dev. The secret's device copy is zeroed and freed on every path. Needs the split-key product.
+ * rs_expand_keys_dev: the full key (layouts of rs_load_keys) from the mask seed and the bodies; every pointer DEVICE, bk 16-byte
+ * aligned. Needs no product: works on every context. Synchronous.
+ * rs_load_compressed_keys (HOST bodies) / rs_load_compressed_keys_dev (DEVICE bodies): rs_load_keys of the expanded key (SERVER
+ * side); the expansion happens on the device, the full key never exists on the host. A failed load, invalid arguments included,
+ * leaves the context with no key. */
+int rs_keygen_compressed_dev(rs_ctx* ctx, int32_t* bk_body, int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
+                             const uint8_t* mask_seed, const uint8_t* noise_seed, double bk_stdev, double ks_stdev);
+int rs_expand_keys_dev(rs_ctx* ctx, int32_t* bk, int32_t* ksk, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body);
+int rs_load_compressed_keys(rs_ctx* ctx, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body);
+int rs_load_compressed_keys_dev(rs_ctx* ctx, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body);
+
 /* Arithmetic of the external product (both keys are resident after rs_load_keys; switching is free):
  *   RS_MODE_FFT        folded 512-point complex FP64 FFT -- the arithmetic class of TFHE's own
  *                      tGswFFTExternMulToTLwe -- rounded to the nearest integer. The true product is an

@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "rs_bootstrap_lut_dev", "rs_set_certificate_limit", "rs_certify", "rs_reserve_stream", "rs_last_kernel_ms_stream", "rs_last_launch", "rs_copy_dev_to_dev",
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
+    "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -89,6 +90,10 @@ def load_library(path=None):
     L.rs_load_synthetic_keys.argtypes = [vp, C.c_uint64]
     L.rs_load_keys_dev.argtypes = [vp, vp, vp]
     L.rs_keygen_dev.argtypes = [vp, vp, vp, _i32p, _i32p, C.c_char_p, C.c_double, C.c_double]
+    L.rs_keygen_compressed_dev.argtypes = [vp, vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
+    L.rs_expand_keys_dev.argtypes = [vp, vp, vp, C.c_char_p, vp, vp]
+    L.rs_load_compressed_keys.argtypes = [vp, C.c_char_p, _i32p, _i32p]
+    L.rs_load_compressed_keys_dev.argtypes = [vp, C.c_char_p, vp, vp]
     L.rs_reserve.argtypes = [vp, C.c_size_t]
     L.rs_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_bootstrap.argtypes = [vp, _i32p, _i32p, C.c_int32, C.c_size_t]
@@ -246,6 +251,62 @@ class Backend:
         assert bk.numel() == nb and ksk.numel() == nk, "key tensors have the wrong size"
         _check(self.L, self.L.rs_keygen_dev(self.h, self._ck_dev(bk), self._ck_dev(ksk), plwe, ptlwe, seed, float(bk_stdev), float(ks_stdev)))
         return bk, ksk
+
+    def _body_sizes(self):
+        p = self.p
+        return p.n * 2 * p.bk_l * p.N, p.N * p.ks_t * (1 << p.ks_basebit)
+
+    @staticmethod
+    def _seed32(seed, what="seed"):
+        seed = bytes(seed)
+        assert len(seed) == 32, what + " must be 32 bytes"
+        return seed
+
+    def keygen_compressed(self, lwe_key, tlwe_key, mask_seed, noise_seed, bk_stdev, ks_stdev, bk_body=None, ksk_body=None):
+        """Bodies of a compressed evaluation key generated on the device (rs_keygen_compressed_dev) -> (bk_body [n][2l][N],
+        ksk_body [N][t][2^basebit]) int32 CUDA tensors (or into the given ones). The masks are those of mask_seed (public); the
+        noise comes from noise_seed (private, must differ). Does not load the key."""
+        p = self.p
+        lwe, plwe = _np_i32(lwe_key)
+        tlwe, ptlwe = _np_i32(tlwe_key)
+        assert lwe.size == p.n and tlwe.size == p.N, "secret keys have the wrong size"
+        mask_seed, noise_seed = self._seed32(mask_seed, "mask_seed"), self._seed32(noise_seed, "noise_seed")
+        bk_body = self.empty(p.n, 2 * p.bk_l, p.N) if bk_body is None else bk_body
+        ksk_body = self.empty(p.N, p.ks_t, 1 << p.ks_basebit) if ksk_body is None else ksk_body
+        nb, nk = self._body_sizes()
+        assert bk_body.numel() == nb and ksk_body.numel() == nk, "body tensors have the wrong size"
+        _check(self.L, self.L.rs_keygen_compressed_dev(self.h, self._ck_dev(bk_body), self._ck_dev(ksk_body), plwe, ptlwe, mask_seed,
+                                                       noise_seed, float(bk_stdev), float(ks_stdev)))
+        return bk_body, ksk_body
+
+    def expand_keys(self, mask_seed, bk_body, ksk_body, bk=None, ksk=None):
+        """The full evaluation key of a compressed one, expanded on the device (rs_expand_keys_dev) -> (bk [n][2l][2][N],
+        ksk [N][t][2^basebit][n+1]) int32 CUDA tensors (or into the given ones). Does not load the key."""
+        p = self.p
+        mask_seed = self._seed32(mask_seed, "mask_seed")
+        nb, nk = self._body_sizes()
+        assert bk_body.numel() == nb and ksk_body.numel() == nk, "body tensors have the wrong size"
+        bk = self.empty(p.n, 2 * p.bk_l, 2, p.N) if bk is None else bk
+        ksk = self.empty(p.N, p.ks_t, 1 << p.ks_basebit, p.n + 1) if ksk is None else ksk
+        fb, fk = self._key_sizes()
+        assert bk.numel() == fb and ksk.numel() == fk, "key tensors have the wrong size"
+        _check(self.L, self.L.rs_expand_keys_dev(self.h, self._ck_dev(bk), self._ck_dev(ksk), mask_seed, self._ck_dev(bk_body),
+                                                 self._ck_dev(ksk_body)))
+        return bk, ksk
+
+    def load_compressed_keys(self, mask_seed, bk_body, ksk_body):
+        """Loads a compressed evaluation key, expanded on the device: numpy bodies go through rs_load_compressed_keys (host),
+        CUDA tensors through rs_load_compressed_keys_dev. The full key never exists on the host."""
+        mask_seed = self._seed32(mask_seed, "mask_seed")
+        nb, nk = self._body_sizes()
+        if isinstance(bk_body, np.ndarray) or isinstance(ksk_body, np.ndarray):
+            bk_body, pbk = _np_i32(bk_body)
+            ksk_body, pksk = _np_i32(ksk_body)
+            assert bk_body.size == nb and ksk_body.size == nk, "bodies have the wrong size"
+            _check(self.L, self.L.rs_load_compressed_keys(self.h, mask_seed, pbk, pksk))
+        else:
+            assert bk_body.numel() == nb and ksk_body.numel() == nk, "bodies have the wrong size"
+            _check(self.L, self.L.rs_load_compressed_keys_dev(self.h, mask_seed, self._ck_dev(bk_body), self._ck_dev(ksk_body)))
 
     def load_synthetic_keys(self, seed):
         """A key of pseudo-random words generated ON THE DEVICE (rs_load_synthetic_keys; client.synthetic_key_words restates the

@@ -176,7 +176,7 @@ LAYERS_LIB = os.path.join(HERE, "libredsec_layers.so")
 LAYERS_SOURCES = [os.path.join(HOST, "tfhe_shim.cpp"), os.path.join(HOST, "layers.cpp")]
 LAYERS_DEPS = LAYERS_SOURCES + [os.path.join(HOST, "tfhe", f) for f in ("tfhe.h", "tfhe_io.h", "tfhe_garbage_collector.h")] + \
     [os.path.join(HOST, "lib", f) for f in ("Layer.h", "BinLayer.h", "IntLayer.h", "BinOps_enc.h", "IntOps_enc.h", "BinFunc.h", "IntFunc.h")] + \
-    [os.path.join(INCLUDE, "redsec_hip.h")]
+    [os.path.join(INCLUDE, "redsec_hip.h"), os.path.join(CSRC, "rs_keygen.h"), os.path.join(CSRC, "rs_ntt.h")]
 
 
 def build_layers(force=False, verbose=False):
@@ -190,7 +190,7 @@ def build_layers(force=False, verbose=False):
         if not force and not _stale(LAYERS_LIB, LAYERS_DEPS):
             return LAYERS_LIB
         tmp = LAYERS_LIB + ".tmp.%d" % os.getpid()
-        cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result", "-I" + HOST, "-I" + INCLUDE] + LAYERS_SOURCES + \
+        cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result", "-Wno-unknown-pragmas", "-I" + HOST, "-I" + INCLUDE, "-I" + CSRC] + LAYERS_SOURCES + \
               ["-L" + HERE, "-lredsec_hip", "-Wl,-rpath,$ORIGIN", "-o", tmp]
         if verbose:
             print(" ".join(cmd))

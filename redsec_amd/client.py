@@ -241,6 +241,45 @@ def read_tfhe_keyset(f, secret):
     return out
 
 
+# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key; redsec_amd/host/
+# tfhe_shim.cpp ParamHeader): magic, int32 n, N, k, l, Bgbit, ks_t, ks_basebit, then double lwe alpha min / max, tlwe alpha min / max.
+_RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
+                       ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
+                       ("tlwe_alpha_max", "<f8")])
+RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352}
+
+
+def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
+    """A compressed cloud key file (binary file object): the RSK1 header with magic RSZ1, the 32-byte mask seed, then the raw
+    bodies bk_body [n][2l][N] and ksk_body [N][t][2^basebit] (int32). ck: redsec_amd.keygen.CompressedKey."""
+    (_, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = PARAM_SETS[ck.name]
+    h = np.zeros((), _RS_HEADER)
+    h["magic"], h["n"], h["N"], h["k"], h["l"], h["Bgbit"], h["ks_t"], h["ks_basebit"] = RS_MAGIC["RSZ1"], ck.n, N, k, l, Bgbit, t, basebit
+    h["lwe_alpha_min"], h["lwe_alpha_max"], h["tlwe_alpha_min"], h["tlwe_alpha_max"] = ks_stdev, max_stdev, bk_stdev, max_stdev
+    host = ck.numpy()
+    f.write(h.tobytes())
+    f.write(host.mask_seed)
+    f.write(np.ascontiguousarray(host.bk_body, np.int32).tobytes())
+    f.write(np.ascontiguousarray(host.ksk_body, np.int32).tobytes())
+
+
+def read_compressed_cloud_key(f):
+    """-> redsec_amd.keygen.CompressedKey of an RSZ1 file (numpy bodies)."""
+    from . import keygen
+    h = np.frombuffer(f.read(_RS_HEADER.itemsize), _RS_HEADER)[0]
+    assert int(h["magic"]) == RS_MAGIC["RSZ1"], "not a compressed cloud key file"
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    assert name is not None, "no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,)
+    n, N, l, t, basebit = int(h["n"]), shape[0], shape[2], shape[4], shape[5]
+    seed = f.read(32)
+    rd = lambda count: np.frombuffer(f.read(4 * count), np.int32)
+    bk_body = rd(n * 2 * l * N).reshape(n, 2 * l, N)
+    ksk_body = rd(N * t * (1 << basebit)).reshape(N, t, 1 << basebit)
+    assert f.read(1) == b"", "trailing bytes in compressed key file"
+    return keygen.CompressedKey(name, n, seed, bk_body, ksk_body)
+
+
 def write_ciphertexts(f, ct):
     """export_gate_bootstrapping_ciphertext_toFile per row of ct [B][n+1]: uid 42, a[n], b, double variance."""
     ct = np.ascontiguousarray(ct, np.int32)

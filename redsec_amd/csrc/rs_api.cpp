@@ -24,6 +24,7 @@
 #include "rs_host.h"
 #include "rs_general.h"
 #include "rs_kernels.h"
+#include "rs_keygen.h"
 
 namespace {
 
@@ -516,7 +517,7 @@ int rs_destroy(rs_ctx* c) {
 }
 
 // where load_keys_impl takes the key words from
-enum class KeySource { kHost, kDevice, kSynthetic };
+enum class KeySource { kHost, kDevice, kSynthetic, kCompressedHost, kCompressedDevice };
 
 // drops every key buffer of the context (a failed load leaves no half-built transform key behind)
 static void free_keys(rs_ctx* c) {
@@ -528,21 +529,47 @@ static void free_keys(rs_ctx* c) {
   c->bk_bytes = c->ksk_bytes = 0;
 }
 
-// bk / ksk: host arrays, device arrays, or unused for the synthetic key of `seed` generated on the device (rs_load_synthetic_keys)
-static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int32_t* ksk, uint64_t seed) {
+// the expansion arguments of this context's parameter set (outputs and bodies filled in by the caller)
+static rs::ExpandArgs expand_args(const rs_ctx* c, const uint8_t* mask_seed) {
+  rs::ExpandArgs e{};
+  rs::kg_seed_words(mask_seed, e.seed);
+  e.n = c->p.n; e.N = c->p.N; e.l = c->p.bk_l; e.t = c->p.ks_t; e.basebit = c->p.ks_basebit;
+  return e;
+}
+
+// bk / ksk: host arrays, device arrays, unused for the synthetic key of `seed` generated on the device (rs_load_synthetic_keys),
+// or the bodies of a compressed key (host or device) whose masks are regenerated from mask_seed
+static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int32_t* ksk, uint64_t seed,
+                          const uint8_t* mask_seed = nullptr) {
   int rc = use_device(c);
   if (rc) return rc;
   if (src != KeySource::kSynthetic && (!bk || !ksk)) return fail(RS_ERR_INVALID, "null key pointer");
+  const bool compressed = src == KeySource::kCompressedHost || src == KeySource::kCompressedDevice;
+  if (compressed && !mask_seed) return fail(RS_ERR_INVALID, "null mask seed");
   const rs_params& p = c->p;
   const size_t n_polys = (size_t)p.n * (size_t)(2 * p.bk_l) * 2;
   const size_t bk_words = n_polys * (size_t)p.N;
-  const size_t ksk_words = (size_t)p.N * p.ks_t * ((size_t)1 << p.ks_basebit) * (size_t)(p.n + 1);
+  const size_t ksk_samples = (size_t)p.N * p.ks_t * ((size_t)1 << p.ks_basebit);
+  const size_t ksk_words = ksk_samples * (size_t)(p.n + 1);
   free_keys(c);
-  int32_t* d_bk = nullptr;   // staging copy of the key words (freed on every path)
+  int32_t* d_bk = nullptr;     // staging copy of the key words (freed on every path)
+  int32_t* d_body = nullptr;   // staging copy of host bodies of a compressed key (freed on every path)
   auto body = [&]() -> int {
     RS_HIP(hipMalloc(&d_bk, bk_words * sizeof(int32_t)));
     if (src == KeySource::kSynthetic) RS_HIP(rs::launch_synthetic_words(d_bk, seed, bk_words, nullptr));
-    else RS_HIP(hipMemcpy(d_bk, bk, bk_words * sizeof(int32_t), src == KeySource::kHost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+    else if (compressed) {
+      const int32_t* bk_body = bk;
+      if (src == KeySource::kCompressedHost) {
+        RS_HIP(hipMalloc(&d_body, bk_words / 2 * sizeof(int32_t)));
+        RS_HIP(hipMemcpy(d_body, bk, bk_words / 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+        bk_body = d_body;
+      }
+      rs::ExpandArgs e = expand_args(c, mask_seed);
+      e.bk = d_bk; e.bk_body = bk_body;
+      RS_HIP(rs::launch_expand_bk(c->logn, e, c->num_cus, nullptr));
+      RS_HIP(hipDeviceSynchronize());
+      if (d_body) { RS_HIP(hipFree(d_body)); d_body = nullptr; }
+    } else RS_HIP(hipMemcpy(d_bk, bk, bk_words * sizeof(int32_t), src == KeySource::kHost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
     if (!c->general) {
       // both transform domains are kept resident (62 + 62 MB default-128, 115 + 115 MB REDsec): the FFT mode's
       // gated exact recomputation needs the NTT-domain key, and the mode can be switched per call
@@ -564,7 +591,20 @@ static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int
     RS_HIP(hipMalloc(&c->d_ksk, ksk_words * sizeof(int32_t)));
     if (src == KeySource::kSynthetic) { RS_HIP(rs::launch_synthetic_words(c->d_ksk, seed ^ 0x6b73ull, ksk_words, nullptr)); RS_HIP(hipDeviceSynchronize()); }
     else if (src == KeySource::kHost) RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyHostToDevice));
-    else { RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyDeviceToDevice)); RS_HIP(hipDeviceSynchronize()); }
+    else if (src == KeySource::kDevice) { RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyDeviceToDevice)); RS_HIP(hipDeviceSynchronize()); }
+    else {
+      const int32_t* ksk_body = ksk;
+      if (src == KeySource::kCompressedHost) {
+        RS_HIP(hipMalloc(&d_body, ksk_samples * sizeof(int32_t)));
+        RS_HIP(hipMemcpy(d_body, ksk, ksk_samples * sizeof(int32_t), hipMemcpyHostToDevice));
+        ksk_body = d_body;
+      }
+      rs::ExpandArgs e = expand_args(c, mask_seed);
+      e.ksk = c->d_ksk; e.ksk_body = ksk_body;
+      RS_HIP(rs::launch_expand_ksk(e, c->num_cus, nullptr));
+      RS_HIP(hipDeviceSynchronize());
+      if (d_body) { RS_HIP(hipFree(d_body)); d_body = nullptr; }
+    }
     c->ksk_bytes = ksk_words * sizeof(int32_t);
     return RS_OK;
   };
@@ -572,6 +612,7 @@ static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int
   if (rc != RS_OK) {
     (void)hipDeviceSynchronize();
     if (d_bk) (void)hipFree(d_bk);
+    if (d_body) (void)hipFree(d_body);
     free_keys(c);
     return rc;
   }
@@ -588,13 +629,30 @@ int rs_load_keys_dev(rs_ctx* c, const int32_t* bk, const int32_t* ksk) {
   return load_keys_impl(c, KeySource::kDevice, bk, ksk, 0);
 }
 int rs_load_synthetic_keys(rs_ctx* c, uint64_t seed) { return load_keys_impl(c, KeySource::kSynthetic, nullptr, nullptr, seed); }
-
-int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
-                  double bk_stdev, double ks_stdev) {
+// a failed compressed load leaves no key, invalid arguments included
+static int load_compressed(rs_ctx* c, KeySource src, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
   int rc = use_device(c);
   if (rc) return rc;
+  if (!mask_seed || !bk_body || !ksk_body) { free_keys(c); return fail(RS_ERR_INVALID, "null pointer"); }
+  return load_keys_impl(c, src, bk_body, ksk_body, 0, mask_seed);
+}
+int rs_load_compressed_keys(rs_ctx* c, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
+  return load_compressed(c, KeySource::kCompressedHost, mask_seed, bk_body, ksk_body);
+}
+int rs_load_compressed_keys_dev(rs_ctx* c, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
+  return load_compressed(c, KeySource::kCompressedDevice, mask_seed, bk_body, ksk_body);
+}
+
+// rs_keygen_dev (noise_seed null) and rs_keygen_compressed_dev (the bodies only, masks of `seed`, noise of noise_seed)
+static int keygen_impl(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
+                       const uint8_t* noise_seed, double bk_stdev, double ks_stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  const bool compressed = noise_seed != nullptr;
   if (!bk || !ksk || !lwe_key || !tlwe_key || !seed) return fail(RS_ERR_INVALID, "null pointer");
   if (((uintptr_t)bk & 15u) != 0) return fail(RS_ERR_INVALID, "bk must be 16-byte aligned");
+  if (compressed && memcmp(seed, noise_seed, 32) == 0)
+    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
   if (!(std::isfinite(bk_stdev) && bk_stdev >= 0.0) || !(std::isfinite(ks_stdev) && ks_stdev >= 0.0))
     return fail(RS_ERR_INVALID, "noise deviations must be finite and non-negative (bk %g, ks %g)", bk_stdev, ks_stdev);
   if (!c->d_tw_gen) return fail(RS_ERR_INVALID, "split-key product not offered for this set: a-priori bound %.3g", c->split_bound);
@@ -612,8 +670,9 @@ int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, 
   a.bk = bk; a.ksk = ksk;
   a.lwe_key = reinterpret_cast<const int32_t*>(d_sec);
   a.tlwe_key = a.lwe_key + p.n;
-  for (int k = 0; k < 8; ++k)
-    a.seed[k] = (uint32_t)seed[4 * k] | ((uint32_t)seed[4 * k + 1] << 8) | ((uint32_t)seed[4 * k + 2] << 16) | ((uint32_t)seed[4 * k + 3] << 24);
+  rs::kg_seed_words(seed, a.seed);
+  if (compressed) rs::kg_seed_words(noise_seed, a.noise_seed);
+  a.compressed = compressed ? 1 : 0;
   a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
   a.bk_sigma = bk_stdev; a.ks_sigma = ks_stdev;
   a.dev_flag = reinterpret_cast<unsigned long long*>(d_sec + key_bytes);
@@ -640,6 +699,29 @@ int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, 
   memcpy(&dist, &flag, sizeof dist);
   if (!(dist < rs::kSplitBoundEnforce))
     return fail(RS_ERR_INEXACT, "key generation: a rounding distance of %.3g was observed in the a*S products (limit 1/4)", dist);
+  return RS_OK;
+}
+
+int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
+                  double bk_stdev, double ks_stdev) {
+  return keygen_impl(c, bk, ksk, lwe_key, tlwe_key, seed, nullptr, bk_stdev, ks_stdev);
+}
+int rs_keygen_compressed_dev(rs_ctx* c, int32_t* bk_body, int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
+                             const uint8_t* mask_seed, const uint8_t* noise_seed, double bk_stdev, double ks_stdev) {
+  if (!noise_seed) return fail(RS_ERR_INVALID, "null pointer");
+  return keygen_impl(c, bk_body, ksk_body, lwe_key, tlwe_key, mask_seed, noise_seed, bk_stdev, ks_stdev);
+}
+
+int rs_expand_keys_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!bk || !ksk || !mask_seed || !bk_body || !ksk_body) return fail(RS_ERR_INVALID, "null pointer");
+  if (((uintptr_t)bk & 15u) != 0) return fail(RS_ERR_INVALID, "bk must be 16-byte aligned");
+  rs::ExpandArgs e = expand_args(c, mask_seed);
+  e.bk = bk; e.ksk = ksk; e.bk_body = bk_body; e.ksk_body = ksk_body;
+  RS_HIP(rs::launch_expand_bk(c->logn, e, c->num_cus, nullptr));
+  RS_HIP(rs::launch_expand_ksk(e, c->num_cus, nullptr));
+  RS_HIP(hipDeviceSynchronize());
   return RS_OK;
 }
 

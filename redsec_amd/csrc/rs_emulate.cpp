@@ -1133,4 +1133,41 @@ void rs_emu_keygen_uniforms(const uint32_t* w4, double* u1u2) {
 }
 int32_t rs_emu_keygen_noise(const uint32_t* w4, double sigma) { return rs::kg_noise32(w4[0], w4[1], w4[2], w4[3], sigma); }
 
+// expansion of a compressed key (rs_expand_keys_dev) through the device functions its kernels call, lane by lane: one bk row
+// (expand_bk_kernel: thread t of N / 16 stores mask block t, the body is copied word t + T r) -> out[2][N]
+void rs_emu_expand_bk_row(const uint8_t* mask_seed, int N, uint64_t row, const int32_t* body_row, int32_t* out) {
+  uint32_t key[8];
+  rs::kg_seed_words(mask_seed, key);
+  const int T = N / 16;
+  for (int t = 0; t < T; ++t) {
+    uint32_t w[16];
+    rs::kg_bk_mask_block(key, row, t, w);
+    for (int k = 0; k < 16; ++k) out[16 * t + k] = (int32_t)w[k];
+    for (int r = 0; r < 16; ++r) out[N + t + T * r] = body_row[t + T * r];
+  }
+}
+// one ksk sample s (expand_ksk_kernel: the 64 lanes of a wave, chunk by chunk through the LDS transpose) -> out[n + 1]
+void rs_emu_expand_ksk_sample(const uint8_t* mask_seed, int n, int basebit, uint64_t s, int32_t body, int32_t* out) {
+  if ((s & ((1ull << basebit) - 1)) == 0) {
+    for (int k = 0; k <= n; ++k) out[k] = 0;
+    return;
+  }
+  uint32_t key[8];
+  rs::kg_seed_words(mask_seed, key);
+  std::vector<uint32_t> buf(rs::kKgChunk);
+  for (int k0 = 0; k0 < n; k0 += rs::kKgChunk) {
+    for (int lane = 0; lane < 64; ++lane) {
+      uint32_t w[16] = {};
+      rs::kg_ksk_mask_block(key, s, k0, lane, n, w);
+      for (int q = 0; q < 16; ++q) buf[16 * lane + q] = w[q];
+    }
+    for (int q = 0; q < 16; ++q)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int idx = rs::kg_ksk_chunk_word(q, lane), k = k0 + idx;
+        if (k < n) out[k] = (int32_t)buf[idx];
+      }
+  }
+  out[n] = body;
+}
+
 }  // extern "C"

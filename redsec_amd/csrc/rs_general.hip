@@ -7,6 +7,8 @@
 //   gen_polymul_kernel         debug/parity tap through the same transform path
 //   gen_keygen_bk_kernel       evaluation-key generation: TGSW rows of the bootstrapping key, b = a*S + e through the same product
 //   keygen_ksk_kernel          evaluation-key generation: keyswitching-key samples (integer stream work)
+//   expand_bk_kernel           compressed-key expansion: bk masks regenerated from the mask seed, bodies copied beside them
+//   expand_ksk_kernel          compressed-key expansion: ksk masks regenerated from the mask seed, bodies copied beside them
 //
 // One workgroup of T = N/16 threads owns one ciphertext: its TRLWE accumulator (2 x N int32) and the two exchange
 // planes live in LDS (17 N bytes), every thread keeps 8 complex values of the transform in flight and the
@@ -391,6 +393,8 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_polymul_kernel(const int32_t
 // the torus operand (the mask) is split into 16-bit halves, S is the small one. |half| <= 2^15 and S binary keep every half-product
 // coefficient below N 2^15 -- far inside the products gen_error_bound covers (2l rows of Bg/2-digits times 2^15-halves) -- so
 // rounding is exact; the distances are still published through dev_flag like every other general-ring product.
+// a.compressed (rs_keygen_compressed_dev): the noise comes from the noise seed, the c = 0 gadget term enters the body as
+// -s_i 2^(32 - (j+1) Bgbit) S instead of the mask, and only the body is written, to a.bk + row N.
 template <int LOGN>
 __global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs a, const double* __restrict__ tw) {
   using G = Gen<LOGN>;
@@ -402,14 +406,20 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs 
   auto sync = [] { gen_sync<T>(); };
   auto wsync = [] { gen_wave_sync(); };
   const double* twn = gen_stage_twiddles<LOGN>(s_twn, tw, t);
-  uint32_t key[8];
+  uint32_t key[8], nkey[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  for (int k = 0; k < 8; ++k) { key[k] = a.seed[k]; nkey[k] = a.compressed ? a.noise_seed[k] : a.seed[k]; }
   const bool noisy = a.bk_sigma != 0.0;
+  const bool compressed = a.compressed != 0;
   // S in the transform domain, scaled by 1/M (a power of two: exact); kept in registers for all rows of this workgroup
   double sx[kRegs];
+  uint32_t sbits = 0;   // bit r = S[t + T r], the coefficients this thread writes (the compressed body's -gadget S term)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) sx[r] = (double)a.tlwe_key[t + T * r];
+  for (int r = 0; r < 16; ++r) {
+    const int32_t sr = a.tlwe_key[t + T * r];
+    sx[r] = (double)sr;
+    sbits |= (uint32_t)(sr & 1) << r;
+  }
   gen_fft_fwd<LOGN>(sx, t, tw, twn, s_re, s_im, sync, wsync);
 #pragma unroll
   for (int r = 0; r < 16; ++r) sx[r] *= 1.0 / M;
@@ -419,23 +429,25 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs 
     const int i = (int)(row / (2 * a.l)), p = (int)(row % (2 * a.l)), c = p / a.l, j = p % a.l;
     const uint32_t gadget = a.lwe_key[i] ? (1u << (32 - (j + 1) * a.bgbit)) : 0u;
     int32_t* pa = a.bk + (size_t)row * 2 * N;
-    int32_t* pb = pa + N;
+    int32_t* pb = compressed ? a.bk + (size_t)row * N : pa + N;
     {
       uint32_t w[16];
-      kg_chacha_block(key, kKgBkMask, (uint64_t)row, (uint32_t)t, w);
+      kg_bk_mask_block(key, (uint64_t)row, t, w);
 #pragma unroll
       for (int k = 0; k < 16; ++k) s_mask[16 * t + k] = w[k];
-      // the stored mask of a c = 0 row carries the gadget term on coefficient 0 (added after b is formed from the plain mask)
-      const uint32_t w0 = w[0] + ((t == 0 && c == 0) ? gadget : 0u);
-      int4* dst = reinterpret_cast<int4*>(pa) + 4 * t;
-      dst[0] = make_int4((int)w0, (int)w[1], (int)w[2], (int)w[3]);
-      dst[1] = make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]);
-      dst[2] = make_int4((int)w[8], (int)w[9], (int)w[10], (int)w[11]);
-      dst[3] = make_int4((int)w[12], (int)w[13], (int)w[14], (int)w[15]);
+      if (!compressed) {
+        // the stored mask of a c = 0 row carries the gadget term on coefficient 0 (added after b is formed from the plain mask)
+        const uint32_t w0 = w[0] + ((t == 0 && c == 0) ? gadget : 0u);
+        int4* dst = reinterpret_cast<int4*>(pa) + 4 * t;
+        dst[0] = make_int4((int)w0, (int)w[1], (int)w[2], (int)w[3]);
+        dst[1] = make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]);
+        dst[2] = make_int4((int)w[8], (int)w[9], (int)w[10], (int)w[11]);
+        dst[3] = make_int4((int)w[12], (int)w[13], (int)w[14], (int)w[15]);
+      }
       if (noisy) {
 #pragma unroll 1
         for (int g4 = 0; g4 < 4; ++g4) {
-          kg_chacha_block(key, kKgBkNoise, (uint64_t)row, (uint32_t)(4 * t + g4), w);
+          kg_chacha_block(nkey, kKgBkNoise, (uint64_t)row, (uint32_t)(4 * t + g4), w);
 #pragma unroll
           for (int q = 0; q < 4; ++q) s_noise[16 * t + 4 * g4 + q] = (uint32_t)kg_noise32(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], a.bk_sigma);
         }
@@ -470,6 +482,7 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs 
     for (int r = 0; r < 16; ++r) {
       const int jj = t + T * r;
       b[r] += ((uint32_t)fft_round_torus32(S[1][r], dev) << 16) + ((jj == 0 && c == 1) ? gadget : 0u);
+      if (compressed && c == 0 && ((sbits >> r) & 1u)) b[r] -= gadget;
       if (noisy) b[r] += s_noise[jj];
       pb[jj] = (int32_t)b[r];
     }
@@ -481,40 +494,42 @@ __global__ __launch_bounds__(Gen<LOGN>::T) void gen_keygen_bk_kernel(KeygenArgs 
 // Keyswitching-key samples (rs_keygen_dev): one wave per sample s = (i t + j) 2^basebit + v, which is also its row in domains 5 / 6.
 // Lane L generates block 64 m + L of the mask; the words pass through LDS so that the stores and the reads of the LWE key are
 // coalesced, and a wave reduction gives sum a_k s_k mod 2^32. Samples with v = 0 are written as zeros.
+// a.compressed (rs_keygen_compressed_dev): the noise comes from the noise seed and only the body is written, to a.ksk[s].
 constexpr int kKgWaves = 4;
 __global__ __launch_bounds__(64 * kKgWaves) void keygen_ksk_kernel(KeygenArgs a) {
-  __shared__ uint32_t s_w[kKgWaves][64 * 16];
+  __shared__ uint32_t s_w[kKgWaves][kKgChunk];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t* buf = s_w[wv];
-  uint32_t key[8];
+  uint32_t key[8], nkey[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  for (int k = 0; k < 8; ++k) { key[k] = a.seed[k]; nkey[k] = a.compressed ? a.noise_seed[k] : a.seed[k]; }
+  const bool compressed = a.compressed != 0;
   const int base = 1 << a.basebit, W = a.n + 1;
   const long samples = (long)a.N * a.t * base;
   for (long s = (long)blockIdx.x * kKgWaves + wv; s < samples; s += (long)gridDim.x * kKgWaves) {
     int32_t* out = a.ksk + (size_t)s * W;
     const int v = (int)(s & (base - 1));
     if (v == 0) {
-      for (int k = lane; k < W; k += 64) out[k] = 0;
+      if (compressed) { if (lane == 0) a.ksk[s] = 0; }
+      else for (int k = lane; k < W; k += 64) out[k] = 0;
       continue;
     }
     const long ij = s >> a.basebit;
     const int i = (int)(ij / a.t), j = (int)(ij % a.t);
     uint32_t acc = 0;
     uint32_t w[16];
-    for (int k0 = 0; k0 < a.n; k0 += 64 * 16) {
-      const int blk = k0 / 16 + lane;
-      if (16 * blk < a.n) kg_chacha_block(key, kKgKsMask, (uint64_t)s, (uint32_t)blk, w);
+    for (int k0 = 0; k0 < a.n; k0 += kKgChunk) {
+      kg_ksk_mask_block(key, (uint64_t)s, k0, lane, a.n, w);
       gen_wave_sync();   // this wave's reads of the previous chunk are done
 #pragma unroll
       for (int q = 0; q < 16; ++q) buf[16 * lane + q] = w[q];
       gen_wave_sync();
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const int idx = 64 * q + lane, k = k0 + idx;
+        const int idx = kg_ksk_chunk_word(q, lane), k = k0 + idx;
         if (k < a.n) {
           const uint32_t x = buf[idx];
-          out[k] = (int32_t)x;
+          if (!compressed) out[k] = (int32_t)x;
           acc += a.lwe_key[k] ? x : 0u;
         }
       }
@@ -524,11 +539,76 @@ __global__ __launch_bounds__(64 * kKgWaves) void keygen_ksk_kernel(KeygenArgs a)
     if (lane == 0) {
       uint32_t e = 0;
       if (a.ks_sigma != 0.0) {
-        kg_chacha_block(key, kKgKsNoise, (uint64_t)s, 0u, w);
+        kg_chacha_block(nkey, kKgKsNoise, (uint64_t)s, 0u, w);
         e = (uint32_t)kg_noise32(w[0], w[1], w[2], w[3], a.ks_sigma);
       }
-      out[a.n] = (int32_t)(acc + e + (((uint32_t)a.tlwe_key[i] * (uint32_t)v) << (32 - (j + 1) * a.basebit)));
+      const int32_t b = (int32_t)(acc + e + (((uint32_t)a.tlwe_key[i] * (uint32_t)v) << (32 - (j + 1) * a.basebit)));
+      if (compressed) a.ksk[s] = b;
+      else out[a.n] = b;
     }
+  }
+}
+
+// Expansion of a compressed bk (rs_expand_keys_dev): a workgroup of T = N/16 threads per row, the grid striding over the n 2l rows.
+// Thread t regenerates mask words 16 t .. 16 t + 15 (one ChaCha block, kg_bk_mask_block, the mapping of gen_keygen_bk_kernel) and
+// stores them as four 16-byte writes; the body row is copied beside it with coalesced word loads and stores.
+template <int LOGN>
+__global__ __launch_bounds__((1 << LOGN) / 16) void expand_bk_kernel(ExpandArgs a) {
+  constexpr int N = 1 << LOGN, T = N / 16;
+  const int t = threadIdx.x;
+  uint32_t key[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  const long rows = (long)a.n * 2 * a.l;
+  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    int32_t* pa = a.bk + (size_t)row * 2 * N;
+    const int32_t* src = a.bk_body + (size_t)row * N;
+    int32_t body[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) body[r] = src[t + T * r];
+    uint32_t w[16];
+    kg_bk_mask_block(key, (uint64_t)row, t, w);
+    int4* dst = reinterpret_cast<int4*>(pa) + 4 * t;
+    dst[0] = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
+    dst[1] = make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]);
+    dst[2] = make_int4((int)w[8], (int)w[9], (int)w[10], (int)w[11]);
+    dst[3] = make_int4((int)w[12], (int)w[13], (int)w[14], (int)w[15]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) pa[N + t + T * r] = body[r];
+  }
+}
+
+// Expansion of a compressed ksk (rs_expand_keys_dev): one wave per sample, keygen_ksk_kernel's chunking and LDS transpose
+// (kg_ksk_mask_block, kg_ksk_chunk_word), so that the stores on the odd n + 1 stride are coalesced. v = 0 samples are all zero.
+__global__ __launch_bounds__(64 * kKgWaves) void expand_ksk_kernel(ExpandArgs a) {
+  __shared__ uint32_t s_w[kKgWaves][kKgChunk];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t* buf = s_w[wv];
+  uint32_t key[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  const int base = 1 << a.basebit, W = a.n + 1;
+  const long samples = (long)a.N * a.t * base;
+  for (long s = (long)blockIdx.x * kKgWaves + wv; s < samples; s += (long)gridDim.x * kKgWaves) {
+    int32_t* out = a.ksk + (size_t)s * W;
+    if ((s & (base - 1)) == 0) {
+      for (int k = lane; k < W; k += 64) out[k] = 0;
+      continue;
+    }
+    uint32_t w[16];
+    for (int k0 = 0; k0 < a.n; k0 += kKgChunk) {
+      kg_ksk_mask_block(key, (uint64_t)s, k0, lane, a.n, w);
+      gen_wave_sync();   // this wave's reads of the previous chunk are done
+#pragma unroll
+      for (int q = 0; q < 16; ++q) buf[16 * lane + q] = w[q];
+      gen_wave_sync();
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int idx = kg_ksk_chunk_word(q, lane), k = k0 + idx;
+        if (k < a.n) out[k] = (int32_t)buf[idx];
+      }
+    }
+    if (lane == 0) out[a.n] = a.ksk_body[s];
   }
 }
 
@@ -621,6 +701,29 @@ hipError_t launch_keygen_ksk(const KeygenArgs& a, int num_cus, hipStream_t st) {
   if (samples <= 0) return hipSuccess;
   const long blocks = std::min<long>((samples + kKgWaves - 1) / kKgWaves, 16L * num_cus);
   hipLaunchKernelGGL(keygen_ksk_kernel, dim3((unsigned)blocks), dim3(64 * kKgWaves), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_expand_bk(int logn, const ExpandArgs& a, int num_cus, hipStream_t st) {
+  const long rows = (long)a.n * 2 * a.l;
+  if (rows <= 0) return hipSuccess;
+  // 16 workgroups of one to eight waves per CU: enough stores in flight to hide the write latency
+  const dim3 grid((unsigned)std::min<long>(rows, 16L * num_cus)), block((1u << logn) / 16);
+  switch (logn) {
+    case 10: hipLaunchKernelGGL((expand_bk_kernel<10>), grid, block, 0, st, a); break;
+    case 11: hipLaunchKernelGGL((expand_bk_kernel<11>), grid, block, 0, st, a); break;
+    case 12: hipLaunchKernelGGL((expand_bk_kernel<12>), grid, block, 0, st, a); break;
+    case 13: hipLaunchKernelGGL((expand_bk_kernel<13>), grid, block, 0, st, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_expand_ksk(const ExpandArgs& a, int num_cus, hipStream_t st) {
+  const long samples = (long)a.N * a.t * (1L << a.basebit);
+  if (samples <= 0) return hipSuccess;
+  const long blocks = std::min<long>((samples + kKgWaves - 1) / kKgWaves, 16L * num_cus);
+  hipLaunchKernelGGL(expand_ksk_kernel, dim3((unsigned)blocks), dim3(64 * kKgWaves), 0, st, a);
   return hipGetLastError();
 }
 

@@ -105,15 +105,26 @@ hipError_t launch_gen_polymul(int logn, const int32_t* a_small, const int32_t* b
                               long count, unsigned long long* dev_flag, int num_cus, hipStream_t st);
 // evaluation-key generation (rs_keygen_dev; streams of rs_keygen.h): bk rows [n][2l][2][N] and ksk samples [N][t][2^basebit][n+1]
 struct KeygenArgs {
-  int32_t* bk; int32_t* ksk;
+  int32_t* bk; int32_t* ksk;                          // compressed: the bodies bk_body [n][2l][N], ksk_body [N][t][2^basebit]
   const int32_t* lwe_key; const int32_t* tlwe_key;   // device copies, values 0 / 1
-  uint32_t seed[8];
+  uint32_t seed[8];                                   // masks (domains 3, 5); noise too unless compressed
+  uint32_t noise_seed[8];                             // compressed: noise (domains 4, 6)
+  int compressed;                                     // 1: bodies only, the c = 0 gadget term moved into the body (rs_keygen_compressed_dev)
   int n, N, l, bgbit, t, basebit;
   double bk_sigma, ks_sigma;
   unsigned long long* dev_flag;                       // largest rounding distance of the a*S products
 };
 hipError_t launch_keygen_bk(int logn, const KeygenArgs& a, const double* tw, int num_cus, hipStream_t st);
 hipError_t launch_keygen_ksk(const KeygenArgs& a, int num_cus, hipStream_t st);
+// expansion of a compressed key (rs_expand_keys_dev): the masks regenerated from the mask seed, the bodies copied beside them
+struct ExpandArgs {
+  int32_t* bk; int32_t* ksk;                          // full layouts of rs_load_keys (bk 16-byte aligned)
+  const int32_t* bk_body; const int32_t* ksk_body;    // [n][2l][N], [N][t][2^basebit]
+  uint32_t seed[8];                                   // the mask seed
+  int n, N, l, t, basebit;
+};
+hipError_t launch_expand_bk(int logn, const ExpandArgs& a, int num_cus, hipStream_t st);
+hipError_t launch_expand_ksk(const ExpandArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,

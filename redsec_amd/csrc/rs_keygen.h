@@ -69,4 +69,31 @@ RS_HD int32_t kg_noise32(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, dou
   return (int32_t)(uint32_t)(uint64_t)(int64_t)((e - trunc(e)) * 4294967296.0);
 }
 
+// ---- the mask streams of a key, shared by key generation and expansion (rs_keygen_dev, rs_keygen_compressed_dev,
+// rs_expand_keys_dev) so that the words of the two paths cannot drift apart; the lane emulator runs them for the CPU tests ----
+
+// bk row `row`, thread t of the row's N / 16: mask words 16 t .. 16 t + 15 = block t of stream (3, row)
+RS_HD void kg_bk_mask_block(const uint32_t (&key)[8], uint64_t row, int t, uint32_t (&w)[16]) {
+  kg_chacha_block(key, kKgBkMask, row, (uint32_t)t, w);
+}
+
+// ksk sample s, lane L of its wave, chunk k0 (a multiple of 1024) of the n mask words: block k0 / 16 + L of stream (5, s),
+// i.e. words k0 + 16 L .. k0 + 16 L + 15; false (w untouched) when that block lies past the mask
+RS_HD bool kg_ksk_mask_block(const uint32_t (&key)[8], uint64_t s, int k0, int lane, int n, uint32_t (&w)[16]) {
+  const int blk = k0 / 16 + lane;
+  if (16 * blk >= n) return false;
+  kg_chacha_block(key, kKgKsMask, s, (uint32_t)blk, w);
+  return true;
+}
+// the LDS transpose of a chunk: lane L writes its block to buf[16 L + q]; the coalesced read of round q at lane L takes buf[64 q + L],
+// mask word k0 + 64 q + L
+constexpr int kKgChunk = 64 * 16;
+RS_HD int kg_ksk_chunk_word(int q, int lane) { return 64 * q + lane; }
+
+// seed bytes -> the 8 little-endian key words
+RS_HD void kg_seed_words(const uint8_t* seed, uint32_t (&key)[8]) {
+  for (int k = 0; k < 8; ++k)
+    key[k] = (uint32_t)seed[4 * k] | ((uint32_t)seed[4 * k + 1] << 8) | ((uint32_t)seed[4 * k + 2] << 16) | ((uint32_t)seed[4 * k + 3] << 24);
+}
+
 }  // namespace rs

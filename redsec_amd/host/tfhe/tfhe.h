@@ -83,6 +83,10 @@ struct LweBootstrappingKey {
   const TGswParams* bk_params;
   int32_t* bk_words;   // [n][(k+1)l][k+1][N]
   int32_t* ksk_words;  // [k*N][t][base][n+1]
+  // compressed evaluation key (include/redsec_hip.h, rs_load_compressed_keys): 0 = plain full words; 1 = full words whose masks
+  // are the streams of mask_seed (exported as RSZ1); 2 = bodies only, bk_words = bk_body [n][2l][N], ksk_words = ksk_body [N][t][base]
+  int32_t compressed;
+  uint8_t mask_seed[32];
 };
 
 struct rs_ctx;

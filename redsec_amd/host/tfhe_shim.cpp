@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "redsec_hip.h"
+#include "rs_keygen.h"   // the mask streams of a compressed key (csrc/rs_keygen.h): one statement of ChaCha20 for device and host
 
 // seconds spent creating device contexts and uploading / transforming keys since the last call (REDSEC_TRACE reports them apart
 // from a layer's own staging: they happen once per process, inside whichever call touches the GPU first)
@@ -47,6 +48,7 @@ inline uint32_t uniform32() { return (uint32_t)(rng()() >> 32); }
 
 constexpr uint32_t kMagicSecret = 0x31535352u;  // "RSS1"
 constexpr uint32_t kMagicCloud = 0x314b5352u;   // "RSK1"
+constexpr uint32_t kMagicCompressed = 0x315a5352u;   // "RSZ1": RSK1's header, the 32-byte mask seed, bk_body, ksk_body
 
 struct ParamHeader {
   uint32_t magic;
@@ -111,6 +113,22 @@ LweBootstrappingKey* new_bk(const TFheGateBootstrappingParameterSet* p) {
   bk->bk_params = p->tgsw_params;
   bk->bk_words = alloc_words(bk_words(p), "bootstrapping key");
   bk->ksk_words = alloc_words(ksk_words(p), "keyswitch key");
+  bk->compressed = 0;
+  memset(bk->mask_seed, 0, sizeof bk->mask_seed);
+  return bk;
+}
+
+// bodies of a compressed key (include/redsec_hip.h): bk_body [n][2l][N] (half the TGSW words), ksk_body [N][t][base]
+size_t bk_body_words(const TFheGateBootstrappingParameterSet* p) { return bk_words(p) / 2; }
+size_t ksk_body_words(const TFheGateBootstrappingParameterSet* p) { return ksk_words(p) / (size_t)(p->in_out_params->n + 1); }
+LweBootstrappingKey* new_body_bk(const TFheGateBootstrappingParameterSet* p) {
+  LweBootstrappingKey* bk = new LweBootstrappingKey;
+  bk->in_out_params = p->in_out_params;
+  bk->bk_params = p->tgsw_params;
+  bk->bk_words = alloc_words(bk_body_words(p), "bootstrapping key bodies");
+  bk->ksk_words = alloc_words(ksk_body_words(p), "keyswitch key bodies");
+  bk->compressed = 2;
+  memset(bk->mask_seed, 0, sizeof bk->mask_seed);
   return bk;
 }
 
@@ -151,7 +169,9 @@ rs_ctx* ctx_of_fft(const LweBootstrappingKeyFFT* cf) {
   const auto t_setup = std::chrono::steady_clock::now();
   for (size_t i = 0; i < devices.size(); ++i) {
     if (rs_create(&fleet[i], &rp, devices[i]) != 0) die("rs_create");
-    if (rs_load_keys(fleet[i], f->src->bk_words, f->src->ksk_words) != 0) die("rs_load_keys");
+    if (f->src->compressed == 2) {   // bodies only: every device expands the masks itself
+      if (rs_load_compressed_keys(fleet[i], f->src->mask_seed, f->src->bk_words, f->src->ksk_words) != 0) die("rs_load_compressed_keys");
+    } else if (rs_load_keys(fleet[i], f->src->bk_words, f->src->ksk_words) != 0) die("rs_load_keys");
   }
   g_setup_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count();
   f->fleet = fleet;
@@ -181,6 +201,79 @@ void gate(rs_gate_op op, LweSample* result, const LweSample* ca, const LweSample
   redsec_unpack(result, z.data(), n);
 }
 
+bool key_format_is_rs() { const char* f = getenv("REDSEC_KEY_FORMAT"); return f && strcmp(f, "rs") == 0; }
+// REDSEC_KEY_FORMAT=compressed: new keys draw their masks from the ChaCha20 streams of a fresh random mask seed; the cloud key is
+// written as RSZ1 (seed + bodies), the secret key as RSS1 (full words, as under REDSEC_KEY_FORMAT=rs)
+bool key_format_is_compressed() { const char* f = getenv("REDSEC_KEY_FORMAT"); return f && strcmp(f, "compressed") == 0; }
+
+// words [0, count) of stream (domain, row) of the key words `key` (csrc/rs_keygen.h)
+void stream_words(const uint32_t (&key)[8], uint32_t domain, uint64_t row, uint32_t* out, size_t count) {
+  for (size_t b = 0; 16 * b < count; ++b) {
+    uint32_t w[16];
+    rs::kg_chacha_block(key, domain, row, (uint32_t)b, w);
+    for (size_t q = 0; q < 16 && 16 * b + q < count; ++q) out[16 * b + q] = w[q];
+  }
+}
+
+// A compressed key in full words (include/redsec_hip.h, rs_keygen_compressed_dev): bk row p = c l + j of s_i has the domain-3
+// mask of the seed and b = a*S + e + s_i g_j X^0 (c = 1) or a*S + e - s_i g_j S (c = 0); ksk sample s the domain-5 mask and
+// b = a.s + e + message. The noise comes from the shim's generator (only the masks have to be reproducible).
+void compressed_keygen(const TFheGateBootstrappingParameterSet* p, LweBootstrappingKey* bk, const LweKey* lk, const TGswKey* gk) {
+  const TGswParams* gp = p->tgsw_params;
+  const TLweParams* tp = gp->tlwe_params;
+  const int32_t n = p->in_out_params->n, N = tp->N, l = gp->l, kpl = gp->kpl;
+  const int32_t t = p->ks_t, basebit = p->ks_basebit, base = 1 << basebit, W = n + 1;
+  std::random_device rd;
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t v = rd();
+    memcpy(bk->mask_seed + 4 * k, &v, 4);
+  }
+  uint32_t key[8];
+  rs::kg_seed_words(bk->mask_seed, key);
+  for (int32_t i = 0; i < n; ++i)
+    for (int32_t row = 0; row < kpl; ++row) {
+      const uint64_t r = (uint64_t)i * kpl + row;
+      int32_t* apoly = bk->bk_words + r * 2 * (size_t)N;
+      int32_t* bpoly = apoly + N;
+      for (int32_t j = 0; j < N; ++j) bpoly[j] = gaussian32(0, tp->alpha_min);
+      stream_words(key, rs::kKgBkMask, r, reinterpret_cast<uint32_t*>(apoly), (size_t)N);
+      addmul_binary(bpoly, gk->key, apoly, N);
+      const int32_t comp = row / l, dig = row % l;
+      const uint32_t h = (uint32_t)lk->key[i] << (32 - (dig + 1) * gp->Bgbit);
+      if (comp == 1) bpoly[0] = (int32_t)((uint32_t)bpoly[0] + h);
+      else
+        for (int32_t j = 0; j < N; ++j) bpoly[j] = (int32_t)((uint32_t)bpoly[j] - h * (uint32_t)gk->key[j]);
+    }
+  for (int32_t i = 0; i < N; ++i)
+    for (int32_t j = 0; j < t; ++j)
+      for (int32_t v = 0; v < base; ++v) {
+        const uint64_t s = ((uint64_t)i * t + j) * base + v;
+        int32_t* rowp = bk->ksk_words + s * (size_t)W;
+        if (v == 0) { memset(rowp, 0, sizeof(int32_t) * (size_t)W); continue; }
+        stream_words(key, rs::kKgKsMask, s, reinterpret_cast<uint32_t*>(rowp), (size_t)n);
+        uint32_t b = (uint32_t)gaussian32(0, p->in_out_params->alpha_min);
+        for (int32_t k = 0; k < n; ++k) b += (uint32_t)rowp[k] * (uint32_t)lk->key[k];
+        rowp[n] = (int32_t)(b + (((uint32_t)gk->key[i] * (uint32_t)v) << (32 - (j + 1) * basebit)));
+      }
+  bk->compressed = 1;
+}
+
+// RSZ1: header, mask seed, bk_body, ksk_body (bodies taken out of the full words of a key generated here, or written as read)
+void write_compressed(FILE* f, const TFheGateBootstrappingParameterSet* p, const LweBootstrappingKey* bk) {
+  const ParamHeader h = header_from_params(kMagicCompressed, p);
+  write_exact(f, &h, sizeof h, "compressed cloud key header");
+  write_exact(f, bk->mask_seed, sizeof bk->mask_seed, "mask seed");
+  if (bk->compressed == 2) {
+    write_exact(f, bk->bk_words, sizeof(int32_t) * bk_body_words(p), "bootstrapping key bodies");
+    write_exact(f, bk->ksk_words, sizeof(int32_t) * ksk_body_words(p), "keyswitch key bodies");
+    return;
+  }
+  const size_t N = (size_t)p->tgsw_params->tlwe_params->N, W = (size_t)p->in_out_params->n + 1;
+  for (size_t r = 0; r < bk_body_words(p) / N; ++r) write_exact(f, bk->bk_words + (2 * r + 1) * N, sizeof(int32_t) * N, "bootstrapping key body");
+  std::vector<int32_t> kb(ksk_body_words(p));
+  for (size_t s = 0; s < kb.size(); ++s) kb[s] = bk->ksk_words[s * W + W - 1];
+  write_exact(f, kb.data(), sizeof(int32_t) * kb.size(), "keyswitch key bodies");
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -301,6 +394,10 @@ TFheGateBootstrappingSecretKeySet* new_random_gate_bootstrapping_secret_keyset(c
   for (int32_t i = 0; i < n; ++i) lk->key[i] = (int32_t)(uniform32() & 1u);
   for (int32_t i = 0; i < k * N; ++i) gk->key[i] = (int32_t)(uniform32() & 1u);
   LweBootstrappingKey* bk = new_bk(p);
+  if (key_format_is_compressed()) {
+    compressed_keygen(p, bk, lk, gk);
+    return new TFheGateBootstrappingSecretKeySet(p, bk, new_bkfft(p, bk), lk, gk);
+  }
   // TGSW(s_i): row c*l + j = TRLWE encryption of zero + s_i * 2^(32-(j+1)Bgbit) on component c
   for (int32_t i = 0; i < n; ++i)
     for (int32_t row = 0; row < kpl; ++row) {
@@ -371,13 +468,15 @@ void delete_gate_bootstrapping_parameters(TFheGateBootstrappingParameterSet*) {}
 //     reported on stderr unless REDSEC_TFHE_QUIET is set), since those constants are the least certain part of
 //     the restatement; REDSEC_TFHE_STRICT=1 turns a mismatch into an error.
 // (2) this backend's first format: 16-byte-aligned header with magic "RSK1"/"RSS1" + raw arrays.
+// (3) the compressed cloud key "RSZ1" (include/redsec_hip.h): RSK1's header, the 32-byte mask seed,
+//     bk_body [n][2l][N], ksk_body [N][t][base]. Read as seed + bodies (ctx_of_fft expands them on every device); written for
+//     key sets read from RSZ1 or generated under REDSEC_KEY_FORMAT=compressed, whatever REDSEC_KEY_FORMAT says.
 namespace {
 
 enum TfheUid : int32_t {   // [TFHE-recalled]
   kUidLweSample = 42, kUidLweKey = 43, kUidTlweKey = 45, kUidTgswSample = 47, kUidLweKeySwitchKey = 200, kUidLweBootstrappingKey = 201,
 };
 
-bool key_format_is_rs() { const char* f = getenv("REDSEC_KEY_FORMAT"); return f && strcmp(f, "rs") == 0; }
 
 void put_section(FILE* f, const char* title, std::initializer_list<std::pair<const char*, std::string>> props) {
   fprintf(f, "-----BEGIN %s-----\n", title);
@@ -497,6 +596,7 @@ bool file_is_tfhe(FILE* f) {
 }  // namespace
 
 void export_tfheGateBootstrappingCloudKeySet_toFile(FILE* f, const TFheGateBootstrappingCloudKeySet* key) {
+  if (key->bk->compressed) { write_compressed(f, key->params, key->bk); return; }
   if (!key_format_is_rs()) { tfhe_write_params(f, key->params); tfhe_write_bk(f, key->params, key->bk); return; }
   const ParamHeader h = header_from_params(kMagicCloud, key->params);
   write_exact(f, &h, sizeof h, "cloud key header");
@@ -505,7 +605,7 @@ void export_tfheGateBootstrappingCloudKeySet_toFile(FILE* f, const TFheGateBoots
 }
 void export_tfheGateBootstrappingSecretKeySet_toFile(FILE* f, const TFheGateBootstrappingSecretKeySet* key) {
   const ParamHeader h = header_from_params(kMagicSecret, key->params);
-  if (!key_format_is_rs()) {   // write_tfheGateBootstrappingSecretKeySet: cloud part, lwe key, tgsw (= tlwe) key
+  if (!key_format_is_rs() && !key->cloud.bk->compressed) {   // write_tfheGateBootstrappingSecretKeySet: cloud part, lwe key, tgsw (= tlwe) key
     tfhe_write_params(f, key->params);
     tfhe_write_bk(f, key->params, key->cloud.bk);
     put_uid(f, kUidLweKey);
@@ -528,6 +628,15 @@ TFheGateBootstrappingCloudKeySet* new_tfheGateBootstrappingCloudKeySet_fromFile(
   }
   ParamHeader h;
   read_exact(f, &h, sizeof h, "cloud key header");
+  if (h.magic == kMagicCompressed) {   // kept as seed + bodies: the devices expand them (ctx_of_fft), the host never does
+    check_header(h, "compressed cloud key");
+    TFheGateBootstrappingParameterSet* p = params_from_header(h);
+    LweBootstrappingKey* bk = new_body_bk(p);
+    read_exact(f, bk->mask_seed, sizeof bk->mask_seed, "mask seed");
+    read_exact(f, bk->bk_words, sizeof(int32_t) * bk_body_words(p), "bootstrapping key bodies");
+    read_exact(f, bk->ksk_words, sizeof(int32_t) * ksk_body_words(p), "keyswitch key bodies");
+    return new TFheGateBootstrappingCloudKeySet(p, bk, new_bkfft(p, bk));
+  }
   if (h.magic != kMagicCloud) { fprintf(stderr, "redsec tfhe shim: not a cloud key file\n"); abort(); }
   check_header(h, "cloud key");
   TFheGateBootstrappingParameterSet* p = params_from_header(h);

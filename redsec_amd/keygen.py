@@ -21,6 +21,16 @@ Every word of a generated key is a function of a 32-byte seed, the secret keys a
   of component c gains s_i 2^(32 - (j+1) Bgbit) (for c = 0, a[0] changes after b was formed).
   ksk samples with v = 0 are all zero; v >= 1: a = the domain-5 words, b = sum_k a_k s_k + e + ((S_i v) << (32 - (j+1) basebit)).
 
+Compressed key (rs_keygen_compressed_dev, rs_expand_keys_dev; include/redsec_hip.h): a public 32-byte MASK SEED and the bodies,
+another encryption of the same key with the gadget term of c = 0 rows moved out of the mask:
+
+  bk row p = c l + j of s_i: a = domain 3 of the mask seed (stored unchanged); b = a*S + e + s_i g_j X^0 for c = 1 and
+  b = a*S + e - s_i g_j S for c = 0, g_j = 2^(32 - (j+1) Bgbit), e = domain 4 of the noise seed. Same phase as the row above;
+  the difference is -s_i g_j (1, S) for c = 0, an exact encryption of zero.
+  ksk sample s: a = domain 5 of the mask seed; b as above with e = domain 6 of the noise seed; v = 0 samples are all zero.
+  The NOISE SEED (domains 1, 2, 4, 6: the secret keys and the noise) stays private and must differ from the mask seed.
+  Layouts: bk_body int32 [n][2l][N], ksk_body int32 [N][t][2^basebit].
+
 The noise words are restated with numpy's log / cos, which may differ from the device's in the last bit of z: a restated
 noise word can then differ by one from the device's in the rare case where sigma z 2^32 lies that close to an integer. Mask
 words, secret keys and noiseless keys are restated exactly.
@@ -128,39 +138,47 @@ def _times_binary(A, tlwe_key):
     return out
 
 
-def restate_bk(name, seed, lwe_key, tlwe_key, bk_stdev, rows=None, n=None, chunk=256):
-    """bk rows i 2l + p (all n 2l rows if rows is None) -> int32 [R][2][N]."""
+def _bk_rows(name, mask_seed, noise_seed, lwe_key, tlwe_key, bk_stdev, rows, n, chunk, compressed):
     s = _shape(name, n if n is not None else len(lwe_key))
     l, Bgbit, N = s["l"], s["Bgbit"], s["N"]
     rows = np.arange(s["n"] * 2 * l) if rows is None else np.asarray(rows, np.int64).ravel()
     lwe = np.asarray(lwe_key).astype(np.uint32)
-    out = np.empty((len(rows), 2, N), np.int32)
+    tlwe = np.asarray(tlwe_key).astype(np.uint32)
+    out = np.empty((len(rows), N) if compressed else (len(rows), 2, N), np.int32)
     with np.errstate(over="ignore"):
         for lo in range(0, len(rows), chunk):
             r = rows[lo:lo + chunk]
-            A = chacha20_words(seed, DOMAIN_BK_MASK, r, N)
+            A = chacha20_words(mask_seed, DOMAIN_BK_MASK, r, N)
             B = _times_binary(A, tlwe_key)
             if bk_stdev:
-                B += noise32(chacha20_words(seed, DOMAIN_BK_NOISE, r, 4 * N), bk_stdev).view(np.uint32)
+                B += noise32(chacha20_words(noise_seed, DOMAIN_BK_NOISE, r, 4 * N), bk_stdev).view(np.uint32)
             p = r % (2 * l)
             c, j = p // l, p % l
             gadget = lwe[r // (2 * l)] * (np.uint32(1) << (32 - (j + 1) * Bgbit).astype(np.uint32))
-            A[c == 0, 0] += gadget[c == 0]
             B[c == 1, 0] += gadget[c == 1]
+            if compressed:
+                B[c == 0] -= gadget[c == 0, None] * tlwe[None, :]
+                out[lo:lo + chunk] = B.view(np.int32)
+                continue
+            A[c == 0, 0] += gadget[c == 0]
             out[lo:lo + chunk, 0] = A.view(np.int32)
             out[lo:lo + chunk, 1] = B.view(np.int32)
     return out
 
 
-def restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev, rows=None, n=None, chunk=4096):
-    """ksk samples s = (i t + j) 2^basebit + v (all of them if rows is None) -> int32 [R][n+1]."""
+def restate_bk(name, seed, lwe_key, tlwe_key, bk_stdev, rows=None, n=None, chunk=256):
+    """bk rows i 2l + p (all n 2l rows if rows is None) -> int32 [R][2][N]."""
+    return _bk_rows(name, seed, seed, lwe_key, tlwe_key, bk_stdev, rows, n, chunk, False)
+
+
+def _ksk_rows(name, mask_seed, noise_seed, lwe_key, tlwe_key, ks_stdev, rows, n, chunk, compressed):
     s = _shape(name, n if n is not None else len(lwe_key))
     n, N, t, basebit = s["n"], s["N"], s["t"], s["basebit"]
     base = 1 << basebit
     rows = np.arange(N * t * base) if rows is None else np.asarray(rows, np.int64).ravel()
     lwe = np.asarray(lwe_key).astype(np.uint64)
     tlwe = np.asarray(tlwe_key).astype(np.uint64)
-    out = np.zeros((len(rows), n + 1), np.int32)
+    out = np.zeros(len(rows) if compressed else (len(rows), n + 1), np.int32)
     for lo in range(0, len(rows), chunk):
         r = rows[lo:lo + chunk]
         v = r % base
@@ -168,16 +186,24 @@ def restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev, rows=None, n=None, chun
         if len(live) == 0:
             continue
         rl = r[live]
-        A = chacha20_words(seed, DOMAIN_KS_MASK, rl, n)
+        A = chacha20_words(mask_seed, DOMAIN_KS_MASK, rl, n)
         dot = (A.astype(np.uint64) * lwe).sum(axis=-1)
-        e = noise32(chacha20_words(seed, DOMAIN_KS_NOISE, rl, 4), ks_stdev)[:, 0] if ks_stdev else np.zeros(len(rl), np.int32)
+        e = noise32(chacha20_words(noise_seed, DOMAIN_KS_NOISE, rl, 4), ks_stdev)[:, 0] if ks_stdev else np.zeros(len(rl), np.int32)
         ij = rl >> basebit
         i, j = ij // t, ij % t
         mess = (tlwe[i] * (rl % base).astype(np.uint64)) << (32 - (j + 1) * basebit).astype(np.uint64)
         b = (dot + e.view(np.uint32).astype(np.uint64) + mess) & np.uint64(0xFFFFFFFF)
+        if compressed:
+            out[lo + live] = b.astype(np.uint32).view(np.int32)
+            continue
         out[lo + live, :n] = A.view(np.int32)
         out[lo + live, n] = b.astype(np.uint32).view(np.int32)
     return out
+
+
+def restate_ksk(name, seed, lwe_key, tlwe_key, ks_stdev, rows=None, n=None, chunk=4096):
+    """ksk samples s = (i t + j) 2^basebit + v (all of them if rows is None) -> int32 [R][n+1]."""
+    return _ksk_rows(name, seed, seed, lwe_key, tlwe_key, ks_stdev, rows, n, chunk, False)
 
 
 def restate(name, seed, lwe_key, tlwe_key, bk_stdev, ks_stdev, rows=None):
@@ -210,3 +236,107 @@ def generate(backend, seed=None, bk_stdev=None, ks_stdev=None, load=True):
     if load:
         backend.load_keys_dev(bk, ksk)
     return client.SecretKeySet.from_secret(name, lwe, tlwe), bk, ksk
+
+
+# ---- compressed keys ----
+
+class CompressedKey:
+    """A compressed evaluation key: the set name, the LWE dimension n, the public 32-byte mask seed and the bodies bk_body
+    [n][2l][N], ksk_body [N][t][2^basebit] (int32 numpy arrays or CUDA tensors). nbytes: what travels (seed + bodies)."""
+
+    def __init__(self, name, n, mask_seed, bk_body, ksk_body):
+        self.name, self.n, self.mask_seed = name, int(n), bytes(mask_seed)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        self.bk_body, self.ksk_body = bk_body, ksk_body
+
+    @property
+    def nbytes(self):
+        s = _shape(self.name, self.n)
+        return 32 + 4 * (self.n * 2 * s["l"] * s["N"] + s["N"] * s["t"] * (1 << s["basebit"]))
+
+    def numpy(self):
+        """The same key with host bodies."""
+        host = lambda x: x if isinstance(x, np.ndarray) else x.cpu().numpy()
+        return CompressedKey(self.name, self.n, self.mask_seed, host(self.bk_body), host(self.ksk_body))
+
+
+def full_nbytes(name, n=None):
+    """Bytes of the full evaluation key (bk + ksk) of a set."""
+    s = _shape(name, n)
+    return 4 * (s["n"] * 2 * s["l"] * 2 * s["N"] + s["N"] * s["t"] * (1 << s["basebit"]) * (s["n"] + 1))
+
+
+def restate_compressed(name, mask_seed, noise_seed, lwe_key, tlwe_key, bk_stdev, ks_stdev, rows=None):
+    """The bodies rs_keygen_compressed_dev writes, regenerated on the host. rows=None: the whole (bk_body [n][2l][N],
+    ksk_body [N][t][2^basebit]); rows=(bk_rows, ksk_rows): only those bk rows ([R][N]) and ksk samples ([R']); either may be None.
+    The LWE dimension is len(lwe_key). The numpy level does not refuse equal seeds (the tests relate it to restate that way)."""
+    s = _shape(name, len(lwe_key))
+    bk_rows, ksk_rows = (None, None) if rows is None else rows
+    bk = None if rows is not None and bk_rows is None else _bk_rows(name, mask_seed, noise_seed, lwe_key, tlwe_key, bk_stdev, bk_rows, None, 256, True)
+    ksk = None if rows is not None and ksk_rows is None else _ksk_rows(name, mask_seed, noise_seed, lwe_key, tlwe_key, ks_stdev, ksk_rows, None, 4096, True)
+    if rows is None:
+        bk = bk.reshape(s["n"], 2 * s["l"], s["N"])
+        ksk = ksk.reshape(s["N"], s["t"], 1 << s["basebit"])
+    return bk, ksk
+
+
+def expand_bk(name, mask_seed, body_rows, rows, chunk=256):
+    """Expanded bk rows (rs_expand_keys_dev): the domain-3 masks of `rows` beside their bodies body_rows [R][N] -> int32 [R][2][N]."""
+    rows = np.asarray(rows, np.int64).ravel()
+    body_rows = np.asarray(body_rows, np.int32).reshape(len(rows), -1)
+    out = np.empty((len(rows), 2, body_rows.shape[1]), np.int32)
+    for lo in range(0, len(rows), chunk):
+        out[lo:lo + chunk, 0] = chacha20_words(mask_seed, DOMAIN_BK_MASK, rows[lo:lo + chunk], body_rows.shape[1]).view(np.int32)
+    out[:, 1] = body_rows
+    return out
+
+
+def expand_ksk(name, mask_seed, body_words, rows, n, chunk=4096):
+    """Expanded ksk samples (rs_expand_keys_dev): the domain-5 masks of samples `rows` and their body words -> int32 [R][n+1];
+    samples with v = 0 are all zero."""
+    base = 1 << _shape(name)["basebit"]
+    rows = np.asarray(rows, np.int64).ravel()
+    body_words = np.asarray(body_words, np.int32).ravel()
+    out = np.zeros((len(rows), int(n) + 1), np.int32)
+    for lo in range(0, len(rows), chunk):
+        r = rows[lo:lo + chunk]
+        live = np.flatnonzero(r % base != 0)
+        if len(live):
+            out[lo + live, :n] = chacha20_words(mask_seed, DOMAIN_KS_MASK, r[live], n).view(np.int32)
+            out[lo + live, n] = body_words[lo + live]
+    return out
+
+
+def expand(name, mask_seed, bk_body, ksk_body, n=None, rows=None):
+    """The full key of a compressed one, expanded on the host. rows=None: bk_body / ksk_body are whole and the result is the whole
+    (bk [n][2l][2][N], ksk [N][t][2^basebit][n+1]); rows=(bk_rows, ksk_rows): bk_body / ksk_body hold the bodies of exactly those
+    rows and the result those rows ([R][2][N], [R'][n+1]); either entry may be None (skipped). n defaults to the set's."""
+    s = _shape(name, n if n is not None else (np.shape(bk_body)[0] if rows is None else None))
+    if rows is None:
+        N, l, t, base = s["N"], s["l"], s["t"], 1 << s["basebit"]
+        bk = expand_bk(name, mask_seed, np.reshape(bk_body, (-1, N)), np.arange(s["n"] * 2 * l)).reshape(s["n"], 2 * l, 2, N)
+        ksk = expand_ksk(name, mask_seed, ksk_body, np.arange(N * t * base), s["n"]).reshape(N, t, base, s["n"] + 1)
+        return bk, ksk
+    bk_rows, ksk_rows = rows
+    bk = None if bk_rows is None else expand_bk(name, mask_seed, bk_body, bk_rows)
+    ksk = None if ksk_rows is None else expand_ksk(name, mask_seed, ksk_body, ksk_rows, s["n"])
+    return bk, ksk
+
+
+def generate_compressed(backend, noise_seed=None, mask_seed=None, bk_stdev=None, ks_stdev=None, load=True):
+    """Secret keys of domains 1 / 2 of the private noise_seed (default os.urandom(32)) and the bodies of a compressed evaluation key
+    generated on the backend's device under the public mask_seed (default os.urandom(32); must differ from noise_seed)
+    -> (client.SecretKeySet without an evaluation key, CompressedKey with CUDA-tensor bodies). load=True also makes it the
+    backend's key (rs_load_compressed_keys_dev). Client-side operation: see INTEGRATION.md section 11."""
+    p = backend.p
+    name = set_name(p)
+    s = _shape(name, p.n)
+    noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+    mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+    bk_stdev = s["bk_stdev"] if bk_stdev is None else bk_stdev
+    ks_stdev = s["ks_stdev"] if ks_stdev is None else ks_stdev
+    lwe, tlwe = secret_keys(name, noise_seed, p.n)
+    bk_body, ksk_body = backend.keygen_compressed(lwe, tlwe, mask_seed, noise_seed, bk_stdev, ks_stdev)
+    if load:
+        backend.load_compressed_keys(mask_seed, bk_body, ksk_body)
+    return client.SecretKeySet.from_secret(name, lwe, tlwe), CompressedKey(name, p.n, mask_seed, bk_body, ksk_body)
