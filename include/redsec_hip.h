@@ -144,6 +144,29 @@ int rs_expand_keys_dev(rs_ctx* ctx, int32_t* bk, int32_t* ksk, const uint8_t* ma
 int rs_load_compressed_keys(rs_ctx* ctx, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body);
 int rs_load_compressed_keys_dev(rs_ctx* ctx, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body);
 
+/* Seeded LWE ciphertexts: a batch travels as a public 32-byte MASK SEED, a uint64 `first` and one body
+ * word per sample, 4 bytes instead of 4 (n + 1). Streams as for rs_keygen_dev, two more domains:
+ *   domain 7 ciphertext mask   row first + i   the n mask words of ciphertext i of the call (mask seed)
+ *   domain 8 ciphertext noise  same row        1 Gaussian, words 0-3 (noise seed)
+ * Ciphertext i: a_k = word k of stream (7, first + i) of the mask seed; e = dtot32(stdev z) of Gaussian 0 of stream (8, first + i)
+ * of the noise seed, as in rs_keygen_dev; body = sum_k a_k s_k + e + mu_i (mod 2^32). The expanded sample is the usual
+ * int32[B][n+1], the body at word n. Domains 7 and 8 are disjoint from 1-6: one seed may serve a compressed key and ciphertexts.
+ * Rules:
+ *   - the NOISE SEED is private; equal mask and noise seeds would publish the noise and are refused;
+ *   - first + B must not pass 2^64 (the last row is at most 2^64 - 1);
+ *   - a (mask seed, row) pair must never encrypt two messages: equal masks publish the difference of the messages up to noise.
+ *     redsec_amd's default is a fresh random mask seed per call.
+ * Both return RS_ERR_INVALID for null pointers, key words outside {0, 1}, a negative or non-finite stdev, equal seeds and first + B
+ * passing 2^64; B = 0 is a no-op that returns RS_OK. There is no CPU fallback: without a device they fail with RS_ERR_NO_DEVICE.
+ *
+ * CLIENT side. Synchronous. lwe_key HOST int32[n], 0/1. mu DEVICE int32[B] (torus words). body DEVICE int32[B].
+ * ct DEVICE int32[B][n+1], or NULL for bodies only. The secret's private device copy is zeroed and freed on every path. */
+int rs_encrypt_seeded_dev(rs_ctx* ctx, int32_t* body, int32_t* ct, const int32_t* mu, size_t B, const int32_t* lwe_key,
+                          const uint8_t* mask_seed, const uint8_t* noise_seed, uint64_t first, double stdev);
+/* SERVER side. Ordered on `stream`, like the other *_dev calls; needs no loaded key. ct, body DEVICE. */
+int rs_expand_ciphertexts_dev(rs_ctx* ctx, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body,
+                              size_t B, void* stream);
+
 /* Arithmetic of the external product (both keys are resident after rs_load_keys; switching is free):
  *   RS_MODE_FFT        folded 512-point complex FP64 FFT -- the arithmetic class of TFHE's own
  *                      tGswFFTExternMulToTLwe -- rounded to the nearest integer. The true product is an

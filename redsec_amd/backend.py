@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
+    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -94,6 +95,8 @@ def load_library(path=None):
     L.rs_expand_keys_dev.argtypes = [vp, vp, vp, C.c_char_p, vp, vp]
     L.rs_load_compressed_keys.argtypes = [vp, C.c_char_p, _i32p, _i32p]
     L.rs_load_compressed_keys_dev.argtypes = [vp, C.c_char_p, vp, vp]
+    L.rs_encrypt_seeded_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, _i32p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_double]
+    L.rs_expand_ciphertexts_dev.argtypes = [vp, vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp]
     L.rs_reserve.argtypes = [vp, C.c_size_t]
     L.rs_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_bootstrap.argtypes = [vp, _i32p, _i32p, C.c_int32, C.c_size_t]
@@ -307,6 +310,31 @@ class Backend:
         else:
             assert bk_body.numel() == nb and ksk_body.numel() == nk, "bodies have the wrong size"
             _check(self.L, self.L.rs_load_compressed_keys_dev(self.h, mask_seed, self._ck_dev(bk_body), self._ck_dev(ksk_body)))
+
+    # ---- seeded ciphertexts ----
+    def encrypt_seeded(self, lwe_key, mu, mask_seed, noise_seed, first=0, stdev=2.0 ** -15, full=False):
+        """Seeded ciphertexts of the torus words mu (int32 CUDA tensor [B]) under lwe_key (host, 0/1) encrypted on the device
+        (rs_encrypt_seeded_dev, synchronous) -> the bodies int32 [B], or (bodies, ct [B][n+1]) with full=True. mask_seed is public
+        and must not encrypt two messages at one row; noise_seed is private and must differ from it."""
+        lwe, plwe = _np_i32(lwe_key)
+        assert lwe.size == self.p.n, "lwe_key must have n = %d words" % self.p.n
+        B = mu.numel()
+        body = self.empty(B)
+        ct = self.empty(B, self.W) if full else None
+        _check(self.L, self.L.rs_encrypt_seeded_dev(self.h, self._ck_dev(body), self._ck_dev(ct) if full else None, self._ck_dev(mu), B,
+                                                    plwe, self._seed32(mask_seed, "mask_seed"), self._seed32(noise_seed, "noise_seed"),
+                                                    int(first), float(stdev)))
+        return (body, ct) if full else body
+
+    def expand_ciphertexts(self, mask_seed, body, first=0, out=None):
+        """The full samples [B][n+1] of seeded ciphertexts with bodies `body` (int32 CUDA tensor [B]), expanded on the device on
+        torch's current stream (rs_expand_ciphertexts_dev) -> int32 CUDA tensor, ready for the gates and nets.*.run."""
+        B = body.numel()
+        out = self.empty(B, self.W) if out is None else out
+        assert out.numel() == B * self.W, "out must hold [B][n+1] words"
+        _check(self.L, self.L.rs_expand_ciphertexts_dev(self.h, self._ck_dev(out, self.W), self._seed32(mask_seed, "mask_seed"), int(first),
+                                                        self._ck_dev(body), B, self._stream()))
+        return out
 
     def load_synthetic_keys(self, seed):
         """A key of pseudo-random words generated ON THE DEVICE (rs_load_synthetic_keys; client.synthetic_key_words restates the

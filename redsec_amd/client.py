@@ -9,6 +9,8 @@ exactly the layouts include/redsec_hip.h documents.
 Everything is vectorised; negacyclic products with the binary TRLWE key are done as two exact
 float64 matrix products on 16-bit halves (sums stay below 2^26).
 """
+import os
+
 import numpy as np
 
 MSG_SPACE = 4096          # client/decrypt_image.cpp:37 msg_space
@@ -153,6 +155,28 @@ class SecretKeySet:
         v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
         return self.encrypt_torus(v * (1 << 20), SECALPHA, seed)
 
+    # seeded ciphertexts (include/redsec_hip.h rs_encrypt_seeded_dev): the same messages as the methods
+    # above, each sample a body word beside a public mask seed. mask_seed defaults to a fresh os.urandom(32) per call (a (mask seed,
+    # row) pair must never encrypt two messages); noise_seed (private) to another.
+    def encrypt_torus_seeded(self, mu, alpha=SECALPHA, mask_seed=None, noise_seed=None, first=0):
+        """lweSymEncrypt of the torus words mu [B] as seeded ciphertexts (keygen.encrypt_seeded) -> SeededCiphertexts."""
+        from . import keygen
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        body = keygen.encrypt_seeded(self.lwe_key, mu, mask_seed, noise_seed, first, alpha)
+        return SeededCiphertexts(self.name, self.n, mask_seed, first, body)
+
+    def encrypt_bits_seeded(self, bits, mask_seed=None, noise_seed=None, first=0):
+        """bootsSymEncrypt (+-1/8) as seeded ciphertexts."""
+        e8 = 1 << 29
+        return self.encrypt_torus_seeded(np.where(np.asarray(bits) != 0, e8, -e8), SECALPHA, mask_seed, noise_seed, first)
+
+    def encrypt_image_seeded(self, pixels, preprocess="sign", mask_seed=None, noise_seed=None, first=0):
+        """encrypt_image's messages (2 pixel - 255, or the ReLU nets' pixel / 100 - 1, over 4096) as seeded ciphertexts."""
+        px = np.asarray(pixels, dtype=np.int64).ravel()
+        v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
+        return self.encrypt_torus_seeded(v * (1 << 20), SECALPHA, mask_seed, noise_seed, first)
+
     def phase(self, ct):
         ct = np.asarray(ct, np.int32).reshape(-1, self.W)
         dot = (ct[:, :self.n].view(np.uint32).astype(np.uint64) * self.lwe_key.astype(np.uint64)).sum(axis=-1)
@@ -246,7 +270,7 @@ def read_tfhe_keyset(f, secret):
 _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
-RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352}
+RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -278,6 +302,75 @@ def read_compressed_cloud_key(f):
     ksk_body = rd(N * t * (1 << basebit)).reshape(N, t, 1 << basebit)
     assert f.read(1) == b"", "trailing bytes in compressed key file"
     return keygen.CompressedKey(name, n, seed, bk_body, ksk_body)
+
+
+class SeededCiphertexts:
+    """Seeded LWE ciphertexts (include/redsec_hip.h): the set name, the LWE dimension n, the public 32-byte
+    mask seed, the row `first` of the first sample and the bodies (int32 [B], numpy or a CUDA tensor). Sample i has the domain-7
+    mask words of row first + i. nbytes: what travels (seed, first, bodies)."""
+
+    def __init__(self, name, n, mask_seed, first, body):
+        self.name, self.n, self.mask_seed, self.first = name, int(n), bytes(mask_seed), int(first)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        self.body = body
+        if not 0 <= self.first <= (1 << 64) - len(self):
+            raise ValueError("first + B passes 2^64")
+
+    def __len__(self):
+        return int(self.body.numel() if hasattr(self.body, "numel") else np.size(self.body))
+
+    @property
+    def nbytes(self):
+        return 32 + 8 + 4 * len(self)
+
+    def numpy(self):
+        """The same ciphertexts with host bodies."""
+        body = self.body if isinstance(self.body, np.ndarray) else self.body.cpu().numpy()
+        return SeededCiphertexts(self.name, self.n, self.mask_seed, self.first, np.asarray(body, np.int32).ravel())
+
+    def expand(self):
+        """The full samples, expanded on the host (keygen.expand_ciphertexts) -> int32 [B][n+1]."""
+        from . import keygen
+        return keygen.expand_ciphertexts(self.mask_seed, self.numpy().body, self.n, self.first)
+
+
+def write_seeded_ciphertexts(f, sc, max_stdev=0.012467):
+    """An RSC1 file (binary file object): the RSK1 header with magic RSC1, the 32-byte mask seed, uint64 first, then the int32
+    bodies to the end of the file (their count is the file's length). sc: SeededCiphertexts."""
+    (_, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = PARAM_SETS[sc.name]
+    h = np.zeros((), _RS_HEADER)
+    h["magic"], h["n"], h["N"], h["k"], h["l"], h["Bgbit"], h["ks_t"], h["ks_basebit"] = RS_MAGIC["RSC1"], sc.n, N, k, l, Bgbit, t, basebit
+    h["lwe_alpha_min"], h["lwe_alpha_max"], h["tlwe_alpha_min"], h["tlwe_alpha_max"] = ks_stdev, max_stdev, bk_stdev, max_stdev
+    host = sc.numpy()
+    f.write(h.tobytes())
+    f.write(host.mask_seed)
+    f.write(np.uint64(host.first).tobytes())
+    f.write(np.ascontiguousarray(host.body, np.int32).tobytes())
+
+
+def read_seeded_ciphertexts(f, n=None):
+    """-> SeededCiphertexts of an RSC1 file (numpy bodies). Raises ValueError for a truncated file, another magic, a parameter
+    shape no set has, an n outside 1 .. the set's n, or an n other than the given one."""
+    raw = f.read(_RS_HEADER.itemsize)
+    if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSC1"]:
+        raise ValueError("not a seeded ciphertext (RSC1) file")
+    if len(raw) < _RS_HEADER.itemsize:
+        raise ValueError("truncated seeded ciphertext file: short header")
+    h = np.frombuffer(raw, _RS_HEADER)[0]
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    if name is None:
+        raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,))
+    hn = int(h["n"])
+    if not 0 < hn <= PARAM_SETS[name][0] or (n is not None and hn != int(n)):
+        raise ValueError("seeded ciphertexts of n = %d do not fit %s%s" % (hn, name, "" if n is None else " with n = %d" % int(n)))
+    seed, first = f.read(32), f.read(8)
+    if len(seed) < 32 or len(first) < 8:
+        raise ValueError("truncated seeded ciphertext file: short seed or first row")
+    rest = f.read()
+    if len(rest) % 4:
+        raise ValueError("truncated seeded ciphertext file: %d bytes of bodies is not a whole number of words" % len(rest))
+    return SeededCiphertexts(name, hn, seed, int(np.frombuffer(first, "<u8")[0]), np.frombuffer(rest, np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

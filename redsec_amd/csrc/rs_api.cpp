@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <climits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -722,6 +723,72 @@ int rs_expand_keys_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const uint8_t* mask
   RS_HIP(rs::launch_expand_bk(c->logn, e, c->num_cus, nullptr));
   RS_HIP(rs::launch_expand_ksk(e, c->num_cus, nullptr));
   RS_HIP(hipDeviceSynchronize());
+  return RS_OK;
+}
+
+// seeded LWE ciphertexts (include/redsec_hip.h): the checks both directions share
+static int seeded_args(const rs_ctx* c, rs::SeededArgs* a, const uint8_t* mask_seed, uint64_t first, size_t B) {
+  if (B > 0 && B - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + B = %llu + %zu passes 2^64", (unsigned long long)first, B);
+  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
+  rs::kg_seed_words(mask_seed, a->seed);
+  a->first = first; a->B = (long)B;
+  a->n = c->p.n; a->tile = rs::kg_ct_tile(c->p.n);
+  return RS_OK;
+}
+
+int rs_encrypt_seeded_dev(rs_ctx* c, int32_t* body, int32_t* ct, const int32_t* mu, size_t B, const int32_t* lwe_key,
+                          const uint8_t* mask_seed, const uint8_t* noise_seed, uint64_t first, double stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!body || !mu || !lwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (memcmp(mask_seed, noise_seed, 32) == 0)
+    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
+  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
+  const int n = c->p.n;
+  for (int i = 0; i < n; ++i)
+    if (lwe_key[i] != 0 && lwe_key[i] != 1) return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", i, lwe_key[i]);
+  rs::SeededArgs a{};
+  rc = seeded_args(c, &a, mask_seed, first, B);
+  if (rc) return rc;
+  if (B == 0) return RS_OK;
+  // private device copy of the key, one bit per word, zero past n; zeroed and freed before returning
+  std::vector<uint32_t> bits((size_t)(n + 31) / 32, 0u);
+  for (int i = 0; i < n; ++i) bits[(size_t)i >> 5] |= (uint32_t)lwe_key[i] << (i & 31);
+  const size_t bytes = bits.size() * sizeof(uint32_t);
+  uint32_t* d_key = nullptr;
+  RS_HIP(hipMalloc(&d_key, bytes));
+  a.ct = ct; a.body = body; a.mu = mu; a.key_bits = d_key;
+  rs::kg_seed_words(noise_seed, a.noise_seed);
+  a.sigma = stdev;
+  auto run = [&]() -> int {
+    RS_HIP(hipMemcpy(d_key, bits.data(), bytes, hipMemcpyHostToDevice));
+    RS_HIP(rs::launch_encrypt_seeded(a, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  };
+  rc = run();
+  std::fill(bits.begin(), bits.end(), 0u);
+  // the secret leaves the device before the call returns, on the error paths too
+  (void)hipDeviceSynchronize();
+  const hipError_t ez = hipMemset(d_key, 0, bytes);
+  const hipError_t es = hipDeviceSynchronize();
+  (void)hipFree(d_key);
+  if (rc != RS_OK) return rc;
+  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
+  return RS_OK;
+}
+
+int rs_expand_ciphertexts_dev(rs_ctx* c, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body, size_t B,
+                              void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!ct || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
+  rs::SeededArgs a{};
+  rc = seeded_args(c, &a, mask_seed, first, B);
+  if (rc) return rc;
+  if (B == 0) return RS_OK;
+  a.ct = ct; a.body = const_cast<int32_t*>(body);
+  RS_HIP(rs::launch_expand_ciphertexts(a, c->num_cus, (hipStream_t)stream));
   return RS_OK;
 }
 

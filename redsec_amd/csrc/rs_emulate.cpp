@@ -5,6 +5,7 @@
 // CMUX bookkeeping can be checked bit-for-bit against the oracle on a machine without a GPU
 // (pytest -m "not gpu"). It is NOT part of libredsec_hip.so and is never a fallback: the product
 // library has no CPU compute path. Built by redsec_amd/build.py as librs_emulate.so.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <type_traits>
@@ -1169,5 +1170,53 @@ void rs_emu_expand_ksk_sample(const uint8_t* mask_seed, int n, int basebit, uint
   }
   out[n] = body;
 }
+
+// seeded ciphertexts (rs_encrypt_seeded_dev / rs_expand_ciphertexts_dev) through the functions and the placement of
+// seeded_lwe_kernel, thread by thread: tiles of kg_ct_tile(n) ciphertexts, the flat (ciphertext, block) items in strides of
+// kCtThreads, the LDS staging of kg_ct_lds_word, per-ciphertext sums, then the tile stored as one contiguous span.
+// encrypt: lwe_key int32[n] 0/1, mu[B] -> body[B] and ct[B][n+1] (ct may be null); expand: body[B] -> ct[B][n+1]
+static void emu_seeded(bool encrypt, const uint8_t* mask_seed, const uint8_t* noise_seed, int n, uint64_t first, long B,
+                       const int32_t* mu, const int32_t* lwe_key, double sigma, int32_t* body, int32_t* ct) {
+  uint32_t key[8], nkey[8] = {};
+  rs::kg_seed_words(mask_seed, key);
+  if (encrypt) rs::kg_seed_words(noise_seed, nkey);
+  const int C = rs::kg_ct_tile(n), nblk = rs::kg_ct_blocks(n);
+  std::vector<uint32_t> bits((size_t)(n + 31) / 32, 0u), acc((size_t)C), lds((size_t)C * (n + 1));
+  for (int i = 0; encrypt && i < n; ++i) bits[(size_t)i >> 5] |= (uint32_t)(lwe_key[i] & 1) << (i & 31);
+  for (long i0 = 0; i0 < B; i0 += C) {
+    const int cnt = (int)std::min<long>(C, B - i0);
+    for (int t = 0; t < cnt; ++t) {
+      if (encrypt) acc[t] = 0u;
+      else lds[rs::kg_ct_lds_word(t, n, n)] = (uint32_t)body[i0 + t];
+    }
+    for (int t = 0; t < rs::kCtThreads; ++t)
+      for (int it = t; it < cnt * nblk; it += rs::kCtThreads) {
+        const int c = it / nblk, blk = it - c * nblk;
+        uint32_t w[16];
+        rs::kg_ct_mask_block(key, first + (uint64_t)(i0 + c), blk, w);
+        for (int q = 0; q < 16; ++q)
+          if (16 * blk + q < n) lds[rs::kg_ct_lds_word(c, 16 * blk + q, n)] = w[q];
+        if (encrypt) {
+          const uint32_t kb = rs::kg_ct_key_bits(bits.data(), blk);
+          for (int q = 0; q < 16; ++q) acc[c] += ((kb >> q) & 1u) ? w[q] : 0u;
+        }
+      }
+    for (int t = 0; encrypt && t < cnt; ++t) {
+      const uint32_t b = acc[t] + (uint32_t)rs::kg_ct_noise(nkey, first + (uint64_t)(i0 + t), sigma) + (uint32_t)mu[i0 + t];
+      body[i0 + t] = (int32_t)b;
+      lds[rs::kg_ct_lds_word(t, n, n)] = b;
+    }
+    if (ct)
+      for (int j = 0; j < cnt * (n + 1); ++j) ct[i0 * (n + 1) + j] = (int32_t)lds[j];
+  }
+}
+void rs_emu_encrypt_seeded(const uint8_t* mask_seed, const uint8_t* noise_seed, int n, uint64_t first, long B, const int32_t* mu,
+                           const int32_t* lwe_key, double sigma, int32_t* body, int32_t* ct) {
+  emu_seeded(true, mask_seed, noise_seed, n, first, B, mu, lwe_key, sigma, body, ct);
+}
+void rs_emu_expand_ciphertext(const uint8_t* mask_seed, int n, uint64_t first, long B, const int32_t* body, int32_t* ct) {
+  emu_seeded(false, mask_seed, nullptr, n, first, B, nullptr, nullptr, 0.0, const_cast<int32_t*>(body), ct);
+}
+int rs_emu_ct_tile(int n) { return rs::kg_ct_tile(n); }
 
 }  // extern "C"

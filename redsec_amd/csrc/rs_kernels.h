@@ -125,6 +125,22 @@ struct ExpandArgs {
 };
 hipError_t launch_expand_bk(int logn, const ExpandArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_expand_ksk(const ExpandArgs& a, int num_cus, hipStream_t st);
+// seeded LWE ciphertexts (rs_encrypt_seeded_dev, rs_expand_ciphertexts_dev; streams and placement of rs_keygen.h): ciphertext i has
+// row first + i, its mask the domain-7 words of the mask seed; encryption forms body = sum_k a_k s_k + e + mu
+struct SeededArgs {
+  int32_t* ct;                                        // [B][n+1] (16-byte alignment not needed), or nullptr: bodies only (encryption)
+  int32_t* body;                                      // [B]: written by encryption, read by expansion
+  const int32_t* mu;                                  // [B] torus messages (encryption)
+  const uint32_t* key_bits;                           // private device copy of the LWE key, 32 bits per word, zero past n (encryption)
+  uint32_t seed[8];                                   // mask seed (domain 7)
+  uint32_t noise_seed[8];                             // noise seed (domain 8, encryption)
+  uint64_t first;
+  long B;
+  int n, tile;                                        // tile = kg_ct_tile(n)
+  double sigma;
+};
+hipError_t launch_encrypt_seeded(const SeededArgs& a, int num_cus, hipStream_t st);
+hipError_t launch_expand_ciphertexts(const SeededArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,

@@ -23,7 +23,7 @@
 namespace rs {
 
 // domains (the table of include/redsec_hip.h, rs_keygen_dev)
-enum { kKgLweSecret = 1, kKgTlweSecret = 2, kKgBkMask = 3, kKgBkNoise = 4, kKgKsMask = 5, kKgKsNoise = 6 };
+enum { kKgLweSecret = 1, kKgTlweSecret = 2, kKgBkMask = 3, kKgBkNoise = 4, kKgKsMask = 5, kKgKsNoise = 6, kKgCtMask = 7, kKgCtNoise = 8 };
 
 RS_HD uint32_t kg_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
 RS_HD void kg_quarter(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) {
@@ -89,6 +89,44 @@ RS_HD bool kg_ksk_mask_block(const uint32_t (&key)[8], uint64_t s, int k0, int l
 // mask word k0 + 64 q + L
 constexpr int kKgChunk = 64 * 16;
 RS_HD int kg_ksk_chunk_word(int q, int lane) { return 64 * q + lane; }
+
+// ---- seeded LWE ciphertexts (rs_encrypt_seeded_dev, rs_expand_ciphertexts_dev), shared by seeded_lwe_kernel, the lane emulator
+// and the TFHE shim's host writer and reader ----
+
+// ciphertext row `row`: mask words 16 blk .. 16 blk + 15 = block blk of stream (7, row) of the mask seed
+RS_HD void kg_ct_mask_block(const uint32_t (&key)[8], uint64_t row, int blk, uint32_t (&w)[16]) {
+  kg_chacha_block(key, kKgCtMask, row, (uint32_t)blk, w);
+}
+// its noise word: Gaussian 0 (words 0-3) of stream (8, row) of the noise seed
+RS_HD int32_t kg_ct_noise(const uint32_t (&nkey)[8], uint64_t row, double sigma) {
+  if (sigma == 0.0) return 0;
+  uint32_t w[16];
+  kg_chacha_block(nkey, kKgCtNoise, row, 0u, w);
+  return kg_noise32(w[0], w[1], w[2], w[3], sigma);
+}
+// the 16 key bits of block blk (words 16 blk .. 16 blk + 15) from the key packed 32 bits per word, bit k & 31 of word k >> 5
+RS_HD uint32_t kg_ct_key_bits(const uint32_t* packed, int blk) { return (packed[blk >> 1] >> ((blk & 1) * 16)) & 0xffffu; }
+
+// Placement of seeded_lwe_kernel: a workgroup of kCtThreads threads owns a tile of C whole ciphertexts and walks the flat index
+// item = c nblk + blk (nblk = ceil(n / 16) ChaCha blocks per mask) in strides of kCtThreads; word k of tile ciphertext c is staged
+// at LDS word c (n + 1) + k, the tile is then stored as one contiguous span of C (n + 1) words. C is the tile size <= kCtMaxTile
+// whose staging fits kCtLdsWords and whose C nblk items leave the fewest lanes idle in the last stride (ties: the larger tile).
+constexpr int kCtThreads = 256, kCtLdsWords = 12800, kCtMaxTile = 64;
+RS_HD int kg_ct_blocks(int n) { return (n + 15) / 16; }
+RS_HD int kg_ct_tile(int n) {
+  const int nblk = kg_ct_blocks(n);
+  int cap = kCtLdsWords / (n + 1);
+  if (cap > kCtMaxTile) cap = kCtMaxTile;
+  if (cap < 1) cap = 1;
+  int best = 0;
+  long best_idle = 0, best_slots = 1;
+  for (int C = 1; C <= cap; ++C) {
+    const long items = (long)C * nblk, slots = (items + kCtThreads - 1) / kCtThreads * kCtThreads;
+    if ((slots - items) * best_slots <= best_idle * slots || best == 0) { best = C; best_idle = slots - items; best_slots = slots; }
+  }
+  return best;
+}
+RS_HD int kg_ct_lds_word(int c, int k, int n) { return c * (n + 1) + k; }
 
 // seed bytes -> the 8 little-endian key words
 RS_HD void kg_seed_words(const uint8_t* seed, uint32_t (&key)[8]) {

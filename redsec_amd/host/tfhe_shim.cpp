@@ -11,6 +11,7 @@
 #include "tfhe/tfhe.h"
 
 #include <initializer_list>
+#include <sys/stat.h>
 #include <map>
 #include <chrono>
 #include <mutex>
@@ -20,7 +21,7 @@
 #include <vector>
 
 #include "redsec_hip.h"
-#include "rs_keygen.h"   // the mask streams of a compressed key (csrc/rs_keygen.h): one statement of ChaCha20 for device and host
+#include "rs_keygen.h"   // the mask streams of compressed keys and seeded ciphertexts (csrc/rs_keygen.h): one statement of ChaCha20 for device and host
 
 // seconds spent creating device contexts and uploading / transforming keys since the last call (REDSEC_TRACE reports them apart
 // from a layer's own staging: they happen once per process, inside whichever call touches the GPU first)
@@ -49,6 +50,7 @@ inline uint32_t uniform32() { return (uint32_t)(rng()() >> 32); }
 constexpr uint32_t kMagicSecret = 0x31535352u;  // "RSS1"
 constexpr uint32_t kMagicCloud = 0x314b5352u;   // "RSK1"
 constexpr uint32_t kMagicCompressed = 0x315a5352u;   // "RSZ1": RSK1's header, the 32-byte mask seed, bk_body, ksk_body
+constexpr uint32_t kMagicSeededCt = 0x31435352u;     // "RSC1": RSK1's header, the 32-byte mask seed, uint64 first, int32 bodies
 
 struct ParamHeader {
   uint32_t magic;
@@ -354,7 +356,9 @@ void lweSubMulTo(LweSample* r, int32_t k, const LweSample* s, const LweParams* p
   r->b = (Torus32)((uint32_t)r->b - (uint32_t)k * (uint32_t)s->b); r->current_variance += (double)k * k * s->current_variance;
 }
 
-void lweSymEncrypt(LweSample* r, Torus32 message, double alpha, const LweKey* key) {
+namespace {
+// TFHE's lweSymEncrypt: masks from the shim's generator (key generation always takes this path)
+void lwe_sym_encrypt_uniform(LweSample* r, Torus32 message, double alpha, const LweKey* key) {
   const int32_t n = key->params->n;
   uint32_t b = (uint32_t)gaussian32(message, alpha);
   for (int32_t i = 0; i < n; ++i) {
@@ -364,6 +368,93 @@ void lweSymEncrypt(LweSample* r, Torus32 message, double alpha, const LweKey* ke
   }
   r->b = (Torus32)b;
   r->current_variance = alpha * alpha;
+}
+
+// ---- seeded ciphertexts (include/redsec_hip.h rs_encrypt_seeded_dev) ----
+// REDSEC_CT_FORMAT=seeded: lweSymEncrypt draws the mask of each new sample from stream (7, row) of a per-process random mask seed,
+// rows 0, 1, 2, ... in call order (the noise still comes from the shim's generator: only the masks must be reproducible), and
+// export_gate_bootstrapping_ciphertext_toFile writes RSC1 files: the first export to a file writes the header, the seed and the
+// sample's row as `first`, every later one just the body. import_gate_bootstrapping_ciphertext_fromFile reads RSC1 in every mode.
+bool ct_format_is_seeded() { const char* f = getenv("REDSEC_CT_FORMAT"); return f && strcmp(f, "seeded") == 0; }
+
+struct SeededWriter {
+  std::mutex mu;
+  bool have_seed = false;
+  uint8_t seed[32];
+  uint32_t key[8];
+  uint64_t next_row = 0;
+  std::map<const Torus32*, uint64_t> row_of;   // mask array of a sample -> the row its mask was drawn at
+};
+SeededWriter& seeded_writer() {
+  static SeededWriter* const w = new SeededWriter();
+  return *w;
+}
+
+// per open file: the position after the last record this shim read or wrote, and the row of the next sample. A state whose file
+// (device, inode) or position does not match is stale: the FILE* address was reused for another file.
+struct CtFileState {
+  dev_t dev = 0;
+  ino_t ino = 0;
+  long pos = -1;
+  uint32_t key[8];
+  uint64_t next_row = 0;
+};
+std::mutex g_ct_files_mu;
+std::map<FILE*, CtFileState>& ct_files(bool reading) {
+  static std::map<FILE*, CtFileState>* const r = new std::map<FILE*, CtFileState>();
+  static std::map<FILE*, CtFileState>* const w = new std::map<FILE*, CtFileState>();
+  return reading ? *r : *w;
+}
+void file_id(FILE* f, dev_t* dev, ino_t* ino) {
+  struct stat st;
+  if (fstat(fileno(f), &st) == 0) { *dev = st.st_dev; *ino = st.st_ino; }
+  else { *dev = 0; *ino = 0; }
+}
+// the live state of f, or null when f is at its start or its state is stale
+CtFileState* ct_file_state(FILE* f, bool reading) {
+  auto& m = ct_files(reading);
+  const auto it = m.find(f);
+  if (it == m.end()) return nullptr;
+  dev_t dev; ino_t ino;
+  file_id(f, &dev, &ino);
+  const long pos = ftell(f);
+  if (pos == 0 || it->second.dev != dev || it->second.ino != ino || it->second.pos != pos) { m.erase(it); return nullptr; }
+  return &it->second;
+}
+
+[[noreturn]] void ct_die(const char* what) {
+  fprintf(stderr, "redsec tfhe shim: REDSEC_CT_FORMAT=seeded: %s\n", what);
+  abort();
+}
+}  // namespace
+
+void lweSymEncrypt(LweSample* r, Torus32 message, double alpha, const LweKey* key) {
+  if (!ct_format_is_seeded()) { lwe_sym_encrypt_uniform(r, message, alpha, key); return; }
+  const int32_t n = key->params->n;
+  SeededWriter& w = seeded_writer();
+  std::lock_guard<std::mutex> lock(w.mu);
+  if (!w.have_seed) {
+    std::random_device rd;
+    for (int k = 0; k < 8; ++k) {
+      const uint32_t v = rd();
+      memcpy(w.seed + 4 * k, &v, 4);
+    }
+    rs::kg_seed_words(w.seed, w.key);
+    w.have_seed = true;
+  }
+  const uint64_t row = w.next_row++;
+  uint32_t b = (uint32_t)gaussian32(message, alpha);
+  for (int32_t blk = 0; 16 * blk < n; ++blk) {
+    uint32_t words[16];
+    rs::kg_ct_mask_block(w.key, row, blk, words);
+    for (int32_t q = 0; q < 16 && 16 * blk + q < n; ++q) {
+      r->a[16 * blk + q] = (Torus32)words[q];
+      b += words[q] * (uint32_t)key->key[16 * blk + q];
+    }
+  }
+  r->b = (Torus32)b;
+  r->current_variance = alpha * alpha;
+  w.row_of[r->a] = row;
 }
 Torus32 lwePhase(const LweSample* s, const LweKey* key) {
   uint32_t axs = 0;
@@ -420,7 +511,7 @@ TFheGateBootstrappingSecretKeySet* new_random_gate_bootstrapping_secret_keyset(c
         tmp.a = rowp;
         if (v == 0) { lweNoiselessTrivial(&tmp, 0, p->in_out_params); rowp[n] = 0; continue; }
         const uint32_t mess = ((uint32_t)gk->key[i] * (uint32_t)v) << (32 - (j + 1) * basebit);
-        lweSymEncrypt(&tmp, (Torus32)mess, p->in_out_params->alpha_min, lk);
+        lwe_sym_encrypt_uniform(&tmp, (Torus32)mess, p->in_out_params->alpha_min, lk);
         rowp[n] = tmp.b;
       }
   return new TFheGateBootstrappingSecretKeySet(p, bk, new_bkfft(p, bk), lk, gk);
@@ -676,19 +767,97 @@ TFheGateBootstrappingSecretKeySet* new_tfheGateBootstrappingSecretKeySet_fromFil
 // double current_variance = 4n + 16 bytes -- image.ctxt / network_output.ctxt
 // written here are byte-compatible with a TFHE client's.
 static const int32_t kLweSampleTypeUid = kUidLweSample;
+// Under REDSEC_CT_FORMAT=seeded the records are RSC1 instead (see lweSymEncrypt): a sample whose mask is no longer its stream's
+// words (after lweAddTo, say), that was not encrypted here, or whose row is not the next one of the file, cannot be written so.
+static void export_seeded(FILE* f, const LweSample* s, const TFheGateBootstrappingParameterSet* p) {
+  const int32_t n = p->in_out_params->n;
+  SeededWriter& w = seeded_writer();
+  uint64_t row = 0;
+  {
+    std::lock_guard<std::mutex> lock(w.mu);
+    const auto it = w.row_of.find(s->a);
+    if (it == w.row_of.end()) ct_die("the sample was not encrypted by lweSymEncrypt in this process; unset it to write TFHE records");
+    row = it->second;
+    for (int32_t blk = 0; 16 * blk < n; ++blk) {
+      uint32_t words[16];
+      rs::kg_ct_mask_block(w.key, row, blk, words);
+      for (int32_t q = 0; q < 16 && 16 * blk + q < n; ++q)
+        if ((uint32_t)s->a[16 * blk + q] != words[q])
+          ct_die("the sample's mask is no longer its stream's words (changed after encryption); unset it to write TFHE records");
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_ct_files_mu);
+  CtFileState* st = ct_file_state(f, false);
+  if (!st) {
+    const ParamHeader h = header_from_params(kMagicSeededCt, p);
+    write_exact(f, &h, sizeof h, "seeded ciphertext header");
+    write_exact(f, w.seed, sizeof w.seed, "mask seed");
+    write_exact(f, &row, sizeof row, "first row");
+    st = &ct_files(false)[f];
+    file_id(f, &st->dev, &st->ino);
+    st->next_row = row;
+  }
+  if (row != st->next_row) ct_die("the samples of one file must be exported in the order they were encrypted, without gaps");
+  write_exact(f, &s->b, sizeof(Torus32), "sample body");
+  st->next_row = row + 1;
+  st->pos = ftell(f);
+}
 void export_gate_bootstrapping_ciphertext_toFile(FILE* f, const LweSample* s, const TFheGateBootstrappingParameterSet* p) {
+  if (ct_format_is_seeded()) { export_seeded(f, s, p); return; }
   write_exact(f, &kLweSampleTypeUid, sizeof(int32_t), "sample type uid");
   write_exact(f, s->a, sizeof(Torus32) * (size_t)p->in_out_params->n, "sample mask");
   write_exact(f, &s->b, sizeof(Torus32), "sample body");
   write_exact(f, &s->current_variance, sizeof(double), "sample variance");
 }
+// The format is told apart by the first word of the file: 42 (TFHE records) or "RSC1". An RSC1 file's state (mask seed, next row)
+// is kept per FILE* and each mask is regenerated here from stream (7, row) of its seed.
 void import_gate_bootstrapping_ciphertext_fromFile(FILE* f, LweSample* s, const TFheGateBootstrappingParameterSet* p) {
-  int32_t uid = 0;
-  read_exact(f, &uid, sizeof(int32_t), "ciphertext type uid");
-  if (uid != kLweSampleTypeUid) { fprintf(stderr, "redsec tfhe shim: not an LweSample record (type uid %d, expected 42)\n", uid); abort(); }
-  read_exact(f, s->a, sizeof(Torus32) * (size_t)p->in_out_params->n, "ciphertext a");
-  read_exact(f, &s->b, sizeof(Torus32), "ciphertext b");
-  read_exact(f, &s->current_variance, sizeof(double), "ciphertext variance");
+  const int32_t n = p->in_out_params->n;
+  std::lock_guard<std::mutex> lock(g_ct_files_mu);
+  CtFileState* st = ct_file_state(f, true);
+  if (!st) {
+    uint32_t word = 0;
+    read_exact(f, &word, sizeof word, "ciphertext type uid");
+    if (word == kMagicSeededCt) {
+      ParamHeader h;
+      h.magic = word;
+      read_exact(f, reinterpret_cast<char*>(&h) + sizeof word, sizeof h - sizeof word, "seeded ciphertext header");
+      const ParamHeader want = header_from_params(kMagicSeededCt, p);
+      if (h.n != want.n || h.N != want.N || h.k != want.k || h.l != want.l || h.Bgbit != want.Bgbit || h.ks_t != want.ks_t ||
+          h.ks_basebit != want.ks_basebit) {
+        fprintf(stderr, "redsec tfhe shim: seeded ciphertexts of n=%d N=%d l=%d Bgbit=%d t=%d basebit=%d do not fit the key's parameters\n",
+                h.n, h.N, h.l, h.Bgbit, h.ks_t, h.ks_basebit);
+        abort();
+      }
+      uint8_t seed[32];
+      uint64_t first = 0;
+      read_exact(f, seed, sizeof seed, "mask seed");
+      read_exact(f, &first, sizeof first, "first row");
+      st = &ct_files(true)[f];
+      file_id(f, &st->dev, &st->ino);
+      rs::kg_seed_words(seed, st->key);
+      st->next_row = first;
+    } else {
+      if ((int32_t)word != kLweSampleTypeUid) {
+        fprintf(stderr, "redsec tfhe shim: not an LweSample record (type uid %d, expected 42) nor an RSC1 file\n", (int32_t)word);
+        abort();
+      }
+      read_exact(f, s->a, sizeof(Torus32) * (size_t)n, "ciphertext a");
+      read_exact(f, &s->b, sizeof(Torus32), "ciphertext b");
+      read_exact(f, &s->current_variance, sizeof(double), "ciphertext variance");
+      return;
+    }
+  }
+  read_exact(f, &s->b, sizeof(Torus32), "ciphertext body");
+  const uint64_t row = st->next_row;
+  for (int32_t blk = 0; 16 * blk < n; ++blk) {
+    uint32_t words[16];
+    rs::kg_ct_mask_block(st->key, row, blk, words);
+    for (int32_t q = 0; q < 16 && 16 * blk + q < n; ++q) s->a[16 * blk + q] = (Torus32)words[q];
+  }
+  s->current_variance = 0.;
+  st->next_row = row + 1;
+  st->pos = ftell(f);
 }
 
 // ---- GPU ----

@@ -31,6 +31,15 @@ another encryption of the same key with the gadget term of c = 0 rows moved out 
   The NOISE SEED (domains 1, 2, 4, 6: the secret keys and the noise) stays private and must differ from the mask seed.
   Layouts: bk_body int32 [n][2l][N], ksk_body int32 [N][t][2^basebit].
 
+Seeded LWE ciphertexts (rs_encrypt_seeded_dev, rs_expand_ciphertexts_dev; include/redsec_hip.h): ciphertext i of a call has
+row first + i (a uint64):
+
+  domain 7 ciphertext mask   row first + i   the n mask words a_k (mask seed, public)
+  domain 8 ciphertext noise  same row        1 Gaussian, words 0-3 (noise seed, private)
+
+  body = sum_k a_k s_k + e + mu_i (mod 2^32); expanded, the sample is the usual int32 [B][n+1] with the body at word n. Equal seeds
+  are refused; first + B must not pass 2^64; a (mask seed, row) pair must never encrypt two messages.
+
 The noise words are restated with numpy's log / cos, which may differ from the device's in the last bit of z: a restated
 noise word can then differ by one from the device's in the rare case where sigma z 2^32 lies that close to an integer. Mask
 words, secret keys and noiseless keys are restated exactly.
@@ -42,6 +51,7 @@ import numpy as np
 from . import client
 
 DOMAIN_LWE_SECRET, DOMAIN_TLWE_SECRET, DOMAIN_BK_MASK, DOMAIN_BK_NOISE, DOMAIN_KS_MASK, DOMAIN_KS_NOISE = 1, 2, 3, 4, 5, 6
+DOMAIN_CT_MASK, DOMAIN_CT_NOISE = 7, 8
 _SIGMA = b"expand 32-byte k"
 
 
@@ -340,3 +350,62 @@ def generate_compressed(backend, noise_seed=None, mask_seed=None, bk_stdev=None,
     if load:
         backend.load_compressed_keys(mask_seed, bk_body, ksk_body)
     return client.SecretKeySet.from_secret(name, lwe, tlwe), CompressedKey(name, p.n, mask_seed, bk_body, ksk_body)
+
+
+# ---- seeded LWE ciphertexts ----
+
+def _ct_rows(first, B):
+    """Rows first .. first + B - 1 as uint64 (first + B must not pass 2^64)."""
+    first, B = int(first), int(B)
+    if first < 0 or B < 0 or first + B > 1 << 64:
+        raise ValueError("first + B = %d + %d passes 2^64" % (first, B))
+    return np.uint64(first) + np.arange(B, dtype=np.uint64) if B else np.zeros(0, np.uint64)
+
+
+def ct_masks(mask_seed, n, first, B, chunk=None):
+    """Mask words of ciphertexts first .. first + B - 1: the domain-7 words of the mask seed -> uint32 [B][n]."""
+    n = int(n)
+    rows = _ct_rows(first, B)
+    chunk = chunk or max(1, (1 << 18) // ((n + 15) // 16))
+    key = _seed_words(mask_seed)
+    blocks = np.arange((n + 15) // 16, dtype=np.uint32)
+    out = np.empty((len(rows), n), np.uint32)
+    for lo in range(0, len(rows), chunk):
+        r = rows[lo:lo + chunk]
+        out[lo:lo + chunk] = _chacha_blocks(key, DOMAIN_CT_MASK, r[:, None], blocks[None, :]).reshape(len(r), -1)[:, :n]
+    return out
+
+
+def ct_noise(noise_seed, first, B, stdev):
+    """Noise words of ciphertexts first .. first + B - 1: Gaussian 0 of the domain-8 stream of the noise seed -> int32 [B]."""
+    rows = _ct_rows(first, B)
+    if stdev == 0 or len(rows) == 0:
+        return np.zeros(len(rows), np.int32)
+    w = _chacha_blocks(_seed_words(noise_seed), DOMAIN_CT_NOISE, rows, np.uint32(0))[:, :4]
+    return noise32(w, stdev)[:, 0]
+
+
+def _check_seeds(mask_seed, noise_seed):
+    if bytes(mask_seed) == bytes(noise_seed):
+        raise ValueError("mask seed and noise seed are equal: the public mask seed would reveal the noise")
+
+
+def encrypt_seeded(lwe_key, mu, mask_seed, noise_seed, first=0, stdev=client.SECALPHA):
+    """Bodies of seeded ciphertexts of the torus words mu [B] under lwe_key (rs_encrypt_seeded_dev restated) -> int32 [B]."""
+    _check_seeds(mask_seed, noise_seed)
+    lwe = np.asarray(lwe_key, np.int64).ravel()
+    mu = np.asarray(mu).astype(np.int64).ravel()
+    a = ct_masks(mask_seed, lwe.size, first, mu.size).astype(np.uint64)
+    dot = (a * lwe.astype(np.uint64)).sum(axis=-1) if mu.size else np.zeros(0, np.uint64)
+    e = ct_noise(noise_seed, first, mu.size, stdev).view(np.uint32).astype(np.uint64)
+    return ((dot + e + (mu & 0xFFFFFFFF).astype(np.uint64)) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+
+
+def expand_ciphertexts(mask_seed, body, n, first=0):
+    """The full samples of seeded ciphertexts (rs_expand_ciphertexts_dev restated): the domain-7 masks beside the bodies
+    -> int32 [B][n+1]."""
+    body = np.asarray(body, np.int32).ravel()
+    out = np.empty((body.size, int(n) + 1), np.int32)
+    out[:, :int(n)] = ct_masks(mask_seed, n, first, body.size).view(np.int32)
+    out[:, int(n)] = body
+    return out
