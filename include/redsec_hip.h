@@ -167,6 +167,47 @@ int rs_encrypt_seeded_dev(rs_ctx* ctx, int32_t* body, int32_t* ct, const int32_t
 int rs_expand_ciphertexts_dev(rs_ctx* ctx, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body,
                               size_t B, void* stream);
 
+/* Device decryption and the exact noise audit of evaluation keys. CLIENT side: a server holds no secret.
+ * All three are synchronous like rs_keygen_dev and additionally wait for ALL work queued on the context's device, on every stream,
+ * before they read their inputs. Secret keys are HOST pointers with words in {0, 1}; their private device copy (packed bits) is
+ * zeroed and freed on every path. The context's loaded key is not touched and none is needed. The arithmetic is 32-bit integer
+ * only (a'*S is a signed sum of rotated copies of a' over the set bits of S): no floating-point product, so they work on every
+ * context and share nothing with the split-key product that generated the key. No CPU fallback: RS_ERR_NO_DEVICE without a device.
+ *
+ * rs_phase_dev: phase[i] = b_i - sum_k a_ik key_k (mod 2^32) of ct int32[B][dim+1]. dim = n with the LWE key, or dim = k N with the
+ * TRLWE key read as an LWE key (the extracted key of rs_bootstrap_wo_ks_dev's output). phase, ct DEVICE; key HOST int32[dim].
+ * B = 0 is a no-op. RS_ERR_INVALID: null pointer, dim not n or k N, key word outside {0, 1}. */
+int rs_phase_dev(rs_ctx* ctx, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim);
+
+typedef struct rs_key_audit {
+  uint32_t bk_max_abs, ksk_max_abs;   /* largest |noise word| read as signed 32-bit (|INT32_MIN| = 2^31) */
+  uint64_t bk_over, ksk_over;         /* noise words with |e| > bk_limit / ksk_limit */
+  uint64_t ksk_zero_bad;              /* full key only: v = 0 samples with any non-zero word */
+  uint64_t bk_words, ksk_words;       /* noise words looked at: n 2l N and N t (2^basebit - 1); 0 for a skipped half */
+} rs_key_audit;
+
+/* "Is this key, as it lies in device memory, an encryption of my secret with the noise I asked for?" -- every word of it.
+ * Noise words, all arithmetic mod 2^32, products negacyclic, g_j = 2^(32 - (j+1) Bgbit), row p = c l + j of key bit s_i:
+ *   bk, full key, stored row (a', b):  e = b - a'*S - s_i g_j X^0 for c = 1;  e = b - a'*S + s_i g_j S for c = 0
+ *     (for c = 0 the stored mask carries the gadget term, a' = a + s_i g_j X^0, so b - a'*S = e - s_i g_j S);
+ *   bk, compressed: the same two formulas with a' = the domain-3 stream of the mask seed and b = the body row;
+ *   ksk sample (i, j, v), v >= 1:  e = b - sum_k a_k s_k - ((S_i v) << (32 - (j+1) basebit)); compressed: a = domain 5, b = the body word;
+ *   ksk, v = 0: the noise word is 0. Full key: the sample counts in ksk_zero_bad if any of its n + 1 words is non-zero.
+ *     Compressed: the body word is ignored, as rs_expand_keys_dev ignores it.
+ * A correctly generated key returns exactly the generator's noise words (the domain-4 and domain-6 Gaussians of rs_keygen_dev); a
+ * noiseless key returns zeros. redsec_amd/keygen.py restates it (bk_noise, ksk_noise, audit; noise_limits gives default limits).
+ *
+ * rs_audit_keys_dev: the full key, layouts of rs_load_keys (no alignment needed). bk or ksk may be NULL (that half is skipped; both
+ * NULL is RS_ERR_INVALID). bk_noise int32[n][2l][N] and ksk_noise int32[N][t][2^basebit] are optional DEVICE outputs (NULL: report
+ * only). report is HOST. RS_ERR_INVALID also for a null report or key and key words outside {0, 1}.
+ * rs_audit_compressed_keys_dev: the same on a compressed key WITHOUT expanding it: masks regenerated from the public mask seed. */
+int rs_audit_keys_dev(rs_ctx* ctx, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise,
+                      const int32_t* bk, const int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key,
+                      uint32_t bk_limit, uint32_t ksk_limit);
+int rs_audit_compressed_keys_dev(rs_ctx* ctx, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise,
+                                 const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body,
+                                 const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit, uint32_t ksk_limit);
+
 /* Arithmetic of the external product (both keys are resident after rs_load_keys; switching is free):
  *   RS_MODE_FFT        folded 512-point complex FP64 FFT -- the arithmetic class of TFHE's own
  *                      tGswFFTExternMulToTLwe -- rounded to the nearest integer. The true product is an

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
     "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev",
+    "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -48,6 +49,11 @@ class RsConvShape(C.Structure):
 class RsPoolShape(C.Structure):
     _fields_ = [(f, C.c_int32) for f in
                 ("H", "Wd", "C", "win_h", "win_w", "stride_h", "stride_w", "off_h", "off_w", "Ho", "Wo")]
+
+
+class RsKeyAudit(C.Structure):
+    _fields_ = [("bk_max_abs", C.c_uint32), ("ksk_max_abs", C.c_uint32), ("bk_over", C.c_uint64), ("ksk_over", C.c_uint64),
+                ("ksk_zero_bad", C.c_uint64), ("bk_words", C.c_uint64), ("ksk_words", C.c_uint64)]
 
 
 _lib = None
@@ -97,6 +103,9 @@ def load_library(path=None):
     L.rs_load_compressed_keys_dev.argtypes = [vp, C.c_char_p, vp, vp]
     L.rs_encrypt_seeded_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, _i32p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_double]
     L.rs_expand_ciphertexts_dev.argtypes = [vp, vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp]
+    L.rs_phase_dev.argtypes = [vp, vp, vp, C.c_size_t, _i32p, C.c_int32]
+    L.rs_audit_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
+    L.rs_audit_compressed_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, C.c_char_p, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
     L.rs_reserve.argtypes = [vp, C.c_size_t]
     L.rs_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_bootstrap.argtypes = [vp, _i32p, _i32p, C.c_int32, C.c_size_t]
@@ -335,6 +344,52 @@ class Backend:
         _check(self.L, self.L.rs_expand_ciphertexts_dev(self.h, self._ck_dev(out, self.W), self._seed32(mask_seed, "mask_seed"), int(first),
                                                         self._ck_dev(body), B, self._stream()))
         return out
+
+    # ---- device decryption and the noise audit of evaluation keys (CLIENT side) ----
+    def phase(self, ct, key):
+        """Phases b - sum_k a_k key_k of ct (int32 CUDA tensor [B][dim+1]) under the host 0/1 key of dim = len(key) words, taken on
+        the device (rs_phase_dev, synchronous; waits for every stream of the device) -> int32 CUDA tensor [B]. dim = n with the LWE
+        key, dim = N with the ring key for the output of bootstrap_wo_ks."""
+        key, pkey = _np_i32(key)
+        dim = key.size
+        B = ct.numel() // (dim + 1)
+        assert ct.numel() == B * (dim + 1), "ct must hold [B][dim+1] words"
+        out = self.empty(B)
+        _check(self.L, self.L.rs_phase_dev(self.h, self._ck_dev(out), self._ck_dev(ct), B, pkey, dim))
+        return out
+
+    def _audit(self, call, lwe_key, tlwe_key, bk, ksk, limits, noise, shapes, extra=()):
+        from . import keygen
+        p = self.p
+        lwe, plwe = _np_i32(lwe_key)
+        tlwe, ptlwe = _np_i32(tlwe_key)
+        assert lwe.size == p.n and tlwe.size == p.N, "secret keys have the wrong size"
+        assert bk is None or bk.numel() == shapes[0], "bk has the wrong size"
+        assert ksk is None or ksk.numel() == shapes[1], "ksk has the wrong size"
+        bk_limit, ksk_limit = keygen.noise_limits(keygen.set_name(p)) if limits is None else limits
+        bk_noise = self.empty(p.n, 2 * p.bk_l, p.N) if noise and bk is not None else None
+        ksk_noise = self.empty(p.N, p.ks_t, 1 << p.ks_basebit) if noise and ksk is not None else None
+        dev = lambda t: None if t is None else self._ck_dev(t)
+        rep = RsKeyAudit()
+        _check(self.L, call(self.h, C.byref(rep), dev(bk_noise), dev(ksk_noise), *extra, dev(bk), dev(ksk), plwe, ptlwe,
+                            int(bk_limit), int(ksk_limit)))
+        out = {f: int(getattr(rep, f)) for f, _ in RsKeyAudit._fields_}
+        if noise:
+            out.update(bk_noise=bk_noise, ksk_noise=ksk_noise)
+        return out
+
+    def audit_keys(self, lwe_key, tlwe_key, bk=None, ksk=None, limits=None, noise=False):
+        """Exact noise audit of a full evaluation key in device memory under its secret (rs_audit_keys_dev, synchronous): bk
+        [n][2l][2][N] and ksk [N][t][2^basebit][n+1] int32 CUDA tensors, either may be None (skipped). limits = (bk_limit, ksk_limit),
+        default keygen.noise_limits of the set. -> a dict of the rs_key_audit fields, plus bk_noise [n][2l][N] and ksk_noise
+        [N][t][2^basebit] (int32 CUDA tensors, None for a skipped half) with noise=True."""
+        return self._audit(self.L.rs_audit_keys_dev, lwe_key, tlwe_key, bk, ksk, limits, noise, self._key_sizes())
+
+    def audit_compressed_keys(self, lwe_key, tlwe_key, mask_seed, bk_body, ksk_body, limits=None, noise=False):
+        """The same audit of a compressed key, without expanding it (rs_audit_compressed_keys_dev): the masks are regenerated from
+        the public mask seed."""
+        return self._audit(self.L.rs_audit_compressed_keys_dev, lwe_key, tlwe_key, bk_body, ksk_body, limits, noise, self._body_sizes(),
+                           extra=(self._seed32(mask_seed, "mask_seed"),))
 
     def load_synthetic_keys(self, seed):
         """A key of pseudo-random words generated ON THE DEVICE (rs_load_synthetic_keys; client.synthetic_key_words restates the

@@ -18,8 +18,8 @@ INCLUDE = os.path.join(ROOT, "include")
 HIP_LIB = os.path.join(HERE, "libredsec_hip.so")
 EMU_LIB = os.path.join(HERE, "librs_emulate.so")
 
-HIP_SOURCES = ["rs_bootstrap.hip", "rs_general.hip", "rs_kernels.hip", "rs_seeded.hip", "rs_api.cpp"]
-HIP_DEPS = HIP_SOURCES + ["rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
+HIP_SOURCES = ["rs_bootstrap.hip", "rs_general.hip", "rs_kernels.hip", "rs_seeded.hip", "rs_audit.hip", "rs_api.cpp"]
+HIP_DEPS = HIP_SOURCES + ["rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_audit.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
 # Objects of the product library: (object name, source, extra flags). rs_bootstrap.hip is compiled three times (its RS_BS_PART
 # switch): part 1 -- the FFT / exact-NTT blind-rotation kernels and the split duo form -- with LLVM's post-register-allocation
 # scheduler off: its in-block reordering of the hand-laid-out LDS / FP64 sequences costs these kernels 1-3 % (same-box A/B,
@@ -38,10 +38,12 @@ HIP_OBJECTS = [
     ("rs_kernels", "rs_kernels.hip", []),
     # seeded ciphertexts (seeded_lwe_kernel) in an object of their own: every kernel of rs_general keeps its instructions
     ("rs_seeded", "rs_seeded.hip", []),
+    # device decryption and the key audit (lwe_phase_kernel, audit_bk_kernel, audit_ksk_kernel), likewise in an object of their own
+    ("rs_audit", "rs_audit.hip", []),
     ("rs_api", "rs_api.cpp", []),
 ]
 EMU_SOURCES = ["rs_emulate.cpp"]
-EMU_DEPS = EMU_SOURCES + ["rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_host.h"]
+EMU_DEPS = EMU_SOURCES + ["rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_audit.h", "rs_host.h"]
 
 
 def _abs(paths):

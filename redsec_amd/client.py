@@ -177,25 +177,29 @@ class SecretKeySet:
         v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
         return self.encrypt_torus_seeded(v * (1 << 20), SECALPHA, mask_seed, noise_seed, first)
 
-    def phase(self, ct):
+    def phase(self, ct, backend=None):
+        """Phases b - sum_k a_k s_k of ct [B][n+1]; with backend= (a redsec_amd.Backend) ct is an int32 CUDA tensor and the phase is
+        taken on the device (rs_phase_dev)."""
+        if backend is not None:
+            return backend.phase(ct.reshape(-1, self.W), self.lwe_key).cpu().numpy()
         ct = np.asarray(ct, np.int32).reshape(-1, self.W)
         dot = (ct[:, :self.n].view(np.uint32).astype(np.uint64) * self.lwe_key.astype(np.uint64)).sum(axis=-1)
         return _wrap32(ct[:, self.n].view(np.uint32).astype(np.uint64) - dot)
 
-    def decrypt_bits(self, ct):
-        return (self.phase(ct) > 0).astype(np.int64)
+    def decrypt_bits(self, ct, backend=None):
+        return (self.phase(ct, backend) > 0).astype(np.int64)
 
-    def decrypt_ints(self, ct, msize=MSG_SPACE):
+    def decrypt_ints(self, ct, msize=MSG_SPACE, backend=None):
         """client/decrypt_image.cpp:52-58: round the phase to multiples of 1/msize, signed."""
-        ph = self.phase(ct).view(np.uint32).astype(np.uint64)
+        ph = self.phase(ct, backend).view(np.uint32).astype(np.uint64)
         interv = 1 << (32 - int(np.log2(msize)))
         m = ((ph + interv // 2) // interv) % msize
         m = m.astype(np.int64)
         return np.where(m > msize // 2, m - msize, m)
 
-    def classify(self, logits_ct):
+    def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
-        return int(np.argmax(self.decrypt_ints(logits_ct)))
+        return int(np.argmax(self.decrypt_ints(logits_ct, backend=backend)))
 
 
 # ---- TFHE v1.1 file formats (the reference's client/*.cpp and nets/*/*/main.cpp exchange these files) -------------

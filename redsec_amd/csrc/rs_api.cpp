@@ -378,6 +378,42 @@ void destroy_ctx(rs_ctx* c) {
 
 bool env_on(const char* name) { const char* v = getenv(name); return v && *v && strcmp(v, "0") != 0; }
 
+// ---- helpers of the secret-key calls on device data (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) ----
+// a 0/1 key appended to `bits`, 32 per word from a fresh word on; the index of the first word outside {0, 1}, or -1
+int pack_key_bits(const int32_t* key, int count, std::vector<uint32_t>& bits) {
+  const size_t base = bits.size();
+  bits.resize(base + (size_t)(count + 31) / 32, 0u);
+  for (int i = 0; i < count; ++i) {
+    if (key[i] != 0 && key[i] != 1) return i;
+    bits[base + ((size_t)i >> 5)] |= (uint32_t)key[i] << (i & 31);
+  }
+  return -1;
+}
+
+// run(d_words, d_extra) with a private device buffer that holds `words` followed by `extra` zeroed bytes. The secret leaves the
+// device (and `words`) before this returns, on the error paths too, as in keygen_impl.
+template <class Run>
+int with_secret_copy(std::vector<uint32_t>& words, size_t extra, Run run) {
+  const size_t key_bytes = (words.size() * sizeof(uint32_t) + 15) & ~(size_t)15, bytes = key_bytes + extra;
+  char* d = nullptr;
+  auto body = [&]() -> int {
+    RS_HIP(hipMalloc(&d, bytes));
+    RS_HIP(hipMemset(d, 0, bytes));
+    RS_HIP(hipMemcpy(d, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return run(reinterpret_cast<const uint32_t*>(d), d + key_bytes);
+  };
+  const int rc = body();
+  std::fill(words.begin(), words.end(), 0u);
+  if (!d) return rc;
+  (void)hipDeviceSynchronize();
+  const hipError_t ez = hipMemset(d, 0, bytes);
+  const hipError_t es = hipDeviceSynchronize();
+  (void)hipFree(d);
+  if (rc != RS_OK) return rc;
+  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
+  return RS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -790,6 +826,76 @@ int rs_expand_ciphertexts_dev(rs_ctx* c, int32_t* ct, const uint8_t* mask_seed, 
   a.ct = ct; a.body = const_cast<int32_t*>(body);
   RS_HIP(rs::launch_expand_ciphertexts(a, c->num_cus, (hipStream_t)stream));
   return RS_OK;
+}
+
+// ---- device decryption and the noise audit of evaluation keys (CLIENT side; kernels of rs_audit.hip, integer arithmetic only) ----
+
+int rs_phase_dev(rs_ctx* c, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!phase || !ct || !key) return fail(RS_ERR_INVALID, "null pointer");
+  if (dim != c->p.n && dim != c->p.k * c->p.N) return fail(RS_ERR_INVALID, "dim = %d is neither n = %d nor k N = %d", dim, c->p.n, c->p.k * c->p.N);
+  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
+  std::vector<uint32_t> bits;
+  const int bad = pack_key_bits(key, dim, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "key[%d] = %d is not 0 or 1", bad, key[bad]); }
+  if (B == 0) { std::fill(bits.begin(), bits.end(), 0u); return RS_OK; }
+  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device, side streams included, has written ct
+    rs::PhaseArgs a{phase, ct, d_bits, (long)B, dim};
+    RS_HIP(rs::launch_lwe_phase(a, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  });
+}
+
+// rs_audit_keys_dev (mask_seed null: bk / ksk are the full key) and rs_audit_compressed_keys_dev (the bodies)
+static int audit_impl(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed, bool compressed,
+                      const int32_t* bk, const int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit,
+                      uint32_t ksk_limit) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!report || !lwe_key || !tlwe_key || (compressed && !mask_seed)) return fail(RS_ERR_INVALID, "null pointer");
+  if (!bk && !ksk) return fail(RS_ERR_INVALID, "both halves of the key are null: nothing to audit");
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  int bad = pack_key_bits(lwe_key, p.n, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
+  const size_t lwe_words = bits.size();
+  bad = pack_key_bits(tlwe_key, p.N, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
+  rs::AuditReportDev dev{};
+  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
+    rs::AuditArgs a{};
+    a.bk = bk; a.ksk = ksk; a.bk_noise = bk_noise; a.ksk_noise = ksk_noise;
+    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    if (compressed) rs::kg_seed_words(mask_seed, a.seed);
+    a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
+    a.bk_limit = bk_limit; a.ksk_limit = ksk_limit;
+    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
+    if (bk) RS_HIP(rs::launch_audit_bk(a, compressed, c->num_cus, nullptr));
+    if (ksk) RS_HIP(rs::launch_audit_ksk(a, compressed, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
+    return RS_OK;
+  });
+  if (rc != RS_OK) return rc;
+  report->bk_max_abs = dev.bk_max_abs; report->ksk_max_abs = dev.ksk_max_abs;
+  report->bk_over = dev.bk_over; report->ksk_over = dev.ksk_over; report->ksk_zero_bad = dev.ksk_zero_bad;
+  report->bk_words = bk ? (uint64_t)p.n * (uint64_t)(2 * p.bk_l) * (uint64_t)p.N : 0u;
+  report->ksk_words = ksk ? (uint64_t)p.N * (uint64_t)p.ks_t * (((uint64_t)1 << p.ks_basebit) - 1u) : 0u;
+  return RS_OK;
+}
+
+int rs_audit_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const int32_t* bk, const int32_t* ksk,
+                      const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit, uint32_t ksk_limit) {
+  return audit_impl(c, report, bk_noise, ksk_noise, nullptr, false, bk, ksk, lwe_key, tlwe_key, bk_limit, ksk_limit);
+}
+int rs_audit_compressed_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed,
+                                 const int32_t* bk_body, const int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
+                                 uint32_t bk_limit, uint32_t ksk_limit) {
+  return audit_impl(c, report, bk_noise, ksk_noise, mask_seed, true, bk_body, ksk_body, lwe_key, tlwe_key, bk_limit, ksk_limit);
 }
 
 int rs_reserve(rs_ctx* c, size_t max_batch) { return rs_reserve_stream(c, max_batch, nullptr); }

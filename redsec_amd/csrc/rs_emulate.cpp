@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "rs_audit.h"
 #include "rs_general.h"
 #include "rs_host.h"
 #include "rs_keygen.h"
@@ -1218,5 +1219,97 @@ void rs_emu_expand_ciphertext(const uint8_t* mask_seed, int n, uint64_t first, l
   emu_seeded(false, mask_seed, nullptr, n, first, B, nullptr, nullptr, 0.0, const_cast<int32_t*>(body), ct);
 }
 int rs_emu_ct_tile(int n) { return rs::kg_ct_tile(n); }
+
+// ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of
+// rs_audit.h, as the kernels of rs_audit.hip place them: a wave of 64 lanes per LWE sample, a workgroup of kAuThreads per bk row ----
+static std::vector<uint32_t> emu_pack_bits(const int32_t* key, int count) {
+  std::vector<uint32_t> bits((size_t)(count + 31) / 32, 0u);
+  for (int i = 0; i < count; ++i) bits[(size_t)i >> 5] |= (uint32_t)(key[i] & 1) << (i & 31);
+  return bits;
+}
+// lwe_phase_kernel: ct[B][dim+1], key int32[dim] 0/1 -> phase[B]
+void rs_emu_phase(const int32_t* ct, long B, int dim, const int32_t* key, int32_t* phase) {
+  const std::vector<uint32_t> bits = emu_pack_bits(key, dim);
+  for (long i = 0; i < B; ++i) {
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(ct) + i * (dim + 1);
+    uint32_t dot = 0u;
+    for (int lane = 0; lane < 64; ++lane) dot += rs::au_lane_dot(row, dim, bits.data(), lane);
+    phase[i] = (int32_t)(row[dim] - dot);
+  }
+}
+// audit_bk_kernel: the noise words of bk row `row`. seeded = 0: stored = the full key's row int32[2][N]; seeded = 1: stored = the
+// body row int32[N], the mask regenerated from mask_seed. -> noise[N]
+void rs_emu_audit_bk_row(int seeded, const uint8_t* mask_seed, int N, int l, int bgbit, uint64_t row, const int32_t* stored,
+                         const int32_t* lwe_key, int n, const int32_t* tlwe_key, int32_t* noise) {
+  const std::vector<uint32_t> lwe = emu_pack_bits(lwe_key, n), S = emu_pack_bits(tlwe_key, N);
+  std::vector<uint16_t> list((size_t)N);
+  int cnt = 0;
+  for (int w = 0; w < N / 32; ++w) cnt = rs::au_list_word(S[w], w, cnt, list.data());
+  std::vector<uint32_t> a((size_t)N);
+  const uint32_t* b_row;
+  if (seeded) {
+    uint32_t key[8];
+    rs::kg_seed_words(mask_seed, key);
+    for (int t = 0; t < rs::kAuThreads; ++t)
+      for (int blk = t; blk < N / 16; blk += rs::kAuThreads) {
+        uint32_t w[16];
+        rs::kg_bk_mask_block(key, row, blk, w);
+        for (int q = 0; q < 16; ++q) a[16 * blk + q] = w[q];
+      }
+    b_row = reinterpret_cast<const uint32_t*>(stored);
+  } else {
+    for (int k = 0; k < N; ++k) a[k] = (uint32_t)stored[k];
+    b_row = reinterpret_cast<const uint32_t*>(stored) + N;
+  }
+  int i, c, j;
+  rs::au_bk_row(row, l, i, c, j);
+  const uint32_t s = rs::au_key_bit(lwe.data(), i), g = rs::au_gadget(j, bgbit);
+  for (int t = 0; t < rs::kAuThreads; ++t)
+    for (int k0 = t; k0 < N; k0 += rs::kAuThreads * rs::kAuKpt) {
+      uint32_t acc[rs::kAuKpt];
+      rs::au_bk_products(a.data(), N, list.data(), cnt, k0, acc);
+      for (int q = 0; q < rs::kAuKpt; ++q) {
+        const int k = k0 + rs::kAuThreads * q;
+        noise[k] = (int32_t)rs::au_bk_noise(b_row[k], acc[q], rs::au_bk_message(c, s, g, k, rs::au_key_bit(S.data(), k)));
+      }
+    }
+}
+// audit_ksk_kernel: the noise word of ksk sample s. seeded = 0: stored = the sample int32[n+1]; seeded = 1: stored = its body word.
+// *zero_bad = 1 for a v = 0 sample of a full key with a non-zero word
+int32_t rs_emu_audit_ksk_word(int seeded, const uint8_t* mask_seed, int n, int t, int basebit, uint64_t s, const int32_t* stored,
+                              const int32_t* lwe_key, int32_t S_i_of_sample, int* zero_bad) {
+  const std::vector<uint32_t> lwe = emu_pack_bits(lwe_key, n);
+  const uint32_t* row = reinterpret_cast<const uint32_t*>(stored);
+  int i, j, v;
+  rs::au_ksk_sample(s, t, basebit, i, j, v);
+  *zero_bad = 0;
+  if (v == 0) {
+    uint32_t any = 0u;
+    for (int lane = 0; !seeded && lane < 64; ++lane) any |= rs::au_lane_or(row, n, lane);
+    *zero_bad = any != 0u;
+    return 0;
+  }
+  uint32_t dot = 0u, b;
+  if (seeded) {
+    uint32_t key[8];
+    rs::kg_seed_words(mask_seed, key);
+    for (int lane = 0; lane < 64; ++lane)
+      for (int k0 = 0; k0 < n; k0 += rs::kKgChunk) dot += rs::au_ksk_seeded_lane_dot(key, s, k0, lane, n, lwe.data());
+    b = row[0];
+  } else {
+    for (int lane = 0; lane < 64; ++lane) dot += rs::au_lane_dot(row, n, lwe.data(), lane);
+    b = row[n];
+  }
+  return (int32_t)rs::au_ksk_noise(b, dot, rs::au_ksk_message((uint32_t)(S_i_of_sample & 1), v, j, basebit));
+}
+// the report reduction: `count` noise words tallied by `parts` threads (word w by thread w % parts), the tallies then merged
+void rs_emu_audit_reduce(const int32_t* noise, long count, uint32_t limit, int parts, uint32_t* max_abs, uint64_t* over) {
+  std::vector<rs::AuTally> tally((size_t)parts, rs::AuTally{0u, 0ull});
+  for (long w = 0; w < count; ++w) rs::au_tally_word(tally[(size_t)(w % parts)], (uint32_t)noise[w], limit);
+  rs::AuTally all{0u, 0ull};
+  for (int p = parts - 1; p >= 0; --p) rs::au_tally_merge(all, tally[(size_t)p]);
+  *max_abs = all.max_abs;
+  *over = all.over;
+}
 
 }  // extern "C"

@@ -141,6 +141,29 @@ struct SeededArgs {
 };
 hipError_t launch_encrypt_seeded(const SeededArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_expand_ciphertexts(const SeededArgs& a, int num_cus, hipStream_t st);
+// device decryption and the exact noise audit of evaluation keys (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev;
+// per-word arithmetic of rs_audit.h, 32-bit integer only). Secret keys are private device copies packed 32 bits per word.
+constexpr int kAuMaxDim = 16384;                      // largest LWE dimension a packed key in LDS serves (rs_create's limit on n)
+struct PhaseArgs {
+  int32_t* phase;                                     // [B]
+  const int32_t* ct;                                  // [B][dim+1]
+  const uint32_t* key_bits;                           // [ceil(dim / 32)], zero past dim
+  long B;
+  int dim;
+};
+hipError_t launch_lwe_phase(const PhaseArgs& a, int num_cus, hipStream_t st);
+struct AuditReportDev { unsigned long long bk_over, ksk_over, ksk_zero_bad; unsigned int bk_max_abs, ksk_max_abs; };   // zeroed by the caller
+struct AuditArgs {
+  const int32_t* bk; const int32_t* ksk;              // full key: layouts of rs_load_keys; compressed: the bodies [n][2l][N], [N][t][2^basebit]
+  int32_t* bk_noise; int32_t* ksk_noise;              // optional outputs [n][2l][N], [N][t][2^basebit]
+  const uint32_t* lwe_bits; const uint32_t* tlwe_bits;   // [ceil(n / 32)], [N / 32]
+  uint32_t seed[8];                                   // compressed: the mask seed (domains 3, 5)
+  int n, N, l, bgbit, t, basebit;
+  uint32_t bk_limit, ksk_limit;
+  AuditReportDev* report;
+};
+hipError_t launch_audit_bk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
+hipError_t launch_audit_ksk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,

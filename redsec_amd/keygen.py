@@ -40,6 +40,13 @@ row first + i (a uint64):
   body = sum_k a_k s_k + e + mu_i (mod 2^32); expanded, the sample is the usual int32 [B][n+1] with the body at word n. Equal seeds
   are refused; first + B must not pass 2^64; a (mask seed, row) pair must never encrypt two messages.
 
+Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
+all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
+
+  bk row p = c l + j of s_i, stored (a', b): e = b - a'*S - s_i g_j X^0 (c = 1), e = b - a'*S + s_i g_j S (c = 0); compressed: a' = the
+  domain-3 stream of the mask seed, b = the body row. ksk sample (i, j, v >= 1): e = b - sum_k a_k s_k - ((S_i v) << (32 - (j+1) basebit));
+  v = 0: the noise word is 0 and, in a full key, every word of the sample must be 0. bk_noise / ksk_noise / audit restate it.
+
 The noise words are restated with numpy's log / cos, which may differ from the device's in the last bit of z: a restated
 noise word can then differ by one from the device's in the rare case where sigma z 2^32 lies that close to an integer. Mask
 words, secret keys and noiseless keys are restated exactly.
@@ -409,3 +416,95 @@ def expand_ciphertexts(mask_seed, body, n, first=0):
     out[:, :int(n)] = ct_masks(mask_seed, n, first, body.size).view(np.int32)
     out[:, int(n)] = body
     return out
+
+
+# ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
+
+GAUSS_BOUND = 8.58   # Box-Muller with u1 >= 2^-53: |z| <= sqrt(2 * 53 * ln 2) = 8.572
+
+
+def noise_limits(name):
+    """Default (bk_limit, ksk_limit) of the audit = floor(8.58 sigma 2^32) + 1 for the set's deviations. A bound, not a statistic:
+    u1 >= 2^-53 gives |z| <= 8.572, so no noise word of an honestly generated key exceeds it."""
+    s = _shape(name)
+    return tuple(int(np.floor(GAUSS_BOUND * sigma * 2.0 ** 32)) + 1 for sigma in (s["bk_stdev"], s["ks_stdev"]))
+
+
+def bk_noise(name, lwe_key, tlwe_key, stored, rows=None, mask_seed=None, chunk=256):
+    """Noise words of bk rows i 2l + p (all n 2l rows if rows is None) -> int32 [R][N]. Full key (mask_seed None): stored holds the
+    rows [R][2][N]; compressed: stored holds the body rows [R][N] and the masks are the domain-3 streams of mask_seed. The LWE
+    dimension is len(lwe_key)."""
+    s = _shape(name, len(lwe_key))
+    l, Bgbit, N = s["l"], s["Bgbit"], s["N"]
+    rows = np.arange(s["n"] * 2 * l) if rows is None else np.asarray(rows, np.int64).ravel()
+    stored = np.asarray(stored, np.int32).reshape(len(rows), -1, N)
+    assert stored.shape[1] == (2 if mask_seed is None else 1), "stored rows have the wrong shape"
+    lwe = np.asarray(lwe_key).astype(np.uint32)
+    tlwe = np.asarray(tlwe_key).astype(np.uint32)
+    out = np.empty((len(rows), N), np.int32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(rows), chunk):
+            r = rows[lo:lo + chunk]
+            if mask_seed is None:
+                A = np.ascontiguousarray(stored[lo:lo + chunk, 0]).view(np.uint32)
+            else:
+                A = chacha20_words(mask_seed, DOMAIN_BK_MASK, r, N)
+            E = np.ascontiguousarray(stored[lo:lo + chunk, -1]).view(np.uint32) - _times_binary(A, tlwe_key)
+            p = r % (2 * l)
+            c, j = p // l, p % l
+            gadget = lwe[r // (2 * l)] * (np.uint32(1) << (32 - (j + 1) * Bgbit).astype(np.uint32))
+            E[c == 1, 0] -= gadget[c == 1]
+            E[c == 0] += gadget[c == 0, None] * tlwe[None, :]
+            out[lo:lo + chunk] = E.view(np.int32)
+    return out
+
+
+def ksk_noise(name, lwe_key, tlwe_key, stored, rows=None, mask_seed=None, chunk=4096):
+    """Noise words of ksk samples s = (i t + j) 2^basebit + v (all of them if rows is None) -> int32 [R]; 0 for v = 0. Full key
+    (mask_seed None): stored holds the samples [R][n+1]; compressed: stored holds the body words [R] (those of v = 0 are ignored)
+    and the masks are the domain-5 streams of mask_seed."""
+    s = _shape(name, len(lwe_key))
+    n, N, t, basebit = s["n"], s["N"], s["t"], s["basebit"]
+    base = 1 << basebit
+    rows = np.arange(N * t * base) if rows is None else np.asarray(rows, np.int64).ravel()
+    stored = np.asarray(stored, np.int32).reshape(len(rows), -1)
+    assert stored.shape[1] == (n + 1 if mask_seed is None else 1), "stored samples have the wrong shape"
+    lwe = np.asarray(lwe_key).astype(np.uint64)
+    tlwe = np.asarray(tlwe_key).astype(np.uint64)
+    out = np.zeros(len(rows), np.int32)
+    for lo in range(0, len(rows), chunk):
+        r = rows[lo:lo + chunk]
+        live = np.flatnonzero(r % base != 0)
+        if len(live) == 0:
+            continue
+        rl = r[live]
+        A = stored[lo + live, :n].view(np.uint32) if mask_seed is None else chacha20_words(mask_seed, DOMAIN_KS_MASK, rl, n)
+        dot = (A.astype(np.uint64) * lwe).sum(axis=-1)
+        ij = rl >> basebit
+        i, j = ij // t, ij % t
+        mess = (tlwe[i] * (rl % base).astype(np.uint64)) << (32 - (j + 1) * basebit).astype(np.uint64)
+        b = stored[lo + live, -1].view(np.uint32).astype(np.uint64)
+        out[lo + live] = ((b - dot - mess) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+    return out
+
+
+def audit(name, lwe_key, tlwe_key, bk=None, ksk=None, mask_seed=None, limits=None, bk_rows=None, ksk_rows=None):
+    """The report of rs_audit_keys_dev (mask_seed None; bk [R][2][N], ksk [R'][n+1]) or rs_audit_compressed_keys_dev (bk, ksk the
+    bodies) for the given rows (None: the whole half; a half that is None is skipped) -> a dict of the rs_key_audit fields plus
+    bk_noise int32 [R][N] and ksk_noise int32 [R'] (None for a skipped half). limits defaults to noise_limits(name)."""
+    bk_limit, ksk_limit = noise_limits(name) if limits is None else limits
+    s = _shape(name, len(lwe_key))
+    base = 1 << s["basebit"]
+    rep = dict(bk_max_abs=0, ksk_max_abs=0, bk_over=0, ksk_over=0, ksk_zero_bad=0, bk_words=0, ksk_words=0, bk_noise=None, ksk_noise=None)
+    mag = lambda e: np.abs(e.astype(np.int64))
+    if bk is not None:
+        e = bk_noise(name, lwe_key, tlwe_key, bk, bk_rows, mask_seed)
+        rep.update(bk_noise=e, bk_words=int(e.size), bk_max_abs=int(mag(e).max(initial=0)), bk_over=int((mag(e) > bk_limit).sum()))
+    if ksk is not None:
+        rows = np.arange(s["N"] * s["t"] * base) if ksk_rows is None else np.asarray(ksk_rows, np.int64).ravel()
+        e = ksk_noise(name, lwe_key, tlwe_key, ksk, rows, mask_seed)
+        live = rows % base != 0
+        rep.update(ksk_noise=e, ksk_words=int(live.sum()), ksk_max_abs=int(mag(e).max(initial=0)), ksk_over=int((mag(e) > ksk_limit).sum()))
+        if mask_seed is None:
+            rep["ksk_zero_bad"] = int(np.asarray(ksk, np.int32).reshape(len(rows), -1)[~live].any(axis=-1).sum())
+    return rep
