@@ -18,22 +18,24 @@ INCLUDE = os.path.join(ROOT, "include")
 HIP_LIB = os.path.join(HERE, "libredsec_hip.so")
 EMU_LIB = os.path.join(HERE, "librs_emulate.so")
 
-HIP_SOURCES = ["rs_bootstrap.hip", "rs_general.hip", "rs_kernels.hip", "rs_seeded.hip", "rs_audit.hip", "rs_api.cpp"]
-HIP_DEPS = HIP_SOURCES + ["rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_audit.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
-# Objects of the product library: (object name, source, extra flags). rs_bootstrap.hip is compiled three times (its RS_BS_PART
-# switch): part 1 -- the FFT / exact-NTT blind-rotation kernels and the split duo form -- with LLVM's post-register-allocation
-# scheduler off: its in-block reordering of the hand-laid-out LDS / FP64 sequences costs these kernels 1-3 % (same-box A/B,
-# profiles/r03/y_ab_compiler_scheduling_*.txt: default-128 +1.3 %, REDsec set +0.9 %, sign1024x1 image 12.36 -> 12.11 ms);
-# part 2 -- the split cooperative and split lock-step kernels -- keeps that pass (they lose 6 % / 0.7 % without it) and is
-# scheduled with the max-memory-clause strategy: the cooperative kernel streams the key from L2 by itself and gains 6.5 % from
-# clustered loads (196-neuron layer 4.33 -> 4.05 ms, split-mode sign1024x1 16.3 -> 15.95 ms; the lock-step kernel -0.5 % / +0.3 %);
-# the other files use the default pipeline (the (9, 3) keyswitch in rs_kernels.hip loses 12 % without the post-RA pass).
+HIP_SOURCES = ["rs_bootstrap.hip", "rs_bootstrap_split.hip", "rs_bootstrap_listed.hip", "rs_general.hip", "rs_kernels.hip", "rs_seeded.hip", "rs_audit.hip", "rs_api.cpp"]
+HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_audit.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
+# THE recipe of the product library: what every object is compiled with, then (object name, source under csrc/, extra flags).
+# build_tree() below and, through it, tools/build_variant.sh and the ISA tools (--print-flags) read it from here.
+HIP_COMMON_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 HIP_OBJECTS = [
-    ("rs_bootstrap_1", "rs_bootstrap.hip", ["-DRS_BS_PART=1", "-mllvm", "-enable-post-misched=0"]),
-    ("rs_bootstrap_2", "rs_bootstrap.hip", ["-DRS_BS_PART=2", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]),
-    # part 4 -- blind_rotate_coop8_listed_kernel (round 6) with part 1's flags, in an object of its own: instantiated inside part 1
-    # it changed the instructions of 15 other kernels there (tools/codeobj_digest.py), the measured BASELINE-config forms among them
-    ("rs_bootstrap_4", "rs_bootstrap.hip", ["-DRS_BS_PART=4", "-mllvm", "-enable-post-misched=0"]),
+    # the FFT / exact-NTT blind-rotation kernels and the split duo form, with LLVM's post-register-allocation scheduler off: its
+    # in-block reordering of the hand-laid-out LDS / FP64 sequences costs these kernels 1-3 % (same-box A/B,
+    # profiles/r03/y_ab_compiler_scheduling_*.txt: default-128 +1.3 %, REDsec set +0.9 %, sign1024x1 image 12.36 -> 12.11 ms)
+    ("rs_bootstrap", "rs_bootstrap.hip", ["-mllvm", "-enable-post-misched=0"]),
+    # the split cooperative and split lock-step kernels keep that pass (they lose 6 % / 0.7 % without it) and are scheduled with
+    # the max-memory-clause strategy: the cooperative kernel streams the key from L2 by itself and gains 6.5 % from clustered
+    # loads (196-neuron layer 4.33 -> 4.05 ms, split-mode sign1024x1 16.3 -> 15.95 ms; the lock-step kernel -0.5 % / +0.3 %)
+    ("rs_bootstrap_split", "rs_bootstrap_split.hip", ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]),
+    # blind_rotate_coop8_listed_kernel (round 6) with the flags of rs_bootstrap, in an object of its own: instantiated beside those
+    # kernels it changed the instructions of 15 of them (tools/codeobj_digest.py), the measured BASELINE-config forms among them
+    ("rs_bootstrap_listed", "rs_bootstrap_listed.hip", ["-mllvm", "-enable-post-misched=0"]),
+    # the other files use the default pipeline (the (9, 3) keyswitch in rs_kernels.hip loses 12 % without the post-RA pass)
     ("rs_general", "rs_general.hip", []),
     ("rs_kernels", "rs_kernels.hip", []),
     # seeded ciphertexts (seeded_lwe_kernel) in an object of their own: every kernel of rs_general keeps its instructions
@@ -108,11 +110,72 @@ def _publish(tmp, target, deps):
     os.replace(tmp + ".stamp", target + ".stamp")
 
 
+def _recipe(src_root):
+    """(common flags, HIP_OBJECTS) of the tree at `src_root`: this module's own for this tree, else read from THAT tree's
+    redsec_amd/build.py, so that a checkout of another commit is built the way that commit builds itself."""
+    path = os.path.join(src_root, "redsec_amd", "build.py")
+    if os.path.realpath(path) == os.path.realpath(__file__):
+        return HIP_COMMON_FLAGS, HIP_OBJECTS
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_redsec_build_recipe", path)
+    other = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(other)
+    return getattr(other, "HIP_COMMON_FLAGS", HIP_COMMON_FLAGS), other.HIP_OBJECTS   # older trees: the same flags, inside build_hip
+
+
+def object_flags(name, src_root=ROOT):
+    """The whole flag list one object of the recipe is compiled with (no input or output file)."""
+    common, objects = _recipe(src_root)
+    for obj, _, extra in objects:
+        if obj == name:
+            return common + ["-I" + os.path.join(src_root, "include"), "-I" + os.path.join(src_root, "redsec_amd", "csrc")] + extra
+    raise KeyError("no object %r in HIP_OBJECTS (%s)" % (name, ", ".join(o[0] for o in objects)))
+
+
+def build_tree(src_root, out, extra=(), per_object=None, verbose=False):
+    """Compile the HIP_OBJECTS of the tree at `src_root` by that tree's recipe and link them into `out`: one object per entry
+    (compiled side by side: the files carry different code-generation flags), then one link. `extra`: flags added to every
+    object; `per_object`: {object name: flags added to that object only} (A/B builds). Objects are written under a per-process
+    directory, so builds may run side by side."""
+    hipcc = find_hipcc()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found")
+    per_object = per_object or {}
+    _, objects = _recipe(src_root)
+    unknown = set(per_object) - {o[0] for o in objects}
+    if unknown:
+        raise KeyError("no object %s in HIP_OBJECTS (%s)" % (sorted(unknown), ", ".join(o[0] for o in objects)))
+    objdir = os.path.join(ROOT, "build", "obj.%d" % os.getpid())
+    os.makedirs(objdir, exist_ok=True)
+    jobs, objs = [], []
+    try:
+        for name, src, _ in objects:
+            obj = os.path.join(objdir, name + ".o")
+            cmd = [hipcc] + object_flags(name, src_root) + list(per_object.get(name, ())) + list(extra) + \
+                  ["-c", os.path.join(src_root, "redsec_amd", "csrc", src), "-o", obj]
+            if verbose:
+                print(" ".join(cmd))
+            jobs.append((cmd, subprocess.Popen(cmd)))
+            objs.append(obj)
+        for cmd, job in jobs:
+            if job.wait() != 0:
+                raise subprocess.CalledProcessError(job.returncode, cmd)
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    finally:
+        for _, job in jobs:
+            if job.poll() is None:
+                job.kill()
+        shutil.rmtree(objdir, ignore_errors=True)
+    return out
+
+
 def build_hip(force=False, verbose=False):
     if not force and not _stale(HIP_LIB, HIP_DEPS):
         return HIP_LIB
-    hipcc = find_hipcc()
-    if hipcc is None:
+    if find_hipcc() is None:
         if os.path.exists(HIP_LIB):
             return HIP_LIB  # prebuilt library shipped with the snapshot
         raise RuntimeError("hipcc not found and no prebuilt libredsec_hip.so present")
@@ -120,34 +183,9 @@ def build_hip(force=False, verbose=False):
     try:
         if not force and not _stale(HIP_LIB, HIP_DEPS):     # another process built it while this one waited for the lock
             return HIP_LIB
-        # One object per source (compiled side by side), then one link: the files carry different code-generation flags.
-        # Objects and the linked library are written under per-process names and renamed into place.
-        objdir = os.path.join(ROOT, "build", "obj.%d" % os.getpid())
-        os.makedirs(objdir, exist_ok=True)
-        common = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
-        jobs, objs = [], []
-        for name, src, extra in HIP_OBJECTS:
-            obj = os.path.join(objdir, name + ".o")
-            cmd = common + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
-            if verbose:
-                print(" ".join(cmd))
-            jobs.append((cmd, subprocess.Popen(cmd)))
-            objs.append(obj)
-        try:
-            for cmd, job in jobs:
-                if job.wait() != 0:
-                    raise subprocess.CalledProcessError(job.returncode, cmd)
-            tmp = HIP_LIB + ".tmp.%d" % os.getpid()
-            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", tmp]
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd)
-            _publish(tmp, HIP_LIB, HIP_DEPS)
-        finally:
-            for _, job in jobs:
-                if job.poll() is None:
-                    job.kill()
-            shutil.rmtree(objdir, ignore_errors=True)
+        tmp = HIP_LIB + ".tmp.%d" % os.getpid()             # linked under a per-process name and renamed into place
+        build_tree(ROOT, tmp, verbose=verbose)
+        _publish(tmp, HIP_LIB, HIP_DEPS)
         return HIP_LIB
     finally:
         lock.close()
@@ -209,6 +247,41 @@ def build_all(force=False, verbose=False):
     return build_hip(force, verbose), build_emulator(force, verbose), build_layers(force, verbose)
 
 
+def main(argv):
+    """python -m redsec_amd.build [--force]                 build everything in this tree
+       python -m redsec_amd.build --print-flags OBJECT      the flags one object of HIP_OBJECTS is compiled with (ISA tools)
+       python -m redsec_amd.build --variant NAME [--src ROOT] [--out PATH] [--object-flags OBJECT="FLAGS"]... [-- FLAGS...]
+           libredsec_hip.so of the tree at ROOT (default: this one), by THAT tree's recipe, into PATH (default:
+           variants/lib_NAME.so) for same-box A/B runs with REDSEC_HIP_LIB; FLAGS go to every object, --object-flags to one."""
+    import argparse
+    import shlex
+    extra = []
+    if "--" in argv:
+        k = argv.index("--")
+        argv, extra = argv[:k], argv[k + 1:]
+    ap = argparse.ArgumentParser(prog="python -m redsec_amd.build", description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--force", action="store_true")
+    ap.add_argument("--print-flags", metavar="OBJECT")
+    ap.add_argument("--variant", metavar="NAME")
+    ap.add_argument("--src", default=ROOT)
+    ap.add_argument("--out")
+    ap.add_argument("--object-flags", action="append", default=[], metavar="OBJECT=FLAGS")
+    a = ap.parse_args(argv)
+    src = os.path.abspath(a.src)
+    if a.print_flags:
+        print(" ".join(object_flags(a.print_flags, src)))
+    elif a.variant:
+        out = os.path.abspath(a.out or os.path.join(ROOT, "variants", "lib_%s.so" % a.variant))
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        per_object = {}
+        for item in a.object_flags:
+            name, _, flags = item.partition("=")
+            per_object.setdefault(name, []).extend(shlex.split(flags))
+        print(build_tree(src, out, extra, per_object, verbose=True))
+    else:
+        print(build_all(force=a.force, verbose=True))
+
+
 if __name__ == "__main__":
     import sys
-    print(build_all(force="--force" in sys.argv, verbose=True))
+    main(sys.argv[1:])

@@ -1,8 +1,5 @@
 // rs_bootstrap.hip -- the transform-based kernels of the gate bootstrap, written once over a
-// "transform policy":
-//   XfNtt<Cfg>  exact negacyclic NTT over a 51-bit prime carried in FP64 (rs_ntt.h)  -- guaranteed exact
-//   XfFft<Cfg>  folded 512-point complex FP64 FFT (rs_fft.h), TFHE's own arithmetic class -- 2.5x fewer
-//               FP64 ops; exact after rounding with overwhelming probability, with a run-time certificate
+// "transform policy" (rs_bootstrap.h: XfNtt<Cfg> exact NTT, XfFft<Cfg> FP64 FFT with a run-time certificate):
 //
 //   bk_transform_kernel       bootstrapping key -> transform domain (the bkFFT analogue; once per key)
 //   blind_rotate_kernel       gate pre-combination + modswitch + n CMUX steps + sample extract
@@ -16,276 +13,14 @@
 // and two inverse transforms update the accumulator. Waves never synchronise with each other after
 // the twiddle tables are staged.
 //
-// Compile-time switches of this file: RS_BS_PART (below: which launchers an object holds) and RS_DIAG (rs_diag.h: phase stamps
-// and the no-key timing probe of diagnostic builds). Every experiment of rounds 1-4 that was measured and not adopted has its
-// verdict in MEASUREMENTS.md and no code path here.
-#include <hip/hip_runtime.h>
-
-#include <cstdlib>
-#include <type_traits>
-
-#include "rs_fft.h"
-#include "rs_cohort.h"
-#include "rs_diag.h"
-#include "rs_kernels.h"
-#include "rs_lds_plan.h"
-#include "rs_ntt.h"
-
-// RS_BS_PART: redsec_amd/build.py compiles this file THREE times, because its kernels want different code-generation flags
-// (profiles/r03/y_ab_compiler_scheduling_*.txt). Bit 1 = every launcher except the one of bit 2 (built with LLVM's post-RA
-// scheduler off: the FFT / exact-NTT kernels and the split duo form gain 1-3 % from it); bit 2 = launch_blind_rotate_split_wg
-// with the split cooperative and split lock-step kernels (built with the default pipeline: they lose 6 % / 0.7 % without that
-// pass); bit 4 = launch_coop8_listed with blind_rotate_coop8_listed_kernel (round 6; part 1's flags; apart so that part 1's
-// device code stays what it was, see there). Kernels are templates, so each object holds only what its launchers name.
-// Default 7: one object with everything.
-#ifndef RS_BS_PART
-#define RS_BS_PART 7
-#endif
+// This unit holds the FFT / exact-NTT kernels and the split duo form, which are built with LLVM's post-RA scheduler off; the
+// split lock-step and cooperative kernels (rs_bootstrap_split.hip) and the listed coop8 kernel (rs_bootstrap_listed.hip) are
+// objects of their own -- redsec_amd/build.py (HIP_OBJECTS) gives the measured reasons. The one compile-time switch is RS_DIAG
+// (rs_diag.h: phase stamps and the no-key timing probe of diagnostic builds). Every experiment of rounds 1-4 that was measured
+// and not adopted has its verdict in MEASUREMENTS.md and no code path here.
+#include "rs_bootstrap.h"
 
 namespace rs {
-
-// Same-wave LDS hand-off: DS operations of one wavefront execute in order, so only the compiler
-// needs to be told not to move LDS accesses across this point.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void stage_tables(double* s_tw, const double* tw_g, int nthreads, int count) {
-  for (int i = threadIdx.x; i < count; i += nthreads) s_tw[i] = tw_g[i];
-  __syncthreads();
-}
-
-// -------------------------------------------------------------------------------------------------
-// Transform policies
-// -------------------------------------------------------------------------------------------------
-template <class C>
-struct XfNtt {
-  using Cfg = C;
-  static constexpr int kTableDoubles = kTwTotal;   // staged in LDS
-  static constexpr bool kCertificate = false;
-  static constexpr bool kSplitKeyLoads = false;   // whole key row prefetched across the transform
-  static constexpr bool kWorkgroupForm = false;
-  static constexpr bool kPreparedDigits = false;  // digits extracted from the raw rotated difference
-  struct State { const double* tw; };
-  __device__ static __forceinline__ void init(State& st, int, const double* tw_lds, const double*) { st.tw = tw_lds; }
-  using LatencyState = State;   // the cooperative kernel's twiddle source (XfFft keeps its per-lane twiddles in registers there)
-  __device__ static __forceinline__ void init_latency(LatencyState& st, int lane, const double* tw_lds, const double* tw_g) { init(st, lane, tw_lds, tw_g); }
-
-  __device__ static __forceinline__ void fwd_digits(int lane, double (&x)[kRegs], const int32_t (&d)[kRegs], int q, uint32_t offset,
-                                                    const State& st, double* buf, const Field& f) {
-    const double* tw = st.tw;
-    fwd_F1_digits<C>(lane, x, d, q, offset, tw, buf, f);
-    wave_lds_sync();
-    fwd_F2<C>(lane, x, tw, buf, f);
-    wave_lds_sync();
-    fwd_F3(lane, x, buf);
-    wave_lds_sync();
-    fwd_F4<C>(lane, x, tw, buf, f);
-    wave_lds_sync();
-  }
-  __device__ static __forceinline__ void fwd_generic(int lane, double (&x)[kRegs], const State& st, double* buf, const Field& f) {
-    const double* tw = st.tw;
-    fwd_F1<C>(lane, x, tw, buf, f);
-    wave_lds_sync();
-    fwd_F2<C>(lane, x, tw, buf, f);
-    wave_lds_sync();
-    fwd_F3(lane, x, buf);
-    wave_lds_sync();
-    fwd_F4<C>(lane, x, tw, buf, f);
-    wave_lds_sync();
-  }
-  // key values: scaled by 1/N and fully reduced; stored as pairs (positions 16 lane + 2v, +1)
-  __device__ static __forceinline__ void key_store(double2* dst, int lane, const double (&x)[kRegs], double scale, const Field& f) {
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-      const double a = f_reduce(f_mulmod(f_reduce(x[2 * v], f), scale, f), f);
-      const double b = f_reduce(f_mulmod(f_reduce(x[2 * v + 1], f), scale, f), f);
-      dst[v * 64 + lane] = make_double2(a, b);
-    }
-  }
-  // multiply-accumulate against key entries v0 .. v0+3 of both columns
-  __device__ static __forceinline__ void mac(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs],
-                                             const double2 (&w0)[4], const double2 (&w1)[4], int v0, const Field& f) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = v0 + k;
-      s0[2 * v] += f_mulmod(x[2 * v], w0[k].x, f);
-      s0[2 * v + 1] += f_mulmod(x[2 * v + 1], w0[k].y, f);
-      s1[2 * v] += f_mulmod(x[2 * v], w1[k].x, f);
-      s1[2 * v + 1] += f_mulmod(x[2 * v + 1], w1[k].y, f);
-    }
-  }
-  __device__ static __forceinline__ void mac8(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs],
-                                              const double2 (&w0)[8], const double2 (&w1)[8], const Field& f) {
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-      s0[2 * v] += f_mulmod(x[2 * v], w0[v].x, f);
-      s0[2 * v + 1] += f_mulmod(x[2 * v + 1], w0[v].y, f);
-      s1[2 * v] += f_mulmod(x[2 * v], w1[v].x, f);
-      s1[2 * v + 1] += f_mulmod(x[2 * v + 1], w1[v].y, f);
-    }
-  }
-  __device__ static __forceinline__ void mid(double (&s0)[kRegs], double (&s1)[kRegs], const Field& f) {
-    if (C::MID_REDUCE) {
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) { s0[u] = f_reduce(s0[u], f); s1[u] = f_reduce(s1[u], f); }
-    }
-  }
-  __device__ static __forceinline__ double partial(double v, const Field& f) { return f_reduce(v, f); }
-  __device__ static __forceinline__ void inverse(int lane, double (&x)[kRegs], const State& st, double* buf, const Field& f) {
-    const double* twi = st.tw + kN;
-    inv_I1<C>(lane, x, twi, buf, f);
-    wave_lds_sync();
-    inv_I2<C>(lane, x, twi, buf, f);
-    wave_lds_sync();
-    inv_I3(lane, x, buf);
-    wave_lds_sync();
-    inv_I4<C>(lane, x, twi, buf, f);
-    wave_lds_sync();
-  }
-  __device__ static __forceinline__ void inverse2(int lane, double (&xa)[kRegs], double (&xb)[kRegs], const State& st, double* buf, const Field& f) {
-    inverse(lane, xa, st, buf, f);
-    inverse(lane, xb, st, buf, f);
-  }
-  __device__ static __forceinline__ int32_t to_torus(double v, double&) { return f_to_torus32(v); }
-};
-
-template <class C>
-struct XfFft {
-  using Cfg = C;
-  static constexpr int kTableDoubles = kFftTwDoubles;   // stage-transposed complex table staged in LDS (8 KB)
-  static constexpr bool kCertificate = true;
-  static constexpr bool kSplitKeyLoads = true;    // second half of the key row fetched after the transform
-  static constexpr bool kWorkgroupForm = true;    // blind_rotate_wg_kernel available
-  static constexpr bool kPreparedDigits = true;   // d[] = gadget_prepare(rotated difference): one v_bfe_i32 per digit
-  // Twiddles are read from the LDS table at every use: keeping the 21 complex values of a lane in
-  // registers (FftTw) spilled 250 B/lane to scratch at the 256-VGPR budget and cost 40 % (scratch
-  // reloads share vmcnt with the in-flight key-row loads).
-  using State = FftTwTable;
-  __device__ static __forceinline__ void init(State& st, int lane, const double* tw_lds, const double*) { st.tw = tw_lds; st.lane = lane; }
-
-  // One wave per SIMD in the cooperative kernel (512 registers): all eight per-lane twiddles stay in registers
-  using LatencyState = FftTwKept<3>;
-  __device__ static __forceinline__ void init_latency(LatencyState& st, int lane, const double* tw_lds, const double* tw_g) {
-    State t;
-    init(t, lane, tw_lds, tw_g);
-    fft_kept_load(st, t);
-  }
-  template <class TWS>
-  __device__ static __forceinline__ void fwd_generic(int lane, double (&x)[kRegs], const TWS& st, double* buf, const Field&) {
-    ffwd_F1(lane, x, st, buf);
-    wave_lds_sync();
-    ffwd_F2(lane, x, st, buf);
-    wave_lds_sync();
-    ffwd_F3(lane, x, buf);
-    wave_lds_sync();
-    ffwd_F4(lane, x, st, buf);
-    wave_lds_sync();
-  }
-  template <class TWS>
-  __device__ static __forceinline__ void fwd_digits(int lane, double (&x)[kRegs], const int32_t (&d)[kRegs], int q, uint32_t offset,
-                                                    const TWS& st, double* buf, const Field& f) {
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) x[r] = (double)gadget_digit_prepared<C>(d[r], q);
-    fwd_generic(lane, x, st, buf, f);
-  }
-  // key values scaled by 1/M (exact power of two); stored as (re, im) of position 8 lane + v
-  __device__ static __forceinline__ void key_store(double2* dst, int lane, const double (&x)[kRegs], double, const Field&) {
-#pragma unroll
-    for (int v = 0; v < 8; ++v) dst[v * 64 + lane] = make_double2(x[v] * (1.0 / kM), x[v + 8] * (1.0 / kM));
-  }
-  __device__ static __forceinline__ void mac(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs],
-                                             const double2 (&w0)[4], const double2 (&w1)[4], int v0, const Field&) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = v0 + k;
-      fft_cmac(s0[v], s0[v + 8], x[v], x[v + 8], w0[k].x, w0[k].y);
-      fft_cmac(s1[v], s1[v + 8], x[v], x[v + 8], w1[k].x, w1[k].y);
-    }
-  }
-  __device__ static __forceinline__ void mac8(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs],
-                                              const double2 (&w0)[8], const double2 (&w1)[8], const Field&) {
-#pragma unroll
-    for (int v = 0; v < 8; ++v) {
-      fft_cmac(s0[v], s0[v + 8], x[v], x[v + 8], w0[v].x, w0[v].y);
-      fft_cmac(s1[v], s1[v + 8], x[v], x[v + 8], w1[v].x, w1[v].y);
-    }
-  }
-  __device__ static __forceinline__ void mid(double (&)[kRegs], double (&)[kRegs], const Field&) {}
-  __device__ static __forceinline__ double partial(double v, const Field&) { return v; }
-  template <class TWS>
-  __device__ static __forceinline__ void inverse(int lane, double (&x)[kRegs], const TWS& st, double* buf, const Field&) {
-    finv_I1(lane, x, st, buf);
-    wave_lds_sync();
-    finv_I2(lane, x, st, buf);
-    wave_lds_sync();
-    finv_I3(lane, x, buf);
-    wave_lds_sync();
-    finv_I4(lane, x, st, buf);
-    wave_lds_sync();
-  }
-  // both accumulator columns at once: the two inverse transforms interleaved phase by phase
-  __device__ static __forceinline__ void inverse2(int lane, double (&xa)[kRegs], double (&xb)[kRegs], const State& st, double* buf, const Field&) {
-    finv_pair<false>(lane, xa, xb, st, buf, [] { wave_lds_sync(); });
-  }
-  __device__ static __forceinline__ int32_t to_torus(double v, double& dev) { return fft_round_torus32(v, dev); }
-
-  // workgroup kernel: planar exchanges through a half-size per-wave buffer
-  static constexpr int kWgBufDoubles = kPlaneDoubles;
-  __device__ static __forceinline__ void inverse_wg(int lane, double (&x)[kRegs], const State& st, double* buf, const Field&) {
-    finv_planar(lane, x, st, buf, [] { wave_lds_sync(); });
-  }
-  __device__ static __forceinline__ void digits(double (&x)[kRegs], const int32_t (&d)[kRegs], int q) {
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) x[r] = (double)gadget_digit_prepared<C>(d[r], q);
-  }
-  // the lock-step workgroup kernel's pairs: per-lane twiddles from registers (FftTwKept) or the LDS tables (State)
-  template <class TWS>
-  __device__ static __forceinline__ void fwd_pair_wg(int lane, double (&xa)[kRegs], double (&xb)[kRegs], const TWS& st, double* buf) {
-    ffwd_pair<true>(lane, xa, xb, st, buf, [] { wave_lds_sync(); });
-  }
-  template <class TWS>
-  __device__ static __forceinline__ void inverse_pair_wg(int lane, double (&xa)[kRegs], double (&xb)[kRegs], const TWS& st, double* buf) {
-    finv_pair<true>(lane, xa, xb, st, buf, [] { wave_lds_sync(); });
-  }
-  static constexpr int kWgTableDoubles = kFftTwDoubles;
-};
-
-// largest rounding distance of the wave -> device flag (positive doubles order like their bit patterns)
-__device__ __forceinline__ void publish_certificate(double dev, unsigned long long* flag, int lane) {
-  if (!flag) return;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(dev, off, 64);
-    dev = o > dev ? o : dev;
-  }
-  if (lane == 0) atomicMax(flag, (unsigned long long)__double_as_longlong(dev));
-}
-
-// Initial accumulator body: (test polynomial * X^rot)_j. Constant test vector (tfhe_bootstrap_woKS_FFT) or, in
-// the programmable form, the ciphertext's own polynomial lut[ct % lut_count] (tfhe_blindRotateAndExtract_FFT).
-__device__ __forceinline__ int32_t test_vector(const BlindRotateArgs& a, long ct, int j, int rot) {
-  if (!a.lut) return rotated_const(a.mu, j, rot);
-  const int32_t* v = a.lut + (size_t)((ct + a.lut_first) % a.lut_count) * kN;
-  const int aa = rot & (kN - 1), nb = (rot >> 10) & 1;
-  const uint32_t x = (uint32_t)v[(j - aa) & (kN - 1)];
-  return (int32_t)((((j < aa) ? 1 : 0) ^ nb) ? 0u - x : x);
-}
-
-// Exact recomputation gate (see BlindRotateArgs::gate_flag). Uniform over the grid: every thread reads the
-// same word, so whole workgroups leave before their first barrier. Returns true when the launch has nothing to do.
-__device__ __forceinline__ bool recompute_not_needed(const BlindRotateArgs& a) {
-  if (!a.gate_flag) return false;
-  const unsigned long long bits = *(const volatile unsigned long long*)a.gate_flag;   // positive doubles order like their bit patterns
-  const bool needed = bits >= a.gate_limit_bits;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (a.running_flag) atomicMax(a.running_flag, bits);
-    if (needed && a.fallback_count) atomicAdd(a.fallback_count, 1ull);
-  }
-  return !needed;
-}
 
 // -------------------------------------------------------------------------------------------------
 // Key transform: one wavefront per key polynomial. Output layout per polynomial: [v 0..7][lane][2]
@@ -454,101 +189,6 @@ __global__ __launch_bounds__(64 * WPB) void blind_rotate_kernel(BlindRotateArgs 
 // (bara == 0) only skip the arithmetic. Groups are assigned round-robin: all groups take the same
 // number of steps, so there is nothing to balance dynamically.
 // -------------------------------------------------------------------------------------------------
-// Direct global -> LDS loads, 16 bytes per lane = 1 KB per wave-instruction, NCHUNK consecutive KB:
-// global address = wave-uniform base (SGPR pair) + lane_off (one VGPR, lane * 16) + k KB; LDS address =
-// M0 + k KB + lane * 16 (the instruction offset advances both sides). Written as asm because (a) hipcc
-// puts a vmcnt(0) in front of the next LDS read whenever it knows of a pending LDS-DMA, which would
-// serialise the prefetch -- the kernels' own `s_waitcnt vmcnt(0)` + barrier orders the data instead;
-// (b) with per-lane 64-bit source pointers the compiler spilled around the issue point, and every
-// scratch reload there waits on vmcnt, i.e. on the key rows that were just requested.
-template <int NCHUNK>
-__device__ __forceinline__ void glds_chunks(const double* gsrc_wave_base, unsigned lane_off, const double* lds_wave_base) {
-  static_assert(NCHUNK >= 1 && NCHUNK <= 4, "instruction offsets are 13-bit signed");
-  const unsigned lds_dst = (unsigned)__builtin_amdgcn_readfirstlane(
-      (int)(unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)lds_wave_base);
-  const unsigned long long base = (unsigned long long)(uintptr_t)gsrc_wave_base;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32));
-  const unsigned long long sbase = ((unsigned long long)hi << 32) | lo;
-  unsigned keep;
-  if constexpr (NCHUNK == 1) {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(sbase), "s"(lds_dst) : "memory");
-  } else if constexpr (NCHUNK == 2) {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(sbase), "s"(lds_dst) : "memory");
-  } else {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(sbase), "s"(lds_dst) : "memory");
-    static_assert(NCHUNK == 4, "1, 2 or 4 chunks");
-  }
-}
-
-// The same with the LDS side given as a byte address (a workgroup-uniform unsigned: no generic-pointer cast, whose null check
-// costs three scalar instructions per call) and the global side as a wave-uniform pointer the caller keeps running.
-template <int NCHUNK>
-__device__ __forceinline__ void glds_chunks_at(const double* gsrc_wave_base, unsigned lane_off, unsigned lds_byte_addr) {
-  static_assert(NCHUNK == 1 || NCHUNK == 2 || NCHUNK == 4, "1, 2 or 4 chunks of 1 KB per wave");
-  unsigned keep;
-  if constexpr (NCHUNK == 1) {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(gsrc_wave_base), "s"(lds_byte_addr) : "memory");
-  } else if constexpr (NCHUNK == 2) {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(gsrc_wave_base), "s"(lds_byte_addr) : "memory");
-  } else {
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(gsrc_wave_base), "s"(lds_byte_addr) : "memory");
-  }
-}
-
-// Pointwise multiply-accumulate of a transform PAIR against its two key rows in LDS (FFT policies), as one
-// stream: 8 steps of two complex positions (4 ds_read_b128: both columns), the reads of step k+1 issued
-// before the FMAs of step k. Read in four blocks of 8 with the FMAs after each block (mac_row), every
-// block exposed a fresh LDS latency because the FMAs of a block drain its reads (in-order return).
-#define RS_MAC_FENCE() __builtin_amdgcn_sched_barrier(0)
-// col0 / col1: offsets (in double2) of the column multiplied into s0 / s1 within a key row -- 0 and kN / 2 for (column 0, column 1);
-// the duo kernel passes them swapped for its odd waves, so that s0 is always the column the wave itself inverts
-__device__ __forceinline__ void mac_pair_stream(double (&s0)[kRegs], double (&s1)[kRegs], const double (&xa)[kRegs], const double (&xb)[kRegs],
-                                                const double* keyA, const double* keyB, int lane, int col0 = 0, int col1 = kN / 2) {
-  const double2* ka = reinterpret_cast<const double2*>(keyA);
-  const double2* kb = reinterpret_cast<const double2*>(keyB);
-  double2 u[2][4];
-  auto issue = [&](int step, double2 (&w)[4]) {
-    const double2* k0 = (step < 4 ? ka : kb) + col0;
-    const double2* k1 = (step < 4 ? ka : kb) + col1;
-    const int v = 2 * (step & 3);
-    w[0] = k0[v * 64 + lane]; w[1] = k0[(v + 1) * 64 + lane];
-    w[2] = k1[v * 64 + lane]; w[3] = k1[(v + 1) * 64 + lane];
-  };
-  auto fma = [&](int step, const double2 (&w)[4]) {
-    const double (&x)[kRegs] = step < 4 ? xa : xb;
-    const int v = 2 * (step & 3);
-    fft_cmac(s0[v], s0[v + 8], x[v], x[v + 8], w[0].x, w[0].y);
-    fft_cmac(s0[v + 1], s0[v + 9], x[v + 1], x[v + 9], w[1].x, w[1].y);
-    fft_cmac(s1[v], s1[v + 8], x[v], x[v + 8], w[2].x, w[2].y);
-    fft_cmac(s1[v + 1], s1[v + 9], x[v + 1], x[v + 9], w[3].x, w[3].y);
-  };
-  issue(0, u[0]);
-#pragma unroll
-  for (int step = 0; step < 8; ++step) {
-    if (step + 1 < 8) issue(step + 1, u[(step + 1) & 1]);
-    RS_MAC_FENCE();
-    fma(step, u[step & 1]);
-    RS_MAC_FENCE();
-  }
-}
-
-#if RS_BS_PART & RS_DIAG_STAMP_PART   // diagnostic builds only (rs_diag.h): the phase sums, [workgroup < 256][wave][phase]
-__device__ unsigned long long g_rs_stamps[256 * 8 * diag::kStampPhases];
-#endif
-
 template <class Xf, int WPB>
 __global__ __launch_bounds__(64 * WPB) void blind_rotate_wg_kernel(BlindRotateArgs a) {
   using C = typename Xf::Cfg;
@@ -735,220 +375,6 @@ __global__ __launch_bounds__(64 * WPB) void blind_rotate_wg_kernel(BlindRotateAr
   RS_STAMP_FLUSH(wave);
   if (wave == 0) cohort_leave<BlindRotateArgs>(steps_done);
   if (Xf::kCertificate) publish_certificate(dev, a.dev_flag, lane);
-}
-
-// -------------------------------------------------------------------------------------------------
-// Blind rotation, lock-step workgroup form on the SPLIT key (RS_MODE_FFT_SPLIT at throughput batch sizes, N = 1024).
-// Same structure as blind_rotate_wg_kernel -- 8 waves walk 8 ciphertexts in lock step and share the key through LDS --
-// but every key row comes as two 16 KB half-rows (the low and the high 16-bit half of the key, rs_general.h), each
-// multiplied into its own pair of column sums: four inverse transforms per CMUX step instead of two, and the result
-// acc += round(lo) + (round(hi) << 16) is exact by the a-priori bound of rs_general.h (no certificate).
-// Four accumulators leave registers for ONE digit transform in flight (the unsplit kernel pairs them); the inverse
-// transforms still run as software-pipelined pairs. LDS: 3 ring slots of 16 KB (the accumulators and exchange planes
-// of 8 ciphertexts leave room for no more), so `bara` lives in a 64-step window refilled from global memory.
-// Half-row h sits in slot h mod 3 and is requested two half-rows ahead: the barrier that publishes h also says every
-// wave has finished h - 1, whose slot then takes h + 2.
-// -------------------------------------------------------------------------------------------------
-// s0 += x * (column at k0), s1 += x * (column at k1): the two columns of one key half-row
-__device__ __forceinline__ void mac_half_stream_cols(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs], const double2* k0, const double2* k1, int lane) {
-  double2 u[2][4];
-  auto issue = [&](int step, double2 (&w)[4]) {
-    const int v = 2 * step;
-    w[0] = k0[v * 64 + lane]; w[1] = k0[(v + 1) * 64 + lane];
-    w[2] = k1[v * 64 + lane]; w[3] = k1[(v + 1) * 64 + lane];
-  };
-  auto fma = [&](int step, const double2 (&w)[4]) {
-    const int v = 2 * step;
-    fft_cmac(s0[v], s0[v + 8], x[v], x[v + 8], w[0].x, w[0].y);
-    fft_cmac(s0[v + 1], s0[v + 9], x[v + 1], x[v + 9], w[1].x, w[1].y);
-    fft_cmac(s1[v], s1[v + 8], x[v], x[v + 8], w[2].x, w[2].y);
-    fft_cmac(s1[v + 1], s1[v + 9], x[v + 1], x[v + 9], w[3].x, w[3].y);
-  };
-  issue(0, u[0]);
-#pragma unroll
-  for (int step = 0; step < 4; ++step) {
-    if (step + 1 < 4) issue(step + 1, u[(step + 1) & 1]);
-    RS_MAC_FENCE();
-    fma(step, u[step & 1]);
-    RS_MAC_FENCE();
-  }
-}
-
-__device__ __forceinline__ void mac_half_stream(double (&s0)[kRegs], double (&s1)[kRegs], const double (&x)[kRegs], const double* key, int lane) {
-  const double2* k0 = reinterpret_cast<const double2*>(key);
-  mac_half_stream_cols(s0, s1, x, k0, k0 + kN / 2, lane);
-}
-
-template <class C, int WPB>
-__global__ __launch_bounds__(64 * WPB) void blind_rotate_wgs_kernel(BlindRotateArgs a) {
-  using Xf = XfFft<C>;
-  static_assert(WPB == 8 || WPB == 4, "a 16 KB half-row is fetched as 16 / WPB one-KB chunks per wave");
-  constexpr int kChunks = 16 / WPB;
-  constexpr int KPL = 2 * C::L;
-  constexpr int kSlotDoubles = 2 * kN;   // one key half-row: 2 columns x N doubles = 16 KB
-  constexpr int kWin = 64;
-  __shared__ double s_tw[Xf::kTableDoubles + 1];
-  __shared__ __attribute__((aligned(16))) double s_buf[WPB][Xf::kWgBufDoubles];
-  __shared__ int32_t s_acc[WPB][2][kN];
-  __shared__ __attribute__((aligned(16))) double s_key[3][kSlotDoubles];
-  __shared__ uint16_t s_bara[WPB][kWin];
-  __shared__ int s_mail[kCohortSlots];   // XCD cohorts: the progress row requested a step ago (wave 0 only; rs_cohort.h)
-  stage_tables(s_tw, a.tw, 64 * WPB, Xf::kTableDoubles);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  double* buf = s_buf[wave];
-  int32_t* acc0 = s_acc[wave][0];
-  int32_t* acc1 = s_acc[wave][1];
-  typename Xf::State tw;
-  Xf::init(tw, lane, s_tw, a.tw);
-  FftTwKept<9> tw_kept;
-  fft_kept_load(tw_kept, tw);
-  const int n = a.n;
-  const long n_groups = (a.B + WPB - 1) / WPB;
-  const int total_half = n * KPL * 2;   // half-rows of one blind rotation (n <= 1024 steps x 4 l: far inside an int; scalar compares)
-  const unsigned lane_off = (unsigned)lane * 16u;
-  auto sync_w = [] { wave_lds_sync(); };
-  RS_WGS_STAMP_DECL;   // -DRS_DIAG=2 (tools/stamp_profile.py --split): 0 step prologue + rotated differences, 1 digits + forward transform,
-                       // 2 key wait + barrier (low half), 3 multiply-accumulate low, 4 key wait + barrier (high half), 5 multiply-accumulate high,
-                       // 6 two inverse pairs + update, 7 group prologue / extract
-  int steps_done = 0;   // CMUX steps of the groups this workgroup has finished (XCD cohorts, rs_cohort.h)
-
-  for (long group = blockIdx.x; group < n_groups; group += gridDim.x, steps_done += n) {
-    const long ct = group * WPB + wave;
-    const bool active = ct < a.B;
-    const int32_t* row0 = a.in0 + (active ? ct : 0) * a.W;
-    const int32_t* row1 = a.in1 ? a.in1 + (active ? ct : 0) * a.W : nullptr;
-    auto word = [&](int i) -> int32_t {
-      uint32_t v = (uint32_t)a.c0 * (uint32_t)row0[i];
-      if (row1) v += (uint32_t)a.c1 * (uint32_t)row1[i];
-      return (int32_t)v;
-    };
-    auto fill_window = [&](int i0) {   // bara of steps [i0, i0 + 64): only this wave reads its row
-      const int i = i0 + lane;
-      s_bara[wave][lane] = (active && i < n) ? (uint16_t)modswitch_2N(word(i)) : (uint16_t)0;
-    };
-    if (active) {
-      const int32_t barb = modswitch_2N((int32_t)((uint32_t)word(n) + (uint32_t)a.bconst));
-      const int rot = 2 * kN - barb;  // in (0, 2N]
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) {
-        const int j = lane + 64 * r;
-        acc0[j] = 0;
-        acc1[j] = test_vector(a, ct, j, rot);
-      }
-    }
-    fill_window(0);
-    // every wave has left the previous group's last multiply-accumulate before the ring is refilled
-    __syncthreads();
-    int h_issue = 0;         // next half-row to request
-    int slot_issue = 0;      // its slot, h_issue mod 3
-    const double* src_next = a.bk_x + (size_t)(wave * kChunks) * 128;   // this wave's share of the next half-row
-    const unsigned key_lds = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)&s_key[0][0]) +
-                             (unsigned)(wave * kChunks) * 1024u;
-    auto issue_next = [&]() {
-      if (h_issue < total_half) {
-        // half-rows are requested in storage order: a running pointer and the slot's byte address, seven scalar instructions
-        // instead of the twenty-two of the general form (a 64-bit index compare, a shift-and-add pair, a pointer cast)
-        glds_chunks_at<kChunks>(src_next, lane_off, key_lds + (unsigned)slot_issue * (unsigned)(kSlotDoubles * sizeof(double)));
-        src_next += kSlotDoubles;
-        if constexpr (diag::kNoKeyProbe) {   // diagnostic builds: every step reads the half-rows of step 0 (they stay in the L2s)
-          if ((h_issue + 1) % (2 * KPL) == 0) src_next -= (size_t)(2 * KPL) * kSlotDoubles;
-        }
-        ++h_issue;
-        slot_issue = slot_issue == 2 ? 0 : slot_issue + 1;
-      }
-    };
-    issue_next();
-    issue_next();
-    int h = 0;               // half-row consumed next
-    int slot = 0;
-    // publishes half-row h (every wave first waits for its own share: at most the next half-row's two loads may still
-    // be in flight) and frees the slot of h - 1 for h + 2
-    // (a bare s_barrier behind explicit counts: __syncthreads() would drain every outstanding load, i.e. also the
-    // half-row requested one barrier ago, and with it half of the prefetch distance)
-    auto publish = [&]() {
-      if (h + 1 < total_half) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(kChunks) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      issue_next();
-    };
-    auto consumed = [&]() { ++h; slot = slot == 2 ? 0 : slot + 1; };
-
-    RS_WGS_STAMP(7);
-    for (int i = 0; i < n; ++i) {
-      if ((i & (kWin - 1)) == 0 && i > 0) { wave_lds_sync(); fill_window(i); }
-      if (wave == 0) cohort_step<BlindRotateArgs>(steps_done + i, s_mail);
-      wave_lds_sync();
-      const int32_t bara = __builtin_amdgcn_readfirstlane((int)s_bara[wave][i & (kWin - 1)]);
-      const bool work = bara != 0;   // tfhe_blindRotate_FFT skips the identity CMUX (the barriers still run)
-      double sl0[kRegs], sl1[kRegs], sh0[kRegs], sh1[kRegs];
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) { sl0[u] = 0.0; sl1[u] = 0.0; sh0[u] = 0.0; sh1[u] = 0.0; }
-      int32_t d[kRegs];
-      auto load_d = [&](auto comp_c) {
-        const int32_t* accc = decltype(comp_c)::value ? acc1 : acc0;
-#pragma unroll
-        for (int r = 0; r < kRegs; ++r) d[r] = gadget_prepare<C>(rotated_diff(accc, lane + 64 * r, bara));
-      };
-      auto row = [&](int q) {
-        double x[kRegs];
-        if (work) {
-          Xf::digits(x, d, q);
-          ffwd_planar(lane, x, tw_kept, buf, sync_w);
-        }
-        RS_WGS_STAMP(1);
-        publish();
-        RS_WGS_STAMP(2);
-        if (work) mac_half_stream(sl0, sl1, x, s_key[slot], lane);
-        consumed();
-        RS_WGS_STAMP(3);
-        publish();
-        RS_WGS_STAMP(4);
-        if (work) mac_half_stream(sh0, sh1, x, s_key[slot], lane);
-        consumed();
-        RS_WGS_STAMP(5);
-      };
-      // (the forward transforms stay single: run as software-pipelined pairs -- two transforms beside the four 32-register column
-      // sums -- the kernel does not fit 256 registers: 1,040 bytes of scratch per lane, compiled in round 4 and dropped)
-      if (work) load_d(std::false_type{});
-      RS_WGS_STAMP(0);
-#pragma unroll 1
-      for (int q = 0; q < C::L; ++q) row(q);
-      if (work) load_d(std::true_type{});
-      RS_WGS_STAMP(0);
-#pragma unroll 1
-      for (int q = 0; q < C::L; ++q) row(q);
-
-      if (work) {
-        Xf::inverse_pair_wg(lane, sl0, sl1, tw, buf);
-        uint32_t lo0[kRegs], lo1[kRegs];
-#pragma unroll
-        for (int r = 0; r < kRegs; ++r) { lo0[r] = (uint32_t)f_to_torus32(sl0[r]); lo1[r] = (uint32_t)f_to_torus32(sl1[r]); }
-        Xf::inverse_pair_wg(lane, sh0, sh1, tw, buf);
-#pragma unroll
-        for (int r = 0; r < kRegs; ++r) {
-          const int j = lane + 64 * r;
-          acc0[j] = (int32_t)((uint32_t)acc0[j] + lo0[r] + ((uint32_t)f_to_torus32(sh0[r]) << 16));
-          acc1[j] = (int32_t)((uint32_t)acc1[j] + lo1[r] + ((uint32_t)f_to_torus32(sh1[r]) << 16));
-        }
-        wave_lds_sync();
-      }
-      RS_WGS_STAMP(6);
-    }
-
-    if (active) {
-      // tLweExtractLweSampleIndex(index 0): a'[0] = acc_a[0], a'[j] = -acc_a[N-j], b' = acc_b[0]
-      int32_t* out = a.u_out + ct * (kN + 1);
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) {
-        const int j = lane + 64 * r;
-        out[j] = (j == 0) ? acc0[0] : (int32_t)(0u - (uint32_t)acc0[kN - j]);
-      }
-      if (lane == 0) out[kN] = acc1[0];
-    }
-  }
-  RS_WGS_STAMP(7);
-  RS_WGS_STAMP_FLUSH(wave);
-  if (wave == 0) cohort_leave<BlindRotateArgs>(steps_done);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1141,163 +567,6 @@ __global__ __launch_bounds__(512) void blind_rotate_duos_kernel(BlindRotateArgs 
   }
 }
 
-// -------------------------------------------------------------------------------------------------
-// Cooperative blind rotation on the SPLIT key (RS_MODE_FFT_SPLIT at latency batch sizes, B <= 2 x #CUs, N = 1024): G waves
-// share ONE ciphertext as in blind_rotate_coop_kernel. Wave g transforms the digit rows [g R, (g+1) R) and multiplies each
-// into FOUR partial sums (low / high key half x two columns; sum index = 2 half + column); every sum has one owner wave
-// that keeps its own partial in registers, adds the other waves' partials from LDS and runs the inverse transform:
-//   G = 4: wave s owns sum s; the rounded low and high results of a column meet in the accumulator by LDS integer
-//          atomics (exact, order-independent);
-//   G = 2: wave w owns both halves of column w -- its two inverse transforms run as a software-pipelined pair.
-// Key half-rows stream from L2 into registers in four chunks per row (the first one requested across the transform).
-// -------------------------------------------------------------------------------------------------
-template <class C, int G>
-__global__ __launch_bounds__(64 * G) void blind_rotate_coops_kernel(BlindRotateArgs a) {
-  using Xf = XfFft<C>;
-  constexpr int KPL = 2 * C::L;
-  constexpr int R = KPL / G;
-  static_assert((G == 2 || G == 4) && KPL % G == 0, "waves split the digit rows evenly within a component");
-  constexpr int OWN = 4 / G;                  // sums per owner wave
-  __shared__ double s_tw[Xf::kTableDoubles + 1];
-  __shared__ __attribute__((aligned(16))) double s_buf[G][kBufDoubles];
-  __shared__ double s_part[G][4 - OWN][kN];   // the sums a wave does NOT own (G = 4: 96 KB, G = 2: 32 KB)
-  __shared__ int32_t s_acc[2][kN];
-  stage_tables(s_tw, a.tw, 64 * G, Xf::kTableDoubles);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const long ct = blockIdx.x;
-  const Field f = a.f;
-  double* buf = s_buf[wave];
-  typename Xf::State tw;
-  Xf::init(tw, lane, s_tw, a.tw);
-  const int32_t* row0 = a.in0 + ct * a.W;
-  const int32_t* row1 = a.in1 ? a.in1 + ct * a.W : nullptr;
-  const int n = a.n;
-  const int comp = wave / (G / 2);
-  const int row_begin = wave * R;
-  auto word = [&](int i) -> int32_t {
-    uint32_t v = (uint32_t)a.c0 * (uint32_t)row0[i];
-    if (row1) v += (uint32_t)a.c1 * (uint32_t)row1[i];
-    return (int32_t)v;
-  };
-  auto owner = [](int sum) { return coops_owner<G>(sum); };              // placement: rs_lds_plan.h (checked on the host)
-  auto slot = [](int sum, int g) { return coops_slot<G>(sum, g); };      // index among the sums wave g does not own
-  if (wave < 2) {
-    const int32_t barb = modswitch_2N((int32_t)((uint32_t)word(n) + (uint32_t)a.bconst));
-    const int rot = 2 * kN - barb;
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) {
-      const int j = lane + 64 * r;
-      s_acc[wave][j] = wave == 0 ? 0 : test_vector(a, ct, j, rot);
-    }
-  }
-  __syncthreads();
-  for (int i = 0; i < n; ++i) {
-    const int32_t bara = __builtin_amdgcn_readfirstlane(modswitch_2N(word(i)));
-    if (bara == 0) continue;   // uniform over the workgroup
-    double s[4][kRegs];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) s[k][u] = 0.0;
-    int32_t d[kRegs];
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) d[r] = gadget_prepare<C>(rotated_diff(s_acc[comp], lane + 64 * r, bara));
-#pragma unroll 1
-    for (int rr = 0; rr < R; ++rr) {
-      const int row = row_begin + (int)((rr + blockIdx.x) % R);
-      const int q = row - comp * C::L;
-      // half-row (row, half) = [column 0: N doubles][column 1: N doubles], pairs (re, im) of position 8 lane + v at [v][lane]
-      const double2* lo0 = reinterpret_cast<const double2*>(a.bk_x + ((size_t)i * KPL + row) * 4 * kN);
-      const double2* lo1 = lo0 + kN / 2;
-      const double2* hi0 = lo0 + kN;
-      const double2* hi1 = hi0 + kN / 2;
-      auto load4 = [&](const double2* k0, const double2* k1, int v0, double2 (&w0)[4], double2 (&w1)[4]) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) { w0[v] = k0[(v0 + v) * 64 + lane]; w1[v] = k1[(v0 + v) * 64 + lane]; }
-      };
-      double x[kRegs];
-      double2 wa0[4], wa1[4], wb0[4], wb1[4], wc0[4], wc1[4], wd0[4], wd1[4];
-      load4(lo0, lo1, 0, wa0, wa1);
-      load4(lo0, lo1, 4, wb0, wb1);
-      load4(hi0, hi1, 0, wc0, wc1);
-      load4(hi0, hi1, 4, wd0, wd1);
-      Xf::fwd_digits(lane, x, d, q, 0u, tw, buf, f);
-      Xf::mac(s[0], s[1], x, wa0, wa1, 0, f);
-      Xf::mac(s[0], s[1], x, wb0, wb1, 4, f);
-      Xf::mac(s[2], s[3], x, wc0, wc1, 0, f);
-      Xf::mac(s[2], s[3], x, wd0, wd1, 4, f);
-    }
-    // partial sums a wave does not own go through LDS (position u*64 + lane is conflict-free)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (owner(k) != wave) {
-        double* dst = s_part[wave][slot(k, wave)];
-#pragma unroll
-        for (int u = 0; u < kRegs; ++u) dst[u * 64 + lane] = s[k][u];
-      }
-    }
-    __syncthreads();   // partials visible; every wave has finished reading the accumulator
-    if constexpr (G == 4) {
-      double x[kRegs];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (wave == k) {
-#pragma unroll
-          for (int u = 0; u < kRegs; ++u) x[u] = s[k][u];
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        if (g != wave) {
-          const double* src = s_part[g][slot(wave, g)];
-#pragma unroll
-          for (int u = 0; u < kRegs; ++u) x[u] += src[u * 64 + lane];
-        }
-      }
-      Xf::inverse(lane, x, tw, buf, f);
-      const int sh = wave >= 2 ? 16 : 0;
-      int32_t* acc = s_acc[wave & 1];
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) atomicAdd(reinterpret_cast<unsigned*>(acc) + lane + 64 * r, (uint32_t)f_to_torus32(x[r]) << sh);
-    } else {
-      double xa[kRegs], xb[kRegs];
-      if (wave == 0) {
-#pragma unroll
-        for (int u = 0; u < kRegs; ++u) { xa[u] = s[0][u]; xb[u] = s[2][u]; }
-      } else {
-#pragma unroll
-        for (int u = 0; u < kRegs; ++u) { xa[u] = s[1][u]; xb[u] = s[3][u]; }
-      }
-      const double* pa = s_part[1 - wave][0];
-      const double* pb = s_part[1 - wave][1];
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) { xa[u] += pa[u * 64 + lane]; xb[u] += pb[u * 64 + lane]; }
-      Xf::inverse2(lane, xa, xb, tw, buf, f);
-      int32_t* acc = s_acc[wave];
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) {
-        const int j = lane + 64 * r;
-        acc[j] = (int32_t)((uint32_t)acc[j] + (uint32_t)f_to_torus32(xa[r]) + ((uint32_t)f_to_torus32(xb[r]) << 16));
-      }
-    }
-    __syncthreads();   // accumulator updated
-  }
-  int32_t* out = a.u_out + ct * (kN + 1);
-  if (wave == 0) {
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) {
-      const int j = lane + 64 * r;
-      out[j] = (j == 0) ? s_acc[0][0] : (int32_t)(0u - (uint32_t)s_acc[0][kN - j]);
-    }
-    if (lane == 0) out[kN] = s_acc[1][0];
-  }
-}
-
-// (An eight-wave form of this kernel -- blind_rotate_coops8_kernel, round 4: rows over 8 waves as in blind_rotate_coop8_kernel, the
-// four sums met by LDS f64 atomics -- was built, bit-exact, and is SLOWER: 4.90 / 6.93 ms against 4.08 ms for 196 sign bootstraps
-// (profiles/r04/i_ab_coop8_atomics_and_coops8.txt). Four 32-register sums beside a transform leave a wave of a two-wave SIMD (256
-// registers) no room to keep a key row in flight across the transform, which is what the four-wave form's 412 registers buy. Removed.)
 // -------------------------------------------------------------------------------------------------
 // Blind rotation, "duo" workgroup form (mid-size batches: 2 x #CUs < B < 8 x #CUs, even l).
 // One wave per ciphertext leaves half the wave slots empty there and every wave streams the whole key
@@ -1719,179 +988,6 @@ __global__ __launch_bounds__(512) void blind_rotate_coop8_kernel(BlindRotateArgs
 }
 
 // -------------------------------------------------------------------------------------------------
-// The same form with a LISTED step (round 6), for the deals with at most one row per wave whose inverse waves carry no row
-// (coop8_listed: l < 4, default-128). There a step is a serial chain -- mask word -> rotated difference -> ONE row -> atomics ->
-// inverse -- and three of its links are shorter here:
-// * the CMUX steps that are not the identity are listed ONCE, in the prologue, in LDS (s_steps: (i << 16) | bara, compacted by
-//   wave ballots; n <= kCoop8MaxSteps, the launcher's condition for this kernel): a step reads its entry a whole step ahead
-//   instead of waiting ~400 cycles for a global load of the ciphertext word in front of its first instruction;
-// * the prepared rotated difference (X^bara - 1) * acc + gadget offset of BOTH components is built once per step by all 512
-//   threads (4 coefficients each) into s_d[2][N] behind the accumulator update, and the row waves read their 16 values from
-//   there (one more workgroup barrier: three per step); in the kernel above each wave of a component rebuilds all 1,024 of
-//   them (32 LDS reads + ~160 vector instructions per lane);
-// * a wave's key row is requested a phase early, behind barrier 1 of the step before: it travels while the two inverse waves
-//   work and the CU's vector-memory path is otherwise idle.
-// 196 default-128 ciphertexts: 2.65 -> 2.49 (list + shared difference) -> 2.21-2.23 ms (early request), same box
-// (profiles/r06/c_*). For l >= 4 (the REDsec set: five rows per SIMD) the same step was built and measured at +1 %
-// (2.42 against 2.40 ms) and stays with the kernel above: there the rows phase is bound by the SIMDs' instruction issue -- 5 rows
-// x ~2.2 k cycles, the throughput kernel's own cost per transform -- and what is taken out of the phases in front of it shows up
-// again as contention inside it (phase stamps: rotated difference 1.35-1.8 k -> 0.75 k, rows 8.6 / 9.7 k -> 9.3 / 10.9 k cycles);
-// an inverse wave that also carries rows cannot request early without standing ~2,000 cycles in the vector-memory issue queue in
-// front of its transform (3.1 k -> 5.1 k cycles, +8 %).
-// LDS: 104 KB as above + 8 KB rotated difference + 8 KB step list = 120 KB.
-// -------------------------------------------------------------------------------------------------
-template <class Xf>
-__global__ __launch_bounds__(512) void blind_rotate_coop8_listed_kernel(BlindRotateArgs a) {
-  using C = typename Xf::Cfg;
-  static_assert(Xf::kCertificate, "FFT policy only: the exact-NTT reduction schedule is validated for four partials");
-  if (recompute_not_needed(a)) return;
-  constexpr int G = kCoop8Waves, L = C::L, KPL = 2 * L;
-  constexpr int kInvA = coop8_inv_a(L), kInvB = coop8_inv_b(L);   // placement: rs_lds_plan.h (checked on the host)
-  static_assert(coop8_listed(L) && coop8_row_count(L, kInvA) == 0 && coop8_row_count(L, kInvB) == 0, "the early key request assumes inverse waves without rows");
-  __shared__ double s_tw[Xf::kTableDoubles + 1];
-  __shared__ double s_buf[G][kBufDoubles];
-  __shared__ double s_sum[2][kN];   // the two column sums, added up by LDS floating-point atomics (zero between steps)
-  __shared__ int32_t s_acc[2][kN];
-  __shared__ int32_t s_d[2][kN];                   // gadget_prepare((X^bara - 1) * acc) of the step about to run, both components
-  __shared__ uint32_t s_steps[kCoop8MaxSteps + 1];   // the steps with bara != 0, in order: (i << 16) | bara
-  __shared__ int s_step_count;
-  stage_tables(s_tw, a.tw, 64 * G, Xf::kTableDoubles);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = threadIdx.x & 63;
-  const long ct = blockIdx.x;
-  const Field f = a.f;
-  double* buf = s_buf[wave];
-  for (int e = threadIdx.x; e < 2 * kN; e += 64 * G) (&s_sum[0][0])[e] = 0.0;
-  typename Xf::State tw;
-  Xf::init(tw, lane, s_tw, a.tw);
-  const int32_t* row0 = a.in0 + ct * a.W;
-  const int32_t* row1 = a.in1 ? a.in1 + ct * a.W : nullptr;
-  const int n = a.n;
-  // rows [first, first + cnt) of this wave's component (digit index q = first + rr, TGSW row comp * L + q)
-  const int comp = coop8_comp(L, wave), cnt = coop8_row_count(L, wave), first = coop8_row_first(L, wave);
-  [[maybe_unused]] const int r_first = cnt > 0 ? (int)(blockIdx.x % (unsigned)cnt) : 0;
-  double dev = 0.0;
-  RS_C8L_STAMP_DECL;   // -DRS_DIAG=256 (tools/stamp_coop8.py): 0 step entry + shared rotated difference, 1 its barrier, 2 rows (forward +
-                      // multiply-accumulate), 3 atomics issued, 4 barrier 1, 5 inverse + accumulator update, 6 barrier 2, 7 prologue / extract
-  auto word = [&](int i) -> int32_t {
-    uint32_t v = (uint32_t)a.c0 * (uint32_t)row0[i];
-    if (row1) v += (uint32_t)a.c1 * (uint32_t)row1[i];
-    return (int32_t)v;
-  };
-  if (wave < 2) {
-    const int32_t barb = modswitch_2N((int32_t)((uint32_t)word(n) + (uint32_t)a.bconst));
-    const int rot = 2 * kN - barb;
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) {
-      const int j = lane + 64 * r;
-      s_acc[wave][j] = wave == 0 ? 0 : test_vector(a, ct, j, rot);
-    }
-  } else if (wave == 2) {
-    // the step list: 64 mask words at a time, the non-zero ones compacted in order behind those of the chunks before
-    int count = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + lane;
-      const int32_t bara = i < n ? modswitch_2N(word(i)) : 0;
-      const unsigned long long live = __ballot(bara != 0);
-      if (bara != 0) s_steps[count + __popcll(live & ((1ull << lane) - 1ull))] = ((uint32_t)i << 16) | (uint32_t)bara;
-      count += __popcll(live);
-    }
-    if (lane == 0) { s_steps[count] = 0u; s_step_count = count; }
-  }
-  __syncthreads();
-  constexpr uint32_t offset = gadget_offset<C>();
-  const int trips = __builtin_amdgcn_readfirstlane(s_step_count);
-  uint32_t entry = trips > 0 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_steps[0]) : 0u;
-  double2 w0[8], w1[8];
-  auto request_row = [&](int step_i, int q) {
-    const double* bk_i = a.bk_x + (size_t)diag::key_step(step_i) * KPL * 2 * kN;
-    const double2* bp0 = reinterpret_cast<const double2*>(bk_i + (size_t)((comp * L + q) * 2) * kN);
-    const double2* bp1 = bp0 + kN / 2;
-#pragma unroll
-    for (int v = 0; v < 8; ++v) { w0[v] = bp0[v * 64 + lane]; w1[v] = bp1[v * 64 + lane]; }
-  };
-  if (cnt > 0 && trips > 0) request_row((int)(entry >> 16), first + r_first);
-  RS_C8L_STAMP(7);
-  for (int k = 0; k < trips; ++k) {
-    const int i = (int)(entry >> 16), bara = (int)(entry & 0xffffu);
-    const uint32_t entry_next = s_steps[k + 1];   // requested a whole step ahead (the entry behind the last one exists: 0)
-    // the prepared rotated difference of both components, 4 coefficients per thread (waves 0-3: component 0, waves 4-7: 1)
-    {
-      const int c = coop8_diff_comp(wave);
-#pragma unroll
-      for (int m = 0; m < kCoop8DiffPerThread; ++m) {
-        const int j = coop8_diff_coeff((int)threadIdx.x, m);
-        s_d[c][j] = gadget_prepare<C>(rotated_diff(s_acc[c], j, bara));
-      }
-    }
-    RS_C8L_STAMP(0);
-    __syncthreads();   // s_d complete; the accumulator is not read again before its update
-    RS_C8L_STAMP(1);
-    double s0[kRegs], s1[kRegs];
-#pragma unroll
-    for (int u = 0; u < kRegs; ++u) { s0[u] = 0.0; s1[u] = 0.0; }
-    if (cnt > 0) {
-      int32_t d[kRegs];
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) d[r] = s_d[comp][lane + 64 * r];
-      int r_run = r_first;   // rr = 0 is row blockIdx.x mod cnt of the wave's share in every step (per-workgroup row order, as in the four-wave form)
-#pragma unroll 1
-      for (int rr = 0; rr < cnt; ++rr) {
-        const int q = first + r_run;
-        r_run = r_run + 1 == cnt ? 0 : r_run + 1;
-        if (rr > 0) request_row(i, q);   // the first row's key is already on its way
-        double x[kRegs];
-        Xf::fwd_digits(lane, x, d, q, offset, tw, buf, f);
-        Xf::mac8(s0, s1, x, w0, w1, f);
-      }
-      RS_C8L_STAMP(2);
-    }
-    // every wave adds its two partial sums into the column sums with ds_add_f64 (no return value: 32 instructions that overlap
-    // the other waves' transforms); the order of the floating-point additions is free -- the sums are rounded to the exact
-    // integers afterwards, with the certificate watching the distance as everywhere
-    if (cnt > 0) {
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) { unsafeAtomicAdd(&s_sum[0][u * 64 + lane], s0[u]); unsafeAtomicAdd(&s_sum[1][u * 64 + lane], s1[u]); }
-    }
-    RS_C8L_STAMP(3);
-    __syncthreads();   // sums complete; every row wave has finished reading the rotated difference
-    RS_C8L_STAMP(4);
-    entry = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry_next);
-    if (cnt > 0 && k + 1 < trips) request_row((int)(entry >> 16), first + r_first);   // the next step's row, while the inverse waves work
-    if (wave == kInvA || wave == kInvB) {
-      double* sum = s_sum[wave == kInvA ? 0 : 1];
-      double x[kRegs];
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) x[u] = sum[u * 64 + lane];
-#pragma unroll
-      for (int u = 0; u < kRegs; ++u) sum[u * 64 + lane] = 0.0;   // for the next step (same lane, same address: in order)
-      Xf::inverse(lane, x, tw, buf, f);
-      int32_t* acc = s_acc[wave == kInvA ? 0 : 1];
-#pragma unroll
-      for (int r = 0; r < kRegs; ++r) {
-        const int j = lane + 64 * r;
-        acc[j] = (int32_t)((uint32_t)acc[j] + (uint32_t)Xf::to_torus(x[r], dev));
-      }
-    }
-    RS_C8L_STAMP(5);
-    __syncthreads();   // accumulator updated, sums zero
-    RS_C8L_STAMP(6);
-  }
-  int32_t* out = a.u_out + ct * (kN + 1);
-  if (wave == 0) {
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) {
-      const int j = lane + 64 * r;
-      out[j] = (j == 0) ? s_acc[0][0] : (int32_t)(0u - (uint32_t)s_acc[0][kN - j]);
-    }
-    if (lane == 0) out[kN] = s_acc[1][0];
-  }
-  RS_C8L_STAMP(7);
-  RS_C8L_STAMP_FLUSH(wave);
-  if (wave == kInvA || wave == kInvB) publish_certificate(dev, a.dev_flag, lane);
-}
-
-// -------------------------------------------------------------------------------------------------
 // Debug tap: out = a_small * b_torus (negacyclic, mod 2^32) through forward/pointwise/inverse.
 // -------------------------------------------------------------------------------------------------
 template <class Xf, int WPB>
@@ -1938,7 +1034,6 @@ __global__ __launch_bounds__(64 * WPB) void polymul_kernel(const int32_t* __rest
 // -------------------------------------------------------------------------------------------------
 // Launchers. cfg: 0 = default-128-shaped gadget, 1 = REDsec-shaped; mode: 0 = exact NTT, 1 = FFT.
 // -------------------------------------------------------------------------------------------------
-#if RS_BS_PART & 1
 template <class Xf, int WPB>
 static hipError_t launch_br(const BlindRotateArgs& a, long max_blocks, hipStream_t st) {
   long blocks = (a.B + WPB - 1) / WPB;
@@ -1953,26 +1048,6 @@ static hipError_t launch_br(const BlindRotateArgs& a, long max_blocks, hipStream
   hipLaunchKernelGGL((blind_rotate_kernel<Xf, WPB>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, args);
   return hipGetLastError();
 }
-
-#endif  // RS_BS_PART & 1
-// XCD cohorts of the lock-step kernels (cohort_step, rs_cohort.h): the ONLY place that hands a kernel a progress table. Every
-// launch path starts from arguments whose `progress` is null and calls this for the launches that may use one: those whose
-// workgroups sweep the key more than once (groups > grid), on a device whose workgroups are dealt round-robin over EIGHT XCDs --
-// the protocol's xcd = blockIdx & 7. The one MI355X configuration that is true for is the whole chip as one partition (SPX,
-// 256 CUs = 8 x 32); under CPX / DPX / QPX partitions a table row would mix workgroups served by different L2s, which
-// could only wait for each other with no L2 to share, so there the workgroups run free. `step_bytes` = key bytes a CMUX step
-// reads; the lag keeps a cohort inside about a third of its XCD's 4 MB L2.
-static hipError_t cohort_setup(BlindRotateArgs& w, int* table, long step_bytes, long groups, long grid, long num_cus, const LaunchOpts& o, hipStream_t st) {
-  w.progress = nullptr; w.cohort_every = 0; w.cohort_lag = 0;
-  if (!table || o.no_cohort || num_cus != 256 || grid > 8L * kCohortSlots || groups <= grid) return hipSuccess;
-  w.cohort_lag = (int32_t)std::max<long>(1, (4L << 20) / 3 / step_bytes - 1);
-  w.cohort_every = w.cohort_lag >= 4 ? 2 : 1;
-  w.progress = table;
-  return hipMemsetAsync(table, 0x7f, 8 * kCohortSlots * sizeof(int), st);
-}
-#if RS_BS_PART & 1
-
-hipError_t launch_coop8_listed(int cfg, const BlindRotateArgs& a, hipStream_t st);   // part 4
 
 template <class Xf>
 static hipError_t launch_br_xf(const BlindRotateArgs& a_in, int wpb, long num_cus, bool coop4, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
@@ -1991,9 +1066,9 @@ static hipError_t launch_br_xf(const BlindRotateArgs& a_in, int wpb, long num_cu
     if constexpr (Xf::kWorkgroupForm) {
       // at most one ciphertext per CU: eight waves share it (two per SIMD), see blind_rotate_coop8_kernel
       if (!o.no_coop8 && a.B <= num_cus) {
-        if constexpr (coop8_listed(Xf::Cfg::L)) {   // its own object (RS_BS_PART bit 4): see there
+        if constexpr (kCoop8ListedCfg<Xf> >= 0) {   // an object of its own: rs_bootstrap_listed.hip
           if (!o.no_coop8_listed && a.n <= kCoop8MaxSteps) {
-            if (hipError_t e = launch_coop8_listed(std::is_same_v<typename Xf::Cfg, CfgDefault128> ? 0 : 1, a, st); e != hipSuccess) return e;
+            if (hipError_t e = launch_coop8_listed(kCoop8ListedCfg<Xf>, a, st); e != hipSuccess) return e;
             return done(kFormCoop8Listed, 8, 1);
           }
         }
@@ -2089,7 +1164,7 @@ hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int 
                   : launch_br_xf<XfFft<CfgRedsecV2>>(a, wpb, num_cus, true, opts, st, info);
 }
 
-// The split duo form's launch (mid-size batches of the split mode): lives in part 1, called from part 2.
+// The split duo form's launch (mid-size batches of the split mode): called from rs_bootstrap_split.hip.
 hipError_t launch_split_duos(int cfg, const BlindRotateArgs& a, long grid, hipStream_t st) {
   if (cfg == 0) hipLaunchKernelGGL((blind_rotate_duos_kernel<CfgDefault128>), dim3((unsigned)grid), dim3(512), 0, st, a);
   else if (cfg == 1) hipLaunchKernelGGL((blind_rotate_duos_kernel<CfgRedsecV2>), dim3((unsigned)grid), dim3(512), 0, st, a);
@@ -2097,87 +1172,7 @@ hipError_t launch_split_duos(int cfg, const BlindRotateArgs& a, long grid, hipSt
   else return hipErrorNotSupported;
   return hipGetLastError();
 }
-#endif  // RS_BS_PART & 1
 
-#if RS_BS_PART & 4
-// blind_rotate_coop8_listed_kernel lives in an object of its own (built with part 1's flags). Instantiated beside the other FFT
-// kernels it changed THEIR code -- 15 of part 1's device functions came out a few instructions different, the REDsec set's
-// coop8 kernel among them (tools/codeobj_digest.py), with the source of none of them touched -- and the kernels of the BASELINE
-// configurations are to stay the instructions that were measured. cfg: 0 default-128, 1 the REDsec set (no listed deal).
-hipError_t launch_coop8_listed(int cfg, const BlindRotateArgs& a, hipStream_t st) {
-  if constexpr (coop8_listed(CfgDefault128::L)) {
-    if (cfg == 0) {
-      hipLaunchKernelGGL((blind_rotate_coop8_listed_kernel<XfFft<CfgDefault128>>), dim3((unsigned)a.B), dim3(512), 0, st, a);
-      return hipGetLastError();
-    }
-  }
-  return hipErrorInvalidValue;
-}
-#endif  // RS_BS_PART & 4
-
-#if RS_BS_PART & 2
-hipError_t launch_split_duos(int cfg, const BlindRotateArgs& a, long grid, hipStream_t st);
-// Split-key workgroup form (N = 1024; cfg 0 / 1 = the two shipped gadgets, 2 = redsec_params_small's l=3 Bgbit=10): a.bk_x = the split key of rs_general.h,
-// a.tw = the FFT tables of rs_fft.h. Returns hipErrorNotSupported for an unknown gadget id (caller: general kernel).
-hipError_t launch_blind_rotate_split_wg(int cfg, const BlindRotateArgs& a_in, int num_cus, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
-  int* const cohort_table = a_in.progress;   // the caller's offer; only cohort_setup puts it back into a launch's arguments
-  BlindRotateArgs a = a_in;
-  a.progress = nullptr; a.cohort_every = 0; a.cohort_lag = 0;
-  // any batch size: even a single group of it walks its CMUX chain in 57 us per step (REDsec set) against the 92 us of a lone
-  // wave of the general kernel (sign1024x1 in split mode: 65.7 -> 40 ms). Up to 4 ciphertexts per CU the groups are 4 waves:
-  // one wave per SIMD on twice the CUs.
-  auto coop = [&](auto c) {
-    using C = decltype(c);
-    LaunchInfo li;
-    li.form = kFormSplitCoop; li.resident = 1;
-
-    if constexpr ((2 * C::L) % 4 == 0) {
-      if (a.B <= num_cus) {
-        hipLaunchKernelGGL((blind_rotate_coops_kernel<C, 4>), dim3((unsigned)a.B), dim3(256), 0, st, a);
-        li.waves_per_block = 4;
-        if (info) *info = li;
-        return hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((blind_rotate_coops_kernel<C, 2>), dim3((unsigned)a.B), dim3(128), 0, st, a);
-    li.waves_per_block = 2;
-    if (info) *info = li;
-    return hipGetLastError();
-  };
-  if (!o.no_coop && a.B <= 2L * num_cus) {   // latency form: several waves per ciphertext, as in the unsplit modes
-    if (cfg == 0) return coop(CfgDefault128{});
-    if (cfg == 1) return coop(CfgRedsecV2{});
-    if (cfg == 2) return coop(CfgRedsecSmall{});
-    return hipErrorNotSupported;
-  }
-  if (!o.no_duo && a.B <= 4L * num_cus) {   // mid-size batches: 4 ciphertexts x 2 waves per workgroup (no_duo: the 4-wave lock-step groups)
-    const long grid = std::min<long>((a.B + 3) / 4, num_cus);
-    if (cfg < 0 || cfg > 2) return hipErrorNotSupported;
-    if (info) { info->form = kFormSplitDuo; info->waves_per_block = 8; info->resident = 4 * grid; }
-    return launch_split_duos(cfg, a, grid, st);
-  }
-  const int wpb = (a.B <= 4L * num_cus && !o.no_wg4) ? 4 : 8;
-  const long groups = (a.B + wpb - 1) / wpb;
-  const long grid = groups < num_cus ? groups : num_cus;
-  BlindRotateArgs w = a;
-  // a CMUX step reads 2 * 2l half-rows of 16 KB
-  if (hipError_t e = cohort_setup(w, cohort_table, 4L * (cfg == 1 ? 10 : 3) * 16384, groups, grid, num_cus, o, st); e != hipSuccess) return e;
-  auto go = [&](auto c) {
-    using C = decltype(c);
-    if (wpb == 8) hipLaunchKernelGGL((blind_rotate_wgs_kernel<C, 8>), dim3((unsigned)grid), dim3(512), 0, st, w);
-    else hipLaunchKernelGGL((blind_rotate_wgs_kernel<C, 4>), dim3((unsigned)grid), dim3(256), 0, st, w);
-  };
-  if (cfg == 0) go(CfgDefault128{});
-  else if (cfg == 1) go(CfgRedsecV2{});
-  else if (cfg == 2) go(CfgRedsecSmall{});
-  else return hipErrorNotSupported;
-  if (info) { info->form = kFormSplitWorkgroup; info->waves_per_block = wpb; info->resident = wpb * grid; }
-  return hipGetLastError();
-}
-
-#endif  // RS_BS_PART & 2
-
-#if RS_BS_PART & 1
 hipError_t launch_bk_transform(int cfg, int mode, const int32_t* bk, double* bk_x, const double* tw, Field f, double scale,
                                long n_polys, hipStream_t st) {
   constexpr int WPB = 4;
@@ -2206,17 +1201,8 @@ hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32
   return hipGetLastError();
 }
 
-#endif  // RS_BS_PART & 1
-
 }  // namespace rs
 
-#if RS_BS_PART & RS_DIAG_STAMP_PART
-// diagnostic builds only (not part of include/redsec_hip.h): copy the per-wave phase sums to the host and clear them
-extern "C" int rs_debug_read_stamps(unsigned long long* host, size_t count) {
-  const size_t all = sizeof(rs::g_rs_stamps) / sizeof(unsigned long long);
-  if (count > all) count = all;
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(rs::g_rs_stamps), count * sizeof(unsigned long long)) != hipSuccess) return 1;
-  static unsigned long long zeros[256 * 8 * rs::diag::kStampPhases];
-  return hipMemcpyToSymbol(HIP_SYMBOL(rs::g_rs_stamps), zeros, sizeof(zeros)) == hipSuccess ? 0 : 1;
-}
+#if RS_STAMPS_ON(1 | 4 | 8)   // blind_rotate_wg_kernel, blind_rotate_duo_kernel, blind_rotate_coop8_kernel
+RS_DEFINE_STAMPS()
 #endif

@@ -4,10 +4,10 @@
 //
 //   RS_DIAG bit   what the diagnostic build does
 //   1             phase stamps in blind_rotate_wg_kernel  (tools/stamp_profile.py)
-//   2             phase stamps in blind_rotate_wgs_kernel (the array then lives in part 2 of rs_bootstrap.hip, RS_BS_PART)
+//   2             phase stamps in blind_rotate_wgs_kernel (the array then lives in rs_bootstrap_split.hip)
 //   4             phase stamps in blind_rotate_duo_kernel (tools/stamp_coop8.py duo)
 //   8             phase stamps in blind_rotate_coop8_kernel (tools/stamp_coop8.py)
-//   256           phase stamps in blind_rotate_coop8_listed_kernel (tools/stamp_coop8.py; the array then lives in part 4)
+//   256           phase stamps in blind_rotate_coop8_listed_kernel (tools/stamp_coop8.py; the array then lives in rs_bootstrap_listed.hip)
 //   16            NO-KEY TIMING PROBE, RESULTS ARE WRONG: every CMUX step reads the key rows of step 0, which stay in the L2s --
 //                 bounds what key streaming can cost a kernel (split lock-step, cooperative, coop8 and general-ring kernels);
 //                 rs_api.cpp then also switches the enforced split certificate off (the sums are garbage by construction)
@@ -22,6 +22,8 @@
 //
 // Phase stamps (cdna_hip_programming.md section 7, in-kernel stamps): s_memtime behind s_waitcnt lgkmcnt(0) at up to eight
 // phase boundaries, summed per wave into g_rs_stamps and read back by rs_debug_read_stamps (not part of include/redsec_hip.h).
+// Both are written once (RS_DEFINE_STAMPS, rs_bootstrap.h) and instantiated by the unit that holds the stamped kernel: bits
+// 1, 4, 8 rs_bootstrap.hip, bit 2 rs_bootstrap_split.hip, bit 256 rs_bootstrap_listed.hip -- stamp bits of ONE unit per build.
 // The stamps drain LDS reads: read the SHARES of a stamped run, never quote its run time.
 //
 // Every experiment switch of rounds 1-4 (RS_T_*, RS_WG_*, RS_GEN_* ...) that was measured and not adopted is gone from the
@@ -52,7 +54,7 @@ constexpr int kStampPhases = 8;
 #ifdef RS_DIAG
 #define RS_STAMPS_ON(bit) (((RS_DIAG) & (bit)) != 0)
 #if defined(__HIPCC__)
-// the phase sums, [workgroup < 256][wave][phase]; defined in the object of rs_bootstrap.hip that launches the stamped kernel
+// the phase sums, [workgroup < 256][wave][phase]; defined in the unit that holds the stamped kernel (RS_DEFINE_STAMPS)
 namespace rs { extern __device__ unsigned long long g_rs_stamps[256 * 8 * diag::kStampPhases]; }
 #endif
 #define RS_STAMP_DECL_ unsigned long long st_sum_[rs::diag::kStampPhases] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_last_; \
@@ -112,13 +114,8 @@ namespace rs { extern __device__ unsigned long long g_rs_stamps[256 * 8 * diag::
 #define RS_C8L_STAMP(k) ((void)0)
 #define RS_C8L_STAMP_FLUSH(wave) ((void)0)
 #endif
-// which object of rs_bootstrap.hip (RS_BS_PART) owns the stamp array: the part that holds the stamped kernel (one bit per build)
-#if RS_STAMPS_ON(2)
-#define RS_DIAG_STAMP_PART 2
-#elif RS_STAMPS_ON(256)
-#define RS_DIAG_STAMP_PART 4
-#elif RS_STAMPS_ON(1 | 4 | 8)
-#define RS_DIAG_STAMP_PART 1
-#else
-#define RS_DIAG_STAMP_PART 0
+// The build has no relocatable device code, so the stamp array lives in the unit of the kernel that writes it and a second unit
+// with a stamped kernel would reference an undefined device symbol.
+#if RS_STAMPS_ON(1 | 4 | 8) + RS_STAMPS_ON(2) + RS_STAMPS_ON(256) > 1
+#error "RS_DIAG: stamp bits of one unit per build (1, 4, 8: rs_bootstrap.hip; 2: rs_bootstrap_split.hip; 256: rs_bootstrap_listed.hip)"
 #endif

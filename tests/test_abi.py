@@ -124,13 +124,14 @@ def test_kernel_form_names_of_the_binding_follow_the_library_enum():
 
 def test_kernel_sources_carry_no_experiment_switches():
     """Round 5 deleted the ~70 compile-time experiment switches of rounds 1-4 (RS_T_*, RS_WG_*, RS_GEN_* ...: each measured, none adopted,
-    verdicts in MEASUREMENTS.md) together with their code paths. What may still select code in csrc/: RS_BS_PART (which launchers an
-    object of rs_bootstrap.hip holds, redsec_amd/build.py) and RS_DIAG (rs_diag.h: phase stamps and the no-key timing probe of
-    diagnostic builds, the ONE guard for everything diagnostic). This test keeps it that way."""
+    verdicts in MEASUREMENTS.md) together with their code paths. What may still select code in csrc/: RS_DIAG (rs_diag.h: phase stamps
+    and the no-key timing probe of diagnostic builds, the ONE guard for everything diagnostic) -- which launchers and kernels an object
+    holds is decided by its translation unit (rs_bootstrap.hip, rs_bootstrap_split.hip, rs_bootstrap_listed.hip), not by a switch. This
+    test keeps it that way."""
     import glob
     import re
     csrc = os.path.join(ROOT, "redsec_amd", "csrc")
-    allowed = {"RS_BS_PART", "RS_DIAG", "RS_DIAG_STAMP_PART", "RS_STAMPS_ON", "RS_HD"}     # the last three: helper macros, not switches
+    allowed = {"RS_DIAG", "RS_STAMPS_ON", "RS_HD"}     # the last two: helper macros, not switches
     seen, conditionals = set(), 0
     for path in sorted(glob.glob(os.path.join(csrc, "*"))):
         text = open(path).read()
@@ -148,27 +149,57 @@ def test_kernel_sources_carry_no_experiment_switches():
             assert not re.search(r"\bif\s*\(\s*[01!]\s*(\)|&&|\|\|)|\b(&&|\|\|)\s*[01]\s*\)", code), "constant condition in %s: %s" % (name, line.strip())
             assert not re.search(r"\b[01]=[01]\b", line), "garbled switch text in %s: %s" % (name, line.strip())
     assert seen <= allowed, sorted(seen - allowed)
-    assert conditionals <= 40, conditionals                          # 25 today, most of them __HIP_DEVICE_COMPILE__ / __HIPCC__
+    assert conditionals <= 24, conditionals                          # 24 today: __HIP_DEVICE_COMPILE__ / __HIPCC__ and rs_diag.h; may go down, never up
 
 
 @pytest.mark.parametrize("src,flags", [
-    ("rs_bootstrap.hip", ["-DRS_DIAG=253"]),                       # stamps of the three part-1 kernels + every timing probe
-    ("rs_bootstrap.hip", ["-DRS_DIAG=2", "-DRS_BS_PART=2"]),      # stamps of the split lock-step kernel: the array lives in part 2
-    ("rs_bootstrap.hip", ["-DRS_DIAG=2", "-DRS_BS_PART=1"]),      # ... and part 1 of that build declares it without defining it
-    ("rs_bootstrap.hip", ["-DRS_DIAG=256", "-DRS_BS_PART=4"]),    # stamps of the listed coop8 kernel: the array lives in part 4
+    ("rs_bootstrap.hip", ["-DRS_DIAG=253"]),                       # stamps of its three stamped kernels + every timing probe
+    ("rs_bootstrap_split.hip", ["-DRS_DIAG=2"]),                   # stamps of the split lock-step kernel: the array lives in its unit
+    ("rs_bootstrap.hip", ["-DRS_DIAG=2"]),                         # ... and rs_bootstrap.hip of that build has no stamped kernel and no array
+    ("rs_bootstrap_listed.hip", ["-DRS_DIAG=256"]),                # stamps of the listed coop8 kernel: the array lives in its unit
     ("rs_general.hip", ["-DRS_DIAG=144"]),                         # no-key and half-key probes of the general rings
     ("rs_api.cpp", ["-DRS_DIAG=48"]),                              # the probes' switch that turns the exactness gates off
 ])
 def test_diagnostic_builds_compile(src, flags):
     """Everything diagnostic sits behind -DRS_DIAG=<bits> (csrc/rs_diag.h) and no product build defines it: nothing but this test would
     notice those paths rotting. Front end only (hipcc -fsyntax-only instantiates every kernel the launchers name): seconds."""
+    r = _syntax_only(src, flags)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
+def _syntax_only(src, flags):
     import shutil
     import subprocess
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     csrc = os.path.join(ROOT, "redsec_amd", "csrc")
-    r = subprocess.run([hipcc, "-fsyntax-only", "--offload-arch=gfx950", "-std=c++17", "-Wno-unused-command-line-argument",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + csrc] + (["-x", "hip"] if src.endswith(".cpp") else []) + flags + [os.path.join(csrc, src)],
-                       capture_output=True, text=True, timeout=300)
+    return subprocess.run([hipcc, "-fsyntax-only", "--offload-arch=gfx950", "-std=c++17", "-Wno-unused-command-line-argument",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc] + (["-x", "hip"] if src.endswith(".cpp") else []) + flags + [os.path.join(csrc, src)],
+                          capture_output=True, text=True, timeout=300)
+
+
+def test_stamp_bits_of_two_units_in_one_build_are_refused():
+    """The stamp array lives in the unit of the stamped kernel and the build has no relocatable device code: -DRS_DIAG=264 (bit 8:
+    rs_bootstrap.hip, bit 256: rs_bootstrap_listed.hip) would leave one unit referencing an undefined device symbol. rs_diag.h refuses
+    it with an #error."""
+    r = _syntax_only("rs_bootstrap.hip", ["-DRS_DIAG=264"])
+    assert r.returncode != 0 and "stamp bits of one unit per build" in r.stderr, r.stderr[-3000:]
+
+
+def test_a_variant_build_of_this_tree_loads_and_exports_the_abi(tmp_path):
+    """tools/build_variant.sh (same-box A/B libraries, the stamped builds of tools/stamp_*.py) goes through the recipe of
+    redsec_amd/build.py (python -m redsec_amd.build --variant): the library it links must load and resolve every ABI symbol, i.e.
+    hold every object of the product library."""
+    import shutil
+    import subprocess
+    import sys
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("no hipcc")
+    out = tmp_path / "lib_variant_test.so"
+    r = subprocess.run([sys.executable, "-m", "redsec_amd.build", "--variant", "variant_test", "--src", ROOT, "--out", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
+    lib = ctypes.CDLL(str(out))
+    for name in redsec_amd.ABI_SYMBOLS:
+        assert hasattr(lib, name), "the variant library does not export " + name

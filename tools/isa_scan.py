@@ -7,10 +7,12 @@ Round 4's gains in the split lock-step kernel (+5.6 %: 64-bit VALU compares and 
 kernel (-2.9 %: 310 selects per CMUX step) and the keyswitch kernels came from reading exactly these numbers.
 
   python tools/isa_scan.py [file.hip] [kernel-name regex] [-- extra hipcc flags]
-  python tools/isa_scan.py redsec_amd/csrc/rs_bootstrap.hip 'wgs_kernel.*Li8E' -- -DRS_BS_PART=2 -mllvm -amdgpu-sched-strategy=max-memory-clause
+  python tools/isa_scan.py redsec_amd/csrc/rs_bootstrap_split.hip 'wgs_kernel.*Li8E'
+  python tools/isa_scan.py redsec_amd/csrc/rs_bootstrap.hip 'coop8_kernel' -- -DRS_DIAG=16
 
-Compiles the file to gfx950 assembly with the build's common flags (the loop depths are LLVM's block comments; blocks laid out of line can
-carry a shallower depth than the loop they belong to: read the table together with the source)."""
+Compiles the file to gfx950 assembly with the flags its object carries in redsec_amd/build.py (HIP_OBJECTS), then the extra ones (the loop
+depths are LLVM's block comments; blocks laid out of line can carry a shallower depth than the loop they belong to: read the table together
+with the source)."""
 import collections
 import os
 import re
@@ -19,6 +21,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from redsec_amd import build  # noqa: E402
 BOOK = re.compile(r"^(scratch_\w+|v_cndmask\w*|v_cmp_\w+_[iu]64\w*|v_lshl_add_u64|v_mad_u64_u32|v_add_co_u32\w*|v_addc_co_u32\w*|v_accvgpr\w+|v_readlane_b32|"
                   r"v_writelane_b32|v_readfirstlane_b32|v_mul_lo_u32|v_mul_hi_u32|s_mul_i32|s_mul_hi_u32|s_cmp_lg_u64|flat_\w+)")
 
@@ -47,8 +51,8 @@ def main():
     pat = re.compile(argv[1] if len(argv) > 1 else ".")
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
-        cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
-               "-I" + os.path.join(ROOT, "redsec_amd/csrc"), "--cuda-device-only", "-S", src, "-o", out] + extra
+        flags = build.object_flags(os.path.splitext(os.path.basename(src))[0])
+        cmd = ["hipcc"] + flags + ["--cuda-device-only", "-S", src, "-o", out] + extra
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         lines = open(out).read().split("\n")
     starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]

@@ -1,8 +1,8 @@
 """Compressed timeline of a kernel's ISA: LDS instructions, waits and barriers with the number of vector
 instructions between them -- the view that exposed the in-order LDS drains.
 
-  hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -Iinclude -Iredsec_amd/csrc -S --cuda-device-only \
-        -o /tmp/k.s redsec_amd/csrc/rs_bootstrap.hip
+  hipcc $(python -m redsec_amd.build --print-flags rs_bootstrap) -S --cuda-device-only -o /tmp/k.s redsec_amd/csrc/rs_bootstrap.hip
+  (the flags of the object in redsec_amd/build.py; likewise rs_bootstrap_split / rs_bootstrap_listed with their .hip files)
   awk '/^_ZN2rs22blind_rotate_wg_kernel/{f=1} f{print} f&&/s_endpgm/{exit}' /tmp/k.s > /tmp/one.s
   python tools/isa_timeline.py /tmp/one.s
 
