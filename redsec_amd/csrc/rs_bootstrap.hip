@@ -1132,8 +1132,9 @@ static hipError_t launch_br_xf(const BlindRotateArgs& a_in, int wpb, long num_cu
     }
   }
   if constexpr (Xf::kWorkgroupForm && Xf::Cfg::L % 2 == 0) {
-    // mid-size batches: 4 ciphertexts x 2 waves per workgroup (no_duo falls back to one wave per ciphertext)
-    if (!o.no_wg && !o.no_duo && a.B > 2L * num_cus) {
+    // mid-size batches: 4 ciphertexts x 2 waves per workgroup (no_duo falls back to one wave per ciphertext). The kernel keeps the
+    // mod-switched mask words of a ciphertext in LDS, s_bara[4][kSmall]: a key with more steps runs one wave per ciphertext.
+    if (!o.no_wg && !o.no_duo && a.n <= kSmall && a.B > 2L * num_cus) {
       const long groups = (a.B + 3) / 4;
       const long grid = groups < num_cus ? groups : num_cus;
       hipLaunchKernelGGL((blind_rotate_duo_kernel<Xf>), dim3((unsigned)grid), dim3(512), 0, st, a);

@@ -27,6 +27,7 @@ constexpr int kCoop8Waves = 8;
 // rotated difference of a step with all 512 threads: thread t takes coefficients (t & 255) + 256 m, m < 4, of component t >> 8
 // (waves 0-3: component 0, waves 4-7: component 1), whichever row the wave then transforms.
 constexpr int kCoop8MaxSteps = 2048;
+static_assert(kCoop8MaxSteps <= 65536 && 2 * kN <= 65536, "a listed step packs (i << 16) | bara: i < kCoop8MaxSteps and bara < 2N in 16 bits each");
 RS_HD constexpr int coop8_diff_comp(int wave) { return wave >> 2; }
 RS_HD constexpr int coop8_diff_coeff(int thread, int m) { return (thread & 255) + 256 * m; }   // m < kCoop8DiffPerThread
 constexpr int kCoop8DiffPerThread = 4;
