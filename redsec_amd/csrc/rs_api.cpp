@@ -225,14 +225,6 @@ int ensure_io(rs_ctx* c, size_t B) {
   return RS_OK;
 }
 
-int pick_wpb(const rs_ctx* c, size_t B) {
-  const size_t cus = (size_t)c->num_cus;
-  if (B >= 8 * cus) return 8;
-  if (B >= 4 * cus) return 4;
-  if (B >= 2 * cus) return 2;
-  return 1;
-}
-
 int ready(rs_ctx* c) {
   int rc = use_device(c);
   if (rc) return rc;
@@ -293,7 +285,6 @@ int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, 
   if (rc) return rc;
   rc = ensure_ws(ln, B);
   if (rc) return rc;
-  const int wpb = pick_wpb(c, B);
   const int mode = c->mode;
   Combo cs[2];
   for (int k = 0; k < count; ++k) { cs[k] = combos[k]; cs[k].u = k == 0 ? ln->d_u0 : ln->d_u1; }
@@ -335,7 +326,7 @@ int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, 
       rs::BlindRotateArgs a = br_args(c, ln, 1, cs[k], mu, lut, B);
       a.dev_flag = slot;
       a.progress = lane_progress(ln);   // used by the lock-step form only, and only when its workgroups sweep the key more than once
-      RS_HIP(rs::launch_blind_rotate(c->cfg, 1, a, wpb, c->num_cus, c->opts, st, &ln->last));
+      RS_HIP(rs::launch_blind_rotate(c->cfg, 1, a, c->num_cus, c->opts, st, &ln->last));
     }
     unsigned long long limit_bits;
     const double lim = rs::diag::kWrongOnPurpose ? 1e300 : c->cert_limit;   // (timing probes of diagnostic builds: never recompute)
@@ -345,11 +336,11 @@ int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, 
       a.gate_flag = slot; a.gate_limit_bits = limit_bits;
       a.running_flag = k == 0 ? ln->d_cert + kCertSlots : nullptr;
       a.fallback_count = k == 0 ? ln->d_cert + kCertSlots + 1 : nullptr;
-      RS_HIP(rs::launch_blind_rotate(c->cfg, 0, a, wpb, c->num_cus, c->opts, st, nullptr));
+      RS_HIP(rs::launch_blind_rotate(c->cfg, 0, a, c->num_cus, c->opts, st, nullptr));
     }
   } else {
     for (int k = 0; k < count; ++k)
-      RS_HIP(rs::launch_blind_rotate(c->cfg, 0, br_args(c, ln, 0, cs[k], mu, lut, B), wpb, c->num_cus, c->opts, st, &ln->last));
+      RS_HIP(rs::launch_blind_rotate(c->cfg, 0, br_args(c, ln, 0, cs[k], mu, lut, B), c->num_cus, c->opts, st, &ln->last));
   }
   if (c->timing) RS_HIP(hipEventRecord(ln->ev[1], st));
   if (out) {

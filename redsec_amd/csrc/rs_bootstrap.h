@@ -394,27 +394,44 @@ __device__ __forceinline__ void mac_half_stream(double (&s0)[kRegs], double (&s1
 // Launch helpers that cross the units
 // -------------------------------------------------------------------------------------------------
 // Which transform policies have a blind_rotate_coop8_listed_kernel (rs_bootstrap_listed.hip, which static_asserts that it
-// instantiates exactly these): the cfg id launch_coop8_listed takes, or -1 -- launch_br_xf then runs blind_rotate_coop8_kernel.
+// instantiates exactly these): the cfg id launch_coop8_listed takes, or -1 -- the plan then names blind_rotate_coop8_kernel.
 template <class Xf> inline constexpr int kCoop8ListedCfg = -1;
 template <> inline constexpr int kCoop8ListedCfg<XfFft<CfgDefault128>> = 0;
 hipError_t launch_coop8_listed(int cfg, const BlindRotateArgs& a, hipStream_t st);                  // rs_bootstrap_listed.hip
 // the split duo form's launch (mid-size batches of the split mode): rs_bootstrap.hip, called from rs_bootstrap_split.hip
 hipError_t launch_split_duos(int cfg, const BlindRotateArgs& a, long grid, hipStream_t st);
 
-// XCD cohorts of the lock-step kernels (cohort_step, rs_cohort.h): the ONLY place that hands a kernel a progress table. Every
-// launch path starts from arguments whose `progress` is null and calls this for the launches that may use one: those whose
-// workgroups sweep the key more than once (groups > grid), on a device whose workgroups are dealt round-robin over EIGHT XCDs --
-// the protocol's xcd = blockIdx & 7. The one MI355X configuration that is true for is the whole chip as one partition (SPX,
-// 256 CUs = 8 x 32); under CPX / DPX / QPX partitions a table row would mix workgroups served by different L2s, which
-// could only wait for each other with no L2 to share, so there the workgroups run free. `step_bytes` = key bytes a CMUX step
-// reads; the lag keeps a cohort inside about a third of its XCD's 4 MB L2.
-inline hipError_t cohort_setup(BlindRotateArgs& w, int* table, long step_bytes, long groups, long grid, long num_cus, const LaunchOpts& o, hipStream_t st) {
-  w.progress = nullptr; w.cohort_every = 0; w.cohort_lag = 0;
-  if (!table || o.no_cohort || num_cus != 256 || grid > 8L * kCohortSlots || groups <= grid) return hipSuccess;
-  w.cohort_lag = (int32_t)std::max<long>(1, (4L << 20) / 3 / step_bytes - 1);
-  w.cohort_every = w.cohort_lag >= 4 ? 2 : 1;
-  w.progress = table;
+// The compile-time facts of a policy that the launch plan depends on (rs_launch_plan.h never sees the policy types).
+template <class Xf>
+constexpr FormTraits form_traits(bool split = false) {
+  return {Xf::kWorkgroupForm, Xf::Cfg::L, std::is_same_v<typename Xf::Cfg, CfgRedsecV2>, split ? -1 : kCoop8ListedCfg<Xf>, split};
+}
+
+// The caller's arguments cut down to the rows of one step of the plan. No table and no counter: cohort_setup and
+// counter_setup below are the ONLY places that hand a kernel a progress table or a work counter.
+inline BlindRotateArgs step_args(const BlindRotateArgs& whole, const LaunchStep& s) {
+  BlindRotateArgs a = whole;
+  a.B = s.rows;
+  a.in0 += s.first * a.W;
+  if (a.in1) a.in1 += s.first * a.W;
+  a.u_out += s.first * (kN + 1);
+  if (a.lut) a.lut_first = (int32_t)((a.lut_first + s.first) % a.lut_count);
+  a.progress = nullptr; a.cohort_every = 0; a.cohort_lag = 0;
+  a.counter = nullptr;                       // every wave has exactly one ciphertext
+  return a;
+}
+// XCD cohorts of the lock-step kernels (cohort_step, rs_cohort.h), where the plan says so: the table filled with "absent".
+inline hipError_t cohort_setup(BlindRotateArgs& w, int* table, const LaunchStep& s, hipStream_t st) {
+  if (!s.cohort) return hipSuccess;
+  w.progress = table; w.cohort_every = s.cohort_every; w.cohort_lag = s.cohort_lag;
   return hipMemsetAsync(table, 0x7f, 8 * kCohortSlots * sizeof(int), st);
+}
+// The work counter of a persistent per-wave launch, zeroed on the stream.
+inline hipError_t counter_setup(BlindRotateArgs& w, unsigned int* counter, const LaunchStep& s, hipStream_t st) {
+  if (!s.persistent) return hipSuccess;
+  if (!counter) return hipErrorInvalidValue;   // (a context created without one plans with no_persist)
+  w.counter = counter;
+  return hipMemsetAsync(counter, 0, sizeof(unsigned int), st);
 }
 
 }  // namespace rs

@@ -1034,135 +1034,52 @@ __global__ __launch_bounds__(64 * WPB) void polymul_kernel(const int32_t* __rest
 // -------------------------------------------------------------------------------------------------
 // Launchers. cfg: 0 = default-128-shaped gadget, 1 = REDsec-shaped; mode: 0 = exact NTT, 1 = FFT.
 // -------------------------------------------------------------------------------------------------
-template <class Xf, int WPB>
-static hipError_t launch_br(const BlindRotateArgs& a, long max_blocks, hipStream_t st) {
-  long blocks = (a.B + WPB - 1) / WPB;
-  BlindRotateArgs args = a;
-  if (a.counter && blocks > max_blocks) {
-    blocks = max_blocks;                       // persistent: one workgroup per CU, waves pull work
-    hipError_t e = hipMemsetAsync(a.counter, 0, sizeof(unsigned int), st);
-    if (e != hipSuccess) return e;
-  } else {
-    args.counter = nullptr;                    // every wave has exactly one ciphertext
-  }
-  hipLaunchKernelGGL((blind_rotate_kernel<Xf, WPB>), dim3((unsigned)blocks), dim3(64 * WPB), 0, st, args);
-  return hipGetLastError();
-}
-
+// One step of a plan -> its kernel instantiation. `if constexpr` only keeps a kernel from being instantiated for a policy the plan
+// never names it for; such a step (the plan and form_traits disagree) is an error.
 template <class Xf>
-static hipError_t launch_br_xf(const BlindRotateArgs& a_in, int wpb, long num_cus, bool coop4, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
-  int* const cohort_table = a_in.progress;   // the caller's offer; only cohort_setup puts it back into a launch's arguments
-  BlindRotateArgs a = a_in;
-  a.progress = nullptr; a.cohort_every = 0; a.cohort_lag = 0;
-  constexpr long kStepBytes = 2L * Xf::Cfg::L * 16384;   // a CMUX step reads 2l rows of 16 KB
-  LaunchInfo li;
-  auto done = [&](int form, int w, long resident) {
-    li.form = form; li.waves_per_block = w; li.resident = resident;
-    if (info) *info = li;
+static hipError_t dispatch_br(const LaunchStep& s, const BlindRotateArgs& a, hipStream_t st) {
+  constexpr FormTraits t = form_traits<Xf>();
+  constexpr bool kWg = Xf::kWorkgroupForm, kOdd = Xf::Cfg::L % 2 != 0;
+  auto run = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)s.grid), dim3((unsigned)s.block), 0, st, a);
     return hipGetLastError();
   };
-  // latency form: several waves per ciphertext while the batch cannot fill the chip by itself
-  if (!o.no_coop) {
-    if constexpr (Xf::kWorkgroupForm) {
-      // at most one ciphertext per CU: eight waves share it (two per SIMD), see blind_rotate_coop8_kernel
-      if (!o.no_coop8 && a.B <= num_cus) {
-        if constexpr (kCoop8ListedCfg<Xf> >= 0) {   // an object of its own: rs_bootstrap_listed.hip
-          if (!o.no_coop8_listed && a.n <= kCoop8MaxSteps) {
-            if (hipError_t e = launch_coop8_listed(kCoop8ListedCfg<Xf>, a, st); e != hipSuccess) return e;
-            return done(kFormCoop8Listed, 8, 1);
-          }
-        }
-        hipLaunchKernelGGL((blind_rotate_coop8_kernel<Xf>), dim3((unsigned)a.B), dim3(512), 0, st, a);
-        return done(kFormCoop8, 8, 1);
-      }
-    }
-    if (coop4 && a.B <= num_cus) {
-      if constexpr ((2 * Xf::Cfg::L) % 4 == 0) {
-        hipLaunchKernelGGL((blind_rotate_coop_kernel<Xf, 4>), dim3((unsigned)a.B), dim3(256), 0, st, a);
-        return done(kFormCoop4, 4, 1);
-      }
-    }
-    if (a.B <= 2L * num_cus) {
-      hipLaunchKernelGGL((blind_rotate_coop_kernel<Xf, 2>), dim3((unsigned)a.B), dim3(128), 0, st, a);
-      return done(kFormCoop2, 2, 1);
-    }
+  switch (plan_key(s.form, s.waves)) {
+    case plan_key(kFormCoop8Listed, 8): if constexpr (t.listed_cfg >= 0) return launch_coop8_listed(t.listed_cfg, a, st); break;   // rs_bootstrap_listed.hip
+    case plan_key(kFormCoop8, 8): if constexpr (kWg) return run(blind_rotate_coop8_kernel<Xf>); break;
+    case plan_key(kFormCoop4, 4): if constexpr ((2 * t.L) % 4 == 0) return run(blind_rotate_coop_kernel<Xf, 4>); break;
+    case plan_key(kFormCoop2, 2): return run(blind_rotate_coop_kernel<Xf, 2>);
+    case plan_key(kFormWorkgroup, 8): if constexpr (kWg) return run(blind_rotate_wg_kernel<Xf, 8>); break;
+    case plan_key(kFormWorkgroup, 4): if constexpr (kWg && kOdd) return run(blind_rotate_wg_kernel<Xf, 4>); break;
+    case plan_key(kFormDuo, 8): if constexpr (kWg && !kOdd) return run(blind_rotate_duo_kernel<Xf>); break;
+    case plan_key(kFormPerWave, 1): return run(blind_rotate_kernel<Xf, 1>);
+    case plan_key(kFormPerWave, 2): return run(blind_rotate_kernel<Xf, 2>);
+    case plan_key(kFormPerWave, 4): return run(blind_rotate_kernel<Xf, 4>);
+    case plan_key(kFormPerWave, 8): return run(blind_rotate_kernel<Xf, 8>);
   }
-  if constexpr (Xf::kWorkgroupForm) {
-    // throughput form: lock-step workgroups of 8 ciphertexts, key rows shared in LDS. Taken as soon as the batch exceeds
-    // FOUR ciphertexts per CU: a partly filled single round of it (10.2 ms for up to 2,048 default-128 ciphertexts) beats two
-    // rounds of the half-size forms (12.8-13.1 ms at 1,536; tools/midsize_rate.py).
-    if (!o.no_wg && a.B > 4L * num_cus) {
-      // The grid walks the batch in rounds of 8 x #CUs ciphertexts. A last round of at most 4 x #CUs of them is cut off
-      // and runs in the form that batch size would take by itself (cooperative / duo / half-size groups: 3.1-8.2 ms against
-      // 14.8 ms for a whole round of the REDsec set, tools/midsize_rate.py); every ciphertext is independent of the split.
-      const long cap = 8L * num_cus, tail = a.B % cap;
-      if (!o.no_tail && a.B > cap && tail > 0 && tail <= 4L * num_cus) {
-        BlindRotateArgs m = a, t = a;
-        m.B = a.B - tail;
-        t.B = tail;
-        t.in0 = a.in0 + m.B * a.W;
-        if (a.in1) t.in1 = a.in1 + m.B * a.W;
-        t.u_out = a.u_out + m.B * (kN + 1);
-        if (a.lut) t.lut_first = (int32_t)((a.lut_first + m.B) % a.lut_count);
-        if (hipError_t ce = cohort_setup(m, cohort_table, kStepBytes, m.B / 8, num_cus, num_cus, o, st); ce != hipSuccess) return ce;
-        hipLaunchKernelGGL((blind_rotate_wg_kernel<Xf, 8>), dim3((unsigned)num_cus), dim3(512), 0, st, m);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;   // (t, the cut-off last round, runs in a form without cohorts: its progress is null)
-        e = launch_br_xf<Xf>(t, wpb, num_cus, coop4, o, st, nullptr);
-        if (e != hipSuccess) return e;
-        return done(kFormWorkgroup, 8, 8 * num_cus);
-      }
-      const long groups = (a.B + 7) / 8;
-      const long grid = groups < num_cus ? groups : num_cus;
-      BlindRotateArgs w = a;
-      if (hipError_t e = cohort_setup(w, cohort_table, kStepBytes, groups, grid, num_cus, o, st); e != hipSuccess) return e;
-      hipLaunchKernelGGL((blind_rotate_wg_kernel<Xf, 8>), dim3((unsigned)grid), dim3(512), 0, st, w);
-      return done(kFormWorkgroup, 8, 8 * grid);   // the workgroups sweep the key together: 8 x grid ciphertexts per sweep
-    }
-  }
-  if constexpr (Xf::kWorkgroupForm && Xf::Cfg::L % 2 != 0) {
-    // odd l (no duo form), 2 x #CUs < B <= 4 x #CUs: half-size lock-step groups, 4 ciphertexts x 1 wave per workgroup = one
-    // wave per SIMD, which delivers 78 % of the full form's rate per CU and shares the key rows (2-3 % faster than the
-    // per-wave kernel, which streams them per wave)
-    if (!o.no_wg && !o.no_wg4 && a.B > 2L * num_cus) {
-      const long groups = (a.B + 3) / 4;
-      const long grid = groups < num_cus ? groups : num_cus;
-      hipLaunchKernelGGL((blind_rotate_wg_kernel<Xf, 4>), dim3((unsigned)grid), dim3(256), 0, st, a);
-      return done(kFormWorkgroup, 4, 4 * grid);
-    }
-  }
-  if constexpr (Xf::kWorkgroupForm && Xf::Cfg::L % 2 == 0) {
-    // mid-size batches: 4 ciphertexts x 2 waves per workgroup (no_duo falls back to one wave per ciphertext). The kernel keeps the
-    // mod-switched mask words of a ciphertext in LDS, s_bara[4][kSmall]: a key with more steps runs one wave per ciphertext.
-    if (!o.no_wg && !o.no_duo && a.n <= kSmall && a.B > 2L * num_cus) {
-      const long groups = (a.B + 3) / 4;
-      const long grid = groups < num_cus ? groups : num_cus;
-      hipLaunchKernelGGL((blind_rotate_duo_kernel<Xf>), dim3((unsigned)grid), dim3(512), 0, st, a);
-      return done(kFormDuo, 8, 4 * grid);
-    }
-  }
-  hipError_t e;
-  switch (wpb) {
-    case 1: e = launch_br<Xf, 1>(a, 1L << 40, st); break;
-    case 2: e = launch_br<Xf, 2>(a, 1L << 40, st); break;
-    case 4: e = launch_br<Xf, 4>(a, 1L << 40, st); break;
-    default: wpb = 8; e = launch_br<Xf, 8>(a, num_cus, st); break;   // ~150 KB LDS: exactly one workgroup per CU
-  }
-  const long waves = a.B < (long)wpb * num_cus ? a.B : (long)wpb * num_cus;
-  li.form = kFormPerWave; li.waves_per_block = wpb; li.resident = waves;   // waves drift apart: an upper bound on key sharing
-  if (info) *info = li;
-  return e;
+  return hipErrorInvalidValue;
 }
 
-hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int wpb, int num_cus, const LaunchOpts& opts, hipStream_t st,
-                               LaunchInfo* info) {
+// Plan (rs_launch_plan.h: every threshold lives there), then per step: slice the arguments, zero what the step needs, dispatch.
+template <class Xf>
+static hipError_t launch_br_xf(const BlindRotateArgs& whole, int num_cus, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
+  const LaunchPlan plan = plan_blind_rotate(form_traits<Xf>(), whole.n, whole.B, num_cus, o, whole.progress != nullptr);
+  for (int k = 0; k < plan.steps; ++k) {
+    BlindRotateArgs a = step_args(whole, plan.step[k]);
+    if (hipError_t e = cohort_setup(a, whole.progress, plan.step[k], st); e != hipSuccess) return e;
+    if (hipError_t e = counter_setup(a, whole.counter, plan.step[k], st); e != hipSuccess) return e;
+    if (hipError_t e = dispatch_br<Xf>(plan.step[k], a, st); e != hipSuccess) return e;
+  }
+  if (info) *info = plan.info;
+  return hipSuccess;
+}
+
+hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int num_cus, const LaunchOpts& opts, hipStream_t st, LaunchInfo* info) {
   if (a.B <= 0) return hipSuccess;
   if (mode == 0) {
-    return cfg == 0 ? launch_br_xf<XfNtt<CfgDefault128>>(a, wpb, num_cus, false, opts, st, info)
-                    : launch_br_xf<XfNtt<CfgRedsecV2>>(a, wpb, num_cus, true, opts, st, info);
+    return cfg == 0 ? launch_br_xf<XfNtt<CfgDefault128>>(a, num_cus, opts, st, info) : launch_br_xf<XfNtt<CfgRedsecV2>>(a, num_cus, opts, st, info);
   }
-  return cfg == 0 ? launch_br_xf<XfFft<CfgDefault128>>(a, wpb, num_cus, false, opts, st, info)
-                  : launch_br_xf<XfFft<CfgRedsecV2>>(a, wpb, num_cus, true, opts, st, info);
+  return cfg == 0 ? launch_br_xf<XfFft<CfgDefault128>>(a, num_cus, opts, st, info) : launch_br_xf<XfFft<CfgRedsecV2>>(a, num_cus, opts, st, info);
 }
 
 // The split duo form's launch (mid-size batches of the split mode): called from rs_bootstrap_split.hip.

@@ -356,60 +356,36 @@ __global__ __launch_bounds__(64 * G) void blind_rotate_coops_kernel(BlindRotateA
 // -------------------------------------------------------------------------------------------------
 // Split-key workgroup form (N = 1024; cfg 0 / 1 = the two shipped gadgets, 2 = redsec_params_small's l=3 Bgbit=10): a.bk_x = the split key of rs_general.h,
 // a.tw = the FFT tables of rs_fft.h. Returns hipErrorNotSupported for an unknown gadget id (caller: general kernel).
-hipError_t launch_blind_rotate_split_wg(int cfg, const BlindRotateArgs& a_in, int num_cus, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
-  int* const cohort_table = a_in.progress;   // the caller's offer; only cohort_setup puts it back into a launch's arguments
-  BlindRotateArgs a = a_in;
-  a.progress = nullptr; a.cohort_every = 0; a.cohort_lag = 0;
-  // any batch size: even a single group of it walks its CMUX chain in 57 us per step (REDsec set) against the 92 us of a lone
-  // wave of the general kernel (sign1024x1 in split mode: 65.7 -> 40 ms). Up to 4 ciphertexts per CU the groups are 4 waves:
-  // one wave per SIMD on twice the CUs.
-  auto coop = [&](auto c) {
-    using C = decltype(c);
-    LaunchInfo li;
-    li.form = kFormSplitCoop; li.resident = 1;
-
-    if constexpr ((2 * C::L) % 4 == 0) {
-      if (a.B <= num_cus) {
-        hipLaunchKernelGGL((blind_rotate_coops_kernel<C, 4>), dim3((unsigned)a.B), dim3(256), 0, st, a);
-        li.waves_per_block = 4;
-        if (info) *info = li;
-        return hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((blind_rotate_coops_kernel<C, 2>), dim3((unsigned)a.B), dim3(128), 0, st, a);
-    li.waves_per_block = 2;
-    if (info) *info = li;
-    return hipGetLastError();
-  };
-  if (!o.no_coop && a.B <= 2L * num_cus) {   // latency form: several waves per ciphertext, as in the unsplit modes
-    if (cfg == 0) return coop(CfgDefault128{});
-    if (cfg == 1) return coop(CfgRedsecV2{});
-    if (cfg == 2) return coop(CfgRedsecSmall{});
-    return hipErrorNotSupported;
+// The plan's one step (rs_launch_plan.h: the split forms have no cut-off last round) -> its kernel instantiation.
+template <class C>
+static hipError_t launch_split(int cfg, const BlindRotateArgs& whole, int num_cus, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
+  const LaunchPlan plan = plan_blind_rotate(form_traits<XfFft<C>>(true), whole.n, whole.B, num_cus, o, whole.progress != nullptr);
+  const LaunchStep& s = plan.step[0];
+  BlindRotateArgs a = step_args(whole, s);
+  if (hipError_t e = cohort_setup(a, whole.progress, s, st); e != hipSuccess) return e;
+  auto run = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)s.grid), dim3((unsigned)s.block), 0, st, a); };
+  switch (plan_key(s.form, s.waves)) {
+    case plan_key(kFormSplitCoop, 4):
+      if constexpr ((2 * C::L) % 4 == 0) { run(blind_rotate_coops_kernel<C, 4>); break; }
+      return hipErrorInvalidValue;
+    case plan_key(kFormSplitCoop, 2): run(blind_rotate_coops_kernel<C, 2>); break;
+    case plan_key(kFormSplitDuo, 8):   // built with rs_bootstrap.hip
+      if (hipError_t e = launch_split_duos(cfg, a, s.grid, st); e != hipSuccess) return e;
+      break;
+    // (8 before 4: the order of instantiation is worth an instruction in each of these kernels; tools/codeobj_digest.py)
+    case plan_key(kFormSplitWorkgroup, 8): run(blind_rotate_wgs_kernel<C, 8>); break;
+    case plan_key(kFormSplitWorkgroup, 4): run(blind_rotate_wgs_kernel<C, 4>); break;
+    default: return hipErrorInvalidValue;
   }
-  if (!o.no_duo && a.B <= 4L * num_cus) {   // mid-size batches: 4 ciphertexts x 2 waves per workgroup (no_duo: the 4-wave lock-step groups)
-    const long grid = std::min<long>((a.B + 3) / 4, num_cus);
-    if (cfg < 0 || cfg > 2) return hipErrorNotSupported;
-    if (info) { info->form = kFormSplitDuo; info->waves_per_block = 8; info->resident = 4 * grid; }
-    return launch_split_duos(cfg, a, grid, st);
-  }
-  const int wpb = (a.B <= 4L * num_cus && !o.no_wg4) ? 4 : 8;
-  const long groups = (a.B + wpb - 1) / wpb;
-  const long grid = groups < num_cus ? groups : num_cus;
-  BlindRotateArgs w = a;
-  // a CMUX step reads 2 * 2l half-rows of 16 KB
-  if (hipError_t e = cohort_setup(w, cohort_table, 4L * (cfg == 1 ? 10 : 3) * 16384, groups, grid, num_cus, o, st); e != hipSuccess) return e;
-  auto go = [&](auto c) {
-    using C = decltype(c);
-    if (wpb == 8) hipLaunchKernelGGL((blind_rotate_wgs_kernel<C, 8>), dim3((unsigned)grid), dim3(512), 0, st, w);
-    else hipLaunchKernelGGL((blind_rotate_wgs_kernel<C, 4>), dim3((unsigned)grid), dim3(256), 0, st, w);
-  };
-  if (cfg == 0) go(CfgDefault128{});
-  else if (cfg == 1) go(CfgRedsecV2{});
-  else if (cfg == 2) go(CfgRedsecSmall{});
-  else return hipErrorNotSupported;
-  if (info) { info->form = kFormSplitWorkgroup; info->waves_per_block = wpb; info->resident = wpb * grid; }
+  if (info) *info = plan.info;
   return hipGetLastError();
+}
+
+hipError_t launch_blind_rotate_split_wg(int cfg, const BlindRotateArgs& a, int num_cus, const LaunchOpts& o, hipStream_t st, LaunchInfo* info) {
+  if (cfg == 0) return launch_split<CfgDefault128>(cfg, a, num_cus, o, st, info);
+  if (cfg == 1) return launch_split<CfgRedsecV2>(cfg, a, num_cus, o, st, info);
+  if (cfg == 2) return launch_split<CfgRedsecSmall>(cfg, a, num_cus, o, st, info);
+  return hipErrorNotSupported;
 }
 
 }  // namespace rs

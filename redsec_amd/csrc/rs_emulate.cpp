@@ -15,6 +15,7 @@
 #include "rs_general.h"
 #include "rs_host.h"
 #include "rs_keygen.h"
+#include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
 #include "rs_ntt.h"
 
@@ -1092,6 +1093,23 @@ long rs_emu_exchange_plan(long rows, int n, const int* devices, const unsigned c
     out[6 * i + 4] = (long)ops[i].lo; out[6 * i + 5] = (long)ops[i].hi;
   }
   return (long)ops.size();
+}
+// the launches of a blind-rotation batch (rs_launch_plan.h). traits: (workgroup_form, L, coop4, listed_cfg, split); switches: bits, in
+// this order, of no_coop, no_wg, no_duo, no_persist, no_wg4, no_tail, no_coop8, no_coop8_listed, no_cohort. out: the reported
+// (form, waves, resident), then per step (form, waves, grid, block, first, rows, persistent, cohort, every, lag); returns the steps
+long rs_emu_launch_plan(const int* traits, int n, long B, int num_cus, unsigned switches, int cohort_table_offered, long* out) {
+  const rs::FormTraits t{traits[0] != 0, traits[1], traits[2] != 0, traits[3], traits[4] != 0};
+  rs::LaunchOpts o;
+  bool* const bits[9] = {&o.no_coop, &o.no_wg, &o.no_duo, &o.no_persist, &o.no_wg4, &o.no_tail, &o.no_coop8, &o.no_coop8_listed, &o.no_cohort};
+  for (int k = 0; k < 9; ++k) *bits[k] = (switches >> k) & 1;
+  const rs::LaunchPlan p = rs::plan_blind_rotate(t, n, B, num_cus, o, cohort_table_offered != 0);
+  out[0] = p.info.form; out[1] = p.info.waves_per_block; out[2] = p.info.resident;
+  for (int k = 0; k < p.steps; ++k) {
+    const rs::LaunchStep& s = p.step[k];
+    const long row[10] = {s.form, s.waves, s.grid, s.block, s.first, s.rows, s.persistent, s.cohort, s.cohort_every, s.cohort_lag};
+    std::copy(row, row + 10, out + 3 + 10 * k);
+  }
+  return p.steps;
 }
 // measured transform errors (see GenEmu::transform_error_ratios) and the analysis' per-transform bounds g_f - 1, g_i - 1
 int rs_emu_gen_transform_errors(int logn, uint64_t seed, int amplitude, double* measured2, double* bounds2) {

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "rs_launch_plan.h"
 #include "rs_ntt.h"
 
 namespace rs {
@@ -44,16 +45,7 @@ struct BlindRotateArgs {
   int* progress = nullptr;
   int32_t cohort_every = 0, cohort_lag = 0;
 };
-constexpr int kCohortSlots = 64;   // workgroups per XCD the table has room for (256 CUs / 8 XCDs = 32)
-
-// Launch policy switches, read from the environment ONCE at rs_create (A/B experiments only).
-struct LaunchOpts {
-  bool no_coop = false, no_wg = false, no_duo = false, no_persist = false, no_conv_tiled = false, no_wg4 = false, no_tail = false, no_coop8 = false, no_coop8_listed = false, ks_atomics = false, force_host_staged = false, no_cohort = false;
-};
-// What a blind-rotate launch actually ran: kernel form and how many ciphertexts share one sweep of the key
-// from L2/HBM (R of SURVEY.md section 8d).
-enum { kFormPerWave = 0, kFormWorkgroup = 1, kFormDuo = 2, kFormCoop2 = 3, kFormCoop4 = 4, kFormGeneral = 5, kFormSplitWorkgroup = 6, kFormSplitCoop = 7, kFormSplitDuo = 8, kFormCoop8 = 9, kFormCoop8Listed = 10 };
-struct LaunchInfo { int form = -1; int waves_per_block = 0; long resident = 0; };
+// (LaunchOpts, the kForm* ids, LaunchInfo and kCohortSlots: rs_launch_plan.h)
 
 struct KeyswitchArgs {
   const int32_t* u0;    // [B][N+1]
@@ -92,8 +84,8 @@ struct ConvShape { int32_t H, Wd, Cin, Cout, fh, fw, stride_h, stride_w, off_h, 
 struct PoolShape { int32_t H, Wd, C, win_h, win_w, stride_h, stride_w, off_h, off_w, Ho, Wo; };
 
 // cfg: 0 = CfgDefault128 (l=3, Bgbit=7), 1 = CfgRedsecV2 (l=10, Bgbit=3); mode: 0 = exact NTT, 1 = FFT
-hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int waves_per_block, int num_cus, const LaunchOpts& opts,
-                               hipStream_t st, LaunchInfo* info = nullptr);
+hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int num_cus, const LaunchOpts& opts, hipStream_t st,
+                               LaunchInfo* info = nullptr);
 hipError_t launch_blind_rotate_split_wg(int cfg, const BlindRotateArgs& a, int num_cus, const LaunchOpts& opts, hipStream_t st, LaunchInfo* info);
 hipError_t launch_bk_transform(int cfg, int mode, const int32_t* bk, double* bk_x, const double* tw, Field f, double scale,
                                long n_polys, hipStream_t st);

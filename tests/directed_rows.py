@@ -109,7 +109,8 @@ FORMS = ["per_wave", "workgroup", "duo", "coop2", "coop4", "general", "split_wor
 
 def geometry(form, B, cus, group=None, sweep=None):
     """(rows per workgroup, rows per sweep of a persistent grid or None, first row of a cut-off tail launch or None) of a launch
-    of `form` on B rows -- the launchers' rules (rs_bootstrap.hip, rs_bootstrap_split.hip, rs_api.cpp pick_wpb) restated."""
+    of `form` on B rows -- the rules of the launch plan (redsec_amd/csrc/rs_launch_plan.h) restated independently: its second
+    opinion (tests/test_directed_cpu.py compares the two)."""
     cut = None
     if form in ("coop2", "coop4", "coop8", "coop8_listed", "split_coop"):
         g, s = 1, None                            # one ciphertext per workgroup, its waves share it
@@ -153,3 +154,89 @@ def positions_for(form, B, cus, group=None, sweep=None):
     if g == 1:
         pos.add(B // 2)                           # one ciphertext per workgroup: a workgroup in the middle of the grid as well
     return sorted(pos)
+
+
+# ---- the launch cases: (switches set while the context is created, batch size in units of (#CUs, rows), form, waves) ----
+def _B(cus, spec):
+    return spec[0] * cus + spec[1]
+
+
+BMAX = (8, 11)              # 8 x #CUs + 11: a second sweep of the persistent grids, and a tail of 11 rows that is cut off
+FFT_CASES = [
+    # id, fixture, switches, B, form, waves per workgroup, rows per sweep in #CUs (0: one row per workgroup)
+    ("d-listed", "toy_default", (), (1, 0), "coop8_listed", 8, 0),
+    ("d-listed-few", "toy_default", (), (0, 9), "coop8_listed", 8, 0),
+    ("d-coop8", "toy_default", ("RS_NO_COOP8_LISTED",), (1, 0), "coop8", 8, 0),
+    ("d-coop2", "toy_default", (), (1, 3), "coop2", 2, 0),
+    ("d-wg4", "toy_default", (), (3, 2), "workgroup", 4, 4),
+    ("d-wg8", "toy_default", (), (6, 5), "workgroup", 8, 8),
+    ("d-tail", "toy_default", (), BMAX, "workgroup", 8, 8),
+    ("d-sweeps", "toy_default", ("RS_NO_TAIL",), BMAX, "workgroup", 8, 8),
+    ("d-perwave-persistent", "toy_default", ("RS_NO_WG",), BMAX, "per_wave", 8, None),
+    ("d-perwave-nopersist", "toy_default", ("RS_NO_WG", "RS_NO_PERSIST"), BMAX, "per_wave", 8, None),
+    ("d-perwave-2", "toy_default", ("RS_NO_WG4",), (3, 2), "per_wave", 2, None),
+    ("d-perwave-1", "toy_default", ("RS_NO_COOP",), (1, 3), "per_wave", 1, None),
+    ("r-coop8", "toy_redsec", (), (1, 0), "coop8", 8, 0),
+    ("r-coop4", "toy_redsec", ("RS_NO_COOP8",), (1, 0), "coop4", 4, 0),
+    ("r-coop2", "toy_redsec", (), (1, 3), "coop2", 2, 0),
+    ("r-duo", "toy_redsec", (), (3, 2), "duo", 8, 4),
+    ("r-perwave-2", "toy_redsec", ("RS_NO_DUO",), (3, 2), "per_wave", 2, None),
+    ("r-wg8", "toy_redsec", (), (6, 5), "workgroup", 8, 8),
+    ("r-tail", "toy_redsec", (), BMAX, "workgroup", 8, 8),
+    ("r-sweeps", "toy_redsec", ("RS_NO_TAIL",), BMAX, "workgroup", 8, 8),
+    ("r-perwave-persistent", "toy_redsec", ("RS_NO_WG",), BMAX, "per_wave", 8, None),
+]
+EXACT_CASES = [
+    ("d-exact-coop2", "toy_default", (), (1, 3), "coop2", 2, 0),
+    ("d-exact-perwave", "toy_default", (), BMAX, "per_wave", 8, None),
+    ("r-exact-coop4", "toy_redsec", (), (1, 0), "coop4", 4, 0),
+    ("r-exact-coop2", "toy_redsec", (), (1, 3), "coop2", 2, 0),
+    ("r-exact-perwave-4", "toy_redsec", (), (6, 5), "per_wave", 4, None),
+    ("r-exact-perwave", "toy_redsec", (), BMAX, "per_wave", 8, None),
+]
+SPLIT_CASES = [
+    ("d-split-coop", "toy_default", (), (1, 0), "split_coop", 2, 0),
+    ("d-split-duo", "toy_default", (), (3, 2), "split_duo", 8, 4),
+    ("d-split-wg4", "toy_default", ("RS_NO_DUO",), (3, 2), "split_workgroup", 4, 4),
+    ("d-split-wg8", "toy_default", (), (6, 5), "split_workgroup", 8, 8),
+    ("d-split-sweeps", "toy_default", (), BMAX, "split_workgroup", 8, 8),
+    ("r-split-coop4", "toy_redsec", (), (1, 0), "split_coop", 4, 0),
+    ("r-split-coop2", "toy_redsec", (), (1, 3), "split_coop", 2, 0),
+    ("r-split-duo", "toy_redsec", (), (3, 2), "split_duo", 8, 4),
+    ("r-split-wg4", "toy_redsec", ("RS_NO_DUO",), (3, 2), "split_workgroup", 4, 4),
+    ("r-split-wg8", "toy_redsec", (), (6, 5), "split_workgroup", 8, 8),
+    ("r-split-sweeps", "toy_redsec", (), BMAX, "split_workgroup", 8, 8),
+]
+CASES = [(c, "fft") for c in FFT_CASES] + [(c, "exact") for c in EXACT_CASES] + [(c, "split") for c in SPLIT_CASES]
+
+
+def _resident(case, B, cus):
+    """What last_launch() must report as the ciphertexts of one key sweep."""
+    form, waves, per_cu = case[4], case[5], case[6]
+    if per_cu == 0:
+        return 1
+    if per_cu is None:                                   # per-wave kernel: the waves resident at once
+        return min(B, waves * cus)
+    groups = (B + per_cu - 1) // per_cu
+    return per_cu * min(groups, cus)
+
+
+# ---- the launch plan's inputs (redsec_amd/csrc/rs_launch_plan.h through emu_lib.launch_plan) ----
+# FormTraits (workgroup_form, L, coop4, listed_cfg, split) of every (parameter set, mode) the launchers plan for: what
+# form_traits (rs_bootstrap.h) fills in for the policy. test_gpu_directed.py compares the plan under these with the real launch.
+TRAITS = {
+    ("toy_default", "fft"): (1, 3, 0, 0, 0), ("toy_redsec", "fft"): (1, 10, 1, -1, 0),
+    ("toy_default", "exact"): (0, 3, 0, -1, 0), ("toy_redsec", "exact"): (0, 10, 1, -1, 0),
+    ("toy_default", "split"): (1, 3, 0, -1, 1), ("toy_redsec", "split"): (1, 10, 1, -1, 1),
+    ("small_l3_bgbit10", "split"): (1, 3, 0, -1, 1),          # redsec_params_small's gadget: split mode only
+}
+TOY_N = {"toy_default": 24, "toy_redsec": 20}
+# the switches of LaunchOpts that touch the blind rotation, in the bit order rs_emu_launch_plan takes them
+SWITCHES = ["RS_NO_COOP", "RS_NO_WG", "RS_NO_DUO", "RS_NO_PERSIST", "RS_NO_WG4", "RS_NO_TAIL", "RS_NO_COOP8", "RS_NO_COOP8_LISTED",
+            "RS_NO_COHORT"]
+# the batch sizes where some form's rule changes (tools/stress_modes.py walks the same list on the device)
+EDGES = [(0, 1), (0, 2), (1, -1), (1, 0), (1, 1), (2, 0), (2, 1), (4, 0), (4, 1), (8, -1), (8, 0), (8, 1), (12, 5), (16, 3), (24, 0)]
+
+
+def switch_bits(switches):
+    return sum(1 << SWITCHES.index(s) for s in switches)

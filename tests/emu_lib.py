@@ -3,6 +3,7 @@ import ctypes as C
 
 import numpy as np
 
+from directed_rows import FORMS as _FORMS
 from redsec_amd import build as _build
 
 _i32p = C.POINTER(C.c_int32)
@@ -27,8 +28,25 @@ def lib():
         L.rs_emu_gen_digit_mismatches.restype = C.c_long
         L.rs_emu_gen_digit_mismatches.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_long]
         L.rs_emu_gen_polymul.argtypes = [C.c_int, _i32p, _i32p, _i32p, C.POINTER(C.c_double)]
+        L.rs_emu_launch_plan.restype = C.c_long
+        L.rs_emu_launch_plan.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_long, C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_long)]
         _lib = L
     return _lib
+
+
+_STEP = ["form", "waves", "grid", "block", "first", "rows", "persistent", "cohort", "cohort_every", "cohort_lag"]
+
+
+def launch_plan(traits, n, B, cus, switch_bits=0, table_offered=True):
+    """The launches rs_launch_plan.h plans for B rows of n CMUX steps on `cus` compute units -> (info, steps): `info` as
+    Backend.last_launch() reports it, `steps` the one or two launches as dicts. traits: (workgroup_form, L, coop4, listed_cfg, split)."""
+    out = (C.c_long * 23)()
+    count = lib().rs_emu_launch_plan((C.c_int * 5)(*traits), n, B, cus, switch_bits, int(table_offered), out)
+    info = {"form": _FORMS[out[0]], "waves_per_block": out[1], "resident": out[2]}
+    steps = [dict(zip(_STEP, out[3 + 10 * k:13 + 10 * k])) for k in range(count)]
+    for s in steps:
+        s["form"] = _FORMS[s["form"]]
+    return info, steps
 
 
 def gen_polymul(logn, a, b):

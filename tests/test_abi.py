@@ -102,10 +102,10 @@ def test_header_is_plain_c99_and_a_c_program_links(tmp_path):
 
 
 def test_kernel_form_names_of_the_binding_follow_the_library_enum():
-    """rs_last_launch reports a form id (csrc/rs_kernels.h kForm*); backend.Backend.last_launch names it. A form added on one side only
+    """rs_last_launch reports a form id (csrc/rs_launch_plan.h kForm*); backend.Backend.last_launch names it. A form added on one side only
     would index past the list or mislabel a launch."""
     import re
-    text = open(os.path.join(ROOT, "redsec_amd", "csrc", "rs_kernels.h")).read()
+    text = open(os.path.join(ROOT, "redsec_amd", "csrc", "rs_launch_plan.h")).read()
     enum = re.search(r"enum \{ (kFormPerWave = 0[^}]*)\}", text).group(1)
     ids = {name: int(v) for name, v in re.findall(r"(kForm\w+) = (\d+)", enum)}
     assert sorted(ids.values()) == list(range(len(ids)))

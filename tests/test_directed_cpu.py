@@ -1,6 +1,10 @@
 """Directed inputs on the CPU: the rows of tests/directed_rows.py through the lane emulator of the device kernels (exact NTT
 and FFT) against the oracle, word for word; the rounding-distance facts the GPU certificate-coverage tests rest on (a row
-without a CMUX step measures exactly 0.0, a row with one step measures more); and a self-check of positions_for."""
+without a CMUX step measures exactly 0.0, a row with one step measures more); a self-check of positions_for; and the launch plan
+(redsec_amd/csrc/rs_launch_plan.h through the emulator library): the GPU tests' case tables replayed on it and its invariants
+swept over every boundary batch size, with geometry() as its independent second opinion."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -166,3 +170,132 @@ def test_positions_cover_every_slot_and_group_class(cus):
                              "coop8", "coop8_listed"}
     with pytest.raises(KeyError):
         dr.positions_for("no_such_form", 9, cus)
+
+
+# =====================================================================================================================
+# The launch plan
+# =====================================================================================================================
+@pytest.mark.parametrize("cus", [256, 3])
+def test_the_launch_plan_replays_the_case_tables(cus):
+    """test_gpu_directed.py's `last_launch() == want`, made on the CPU: form, waves and resident ciphertexts of every case."""
+    for case, mode in dr.CASES:
+        cid, fixture, switches, bspec, form, waves, _ = case
+        # the tables give "k x #CUs and a few rows more", the few rows as a count that is meant to stay below one per CU (true on
+        # every device the GPU tests see): on the 3-CU model it is cut down to that, or 9 rows alone would be 3 x #CUs
+        B = dr._B(cus, (bspec[0], min(bspec[1], cus - 1)))
+        info, steps = emu_lib.launch_plan(dr.TRAITS[fixture, mode], dr.TOY_N[fixture], B, cus, dr.switch_bits(switches))
+        assert info == {"form": form, "waves_per_block": waves, "resident": dr._resident(case, B, cus)}, (cid, info)
+        assert (steps[0]["form"], steps[0]["waves"]) == (form, waves)
+        assert len(steps) == (2 if cid.endswith("-tail") else 1), cid
+        if cid.endswith("-tail"):                              # the cut-off rows run as a call on exactly those rows would
+            tail = B % (8 * cus)
+            _, alone = emu_lib.launch_plan(dr.TRAITS[fixture, mode], dr.TOY_N[fixture], tail, cus, dr.switch_bits(switches))
+            assert steps[1] == dict(alone[0], first=B - tail) and (alone[0]["form"] in ("coop8", "coop8_listed"))
+        assert steps[0]["persistent"] == (cid.endswith("-perwave-persistent") or cid in ("d-exact-perwave", "r-exact-perwave")), cid
+
+
+_PER_CU = ("workgroup", "duo", "split_workgroup", "split_duo")          # lock-step forms: at most one workgroup per CU
+
+
+def _default_form(traits, n, B, cus):
+    """(form, waves) of the main launch with no switch set, by batch size per CU: DESIGN.md's table of forms, restated."""
+    wg, L, coop4, listed, split = traits
+    four = coop4 and B <= cus
+    if split:
+        return ("split_coop", 4 if four else 2) if B <= 2 * cus else ("split_duo", 8) if B <= 4 * cus else ("split_workgroup", 8)
+    if wg and B <= cus:
+        return ("coop8_listed" if listed >= 0 and n <= 2048 else "coop8", 8)
+    if B <= 2 * cus:
+        return ("coop4", 4) if four else ("coop2", 2)
+    if wg and B > 4 * cus:
+        return ("workgroup", 8)
+    if wg and L % 2 == 1:
+        return ("workgroup", 4)
+    if wg and n <= 640:
+        return ("duo", 8)
+    return ("per_wave", 8 if B >= 8 * cus else 4 if B >= 4 * cus else 2)
+
+
+@pytest.mark.parametrize("cus", [256, 3])
+def test_the_launch_plan_holds_its_invariants_at_every_boundary(cus):
+    used_pairs = {tuple(case[2]) for case, _ in dr.CASES if len(case[2]) == 2}
+    switch_sets = [()] + [(s,) for s in dr.SWITCHES] + sorted(used_pairs)
+    assert ("RS_NO_WG", "RS_NO_PERSIST") in switch_sets
+    seen = set()
+    for (name, mode), traits in sorted(dr.TRAITS.items()):
+        # beside the edge list: the longest tail that is cut off and the shortest that is not
+        for switches, n, edge, offered in itertools.product(switch_sets, (10, 640, 641, 2048, 2049), dr.EDGES + [(12, 0), (12, 1)], (True, False)):
+            B = dr._B(cus, edge)
+            info, steps = emu_lib.launch_plan(traits, n, B, cus, dr.switch_bits(switches), offered)
+            ctx = (name, mode, switches, n, B, steps)
+            main = steps[0]
+            assert (info["form"], info["waves_per_block"]) == (main["form"], main["waves"]), ctx
+            if not switches:
+                assert (main["form"], main["waves"]) == _default_form(traits, n, B, cus), ctx
+            # the steps tile [0, B) exactly once, in order
+            assert len(steps) in (1, 2) and main["first"] == 0 and sum(s["rows"] for s in steps) == B, ctx
+            assert all(s["rows"] > 0 for s in steps) and steps[-1]["first"] == B - steps[-1]["rows"], ctx
+            for s in steps:
+                seen.add((s["form"], s["waves"]))
+                assert s["block"] == 64 * s["waves"] and s["grid"] >= 1, ctx
+                assert s["form"].startswith("split") == (mode == "split") and s["form"] != "general", ctx
+                if s["form"] in _PER_CU or s["persistent"]:
+                    assert s["grid"] <= cus, ctx
+                if s["persistent"]:
+                    assert s["form"] == "per_wave" and s["waves"] == 8 and "RS_NO_PERSIST" not in switches and s["rows"] > 8 * cus, ctx
+                if s["form"] == "coop8_listed":
+                    assert n <= 2048 and traits[3] >= 0, ctx
+                if s["form"] == "duo":
+                    assert n <= 640 and traits[1] % 2 == 0, ctx
+                # every row has a wave (or, persistent / lock-step, a sweep that reaches it)
+                g, sweep, _ = dr.geometry(s["form"], B if s is main else s["rows"], cus)
+                if s["form"] == "per_wave":
+                    assert s["persistent"] or s["grid"] * s["waves"] >= s["rows"], ctx
+                else:
+                    assert s["grid"] == min(-(-s["rows"] // g), cus if s["form"] in _PER_CU else s["rows"]), ctx
+            # second opinion: rows per workgroup, rows per sweep and the cut position
+            g, sweep, cut = dr.geometry(main["form"], B, cus)
+            assert main["waves"] == (g if main["form"] in ("per_wave", "workgroup", "split_workgroup") else main["waves"]), ctx
+            if main["form"] in _PER_CU:
+                assert info["resident"] == g * main["grid"] and (sweep is None or info["resident"] == min(sweep, g * -(-main["rows"] // g))), ctx
+            if main["form"] == "per_wave" and main["persistent"]:
+                assert sweep == main["grid"] * main["waves"] == info["resident"], ctx
+            if "RS_NO_TAIL" not in switches:
+                assert (steps[1]["first"] if len(steps) == 2 else None) == cut, ctx
+            if len(steps) == 2:
+                tail = steps[1]
+                assert main["form"] == "workgroup" and main["waves"] == 8 and B > 8 * cus and 0 < tail["rows"] <= 4 * cus, ctx
+                assert tail["rows"] == B % (8 * cus) and not tail["cohort"] and info["resident"] == 8 * cus, ctx
+            for s in steps:
+                if s["cohort"]:
+                    groups = -(-s["rows"] // s["waves"])
+                    assert cus == 256 and offered and "RS_NO_COHORT" not in switches and groups > s["grid"], ctx
+                    assert s["form"] in ("workgroup", "split_workgroup") and s["cohort_lag"] >= 1 and s["cohort_every"] in (1, 2), ctx
+                    # the lag keeps a cohort within a third of an XCD's 4 MB L2: a step reads 2l rows (split: 4l half-rows) of 16 KB
+                    step_bytes = (4 if mode == "split" else 2) * traits[1] * 16384
+                    assert s["cohort_lag"] == max(1, (4 << 20) // 3 // step_bytes - 1), ctx
+                    assert s["cohort_every"] == (2 if s["cohort_lag"] >= 4 else 1), ctx
+                else:
+                    assert s["cohort_every"] == 0 and s["cohort_lag"] == 0, ctx
+    assert {f for f, _ in seen} == set(dr.FORMS) - {"general"}
+    if cus == 256:                                             # cohorts are planned at all: whole-chip, more groups than grid
+        _, steps = emu_lib.launch_plan(dr.TRAITS["toy_redsec", "split"], 20, 24 * cus, cus)
+        assert steps[0]["cohort"] and (steps[0]["cohort_lag"], steps[0]["cohort_every"]) == (1, 1)
+        _, steps = emu_lib.launch_plan(dr.TRAITS["toy_default", "fft"], 24, 24 * cus, cus)
+        assert steps[0]["cohort"] and (steps[0]["cohort_lag"], steps[0]["cohort_every"]) == (13, 2)
+
+
+@pytest.mark.parametrize("cus", [256, 3])
+def test_a_cut_off_tail_on_the_per_wave_kernel_keeps_eight_waves(cus):
+    """A tail that no latency or half-size form takes runs one wave per ciphertext with the WHOLE batch's eight waves per
+    workgroup (by itself a batch of its size would take 1, 2 or 4) and without the work counter."""
+    for (fixture, extra), tail_rows in itertools.product((("toy_default", "RS_NO_WG4"), ("toy_redsec", "RS_NO_DUO")), (1, cus, 2 * cus + 1, 4 * cus)):
+        B = 8 * cus + tail_rows
+        bits = dr.switch_bits(("RS_NO_COOP", extra))
+        info, steps = emu_lib.launch_plan(dr.TRAITS[fixture, "fft"], dr.TOY_N[fixture], B, cus, bits)
+        assert info == {"form": "workgroup", "waves_per_block": 8, "resident": 8 * cus} and len(steps) == 2
+        tail = steps[1]
+        assert (tail["form"], tail["waves"], tail["block"], tail["persistent"]) == ("per_wave", 8, 512, 0)
+        assert (tail["first"], tail["rows"], tail["grid"]) == (8 * cus, tail_rows, -(-tail_rows // 8))
+        alone, _ = emu_lib.launch_plan(dr.TRAITS[fixture, "fft"], dr.TOY_N[fixture], tail_rows, cus, bits)
+        assert alone["form"] == "per_wave" and alone["waves_per_block"] == (4 if tail_rows >= 4 * cus else 2 if tail_rows >= 2 * cus else 1)

@@ -24,8 +24,11 @@ import numpy as np
 import pytest
 
 import directed_rows as dr
+import emu_lib
 import oracle_lib as ol
 from backend_pool import BackendPool
+# the launch cases and what last_launch() must report for them (the CPU tests replay the same tables on the launch plan)
+from directed_rows import BMAX, CASES, FFT_CASES, _B, _resident
 
 pytestmark = pytest.mark.gpu
 
@@ -80,71 +83,6 @@ def _luts(p, count, rng):
     luts[1, 1::7] = 2**31 - 1
     luts[count - 1, :] = np.where(np.arange(p.N) % 2 == 0, -2**31, 2**31 - 1)
     return luts
-
-
-# ---- the launch cases: (switches set while the context is created, batch size in units of (#CUs, rows), form, waves) ----
-def _B(cus, spec):
-    return spec[0] * cus + spec[1]
-
-
-BMAX = (8, 11)              # 8 x #CUs + 11: a second sweep of the persistent grids, and a tail of 11 rows that is cut off
-FFT_CASES = [
-    # id, fixture, switches, B, form, waves per workgroup, rows per sweep in #CUs (0: one row per workgroup)
-    ("d-listed", "toy_default", (), (1, 0), "coop8_listed", 8, 0),
-    ("d-listed-few", "toy_default", (), (0, 9), "coop8_listed", 8, 0),
-    ("d-coop8", "toy_default", ("RS_NO_COOP8_LISTED",), (1, 0), "coop8", 8, 0),
-    ("d-coop2", "toy_default", (), (1, 3), "coop2", 2, 0),
-    ("d-wg4", "toy_default", (), (3, 2), "workgroup", 4, 4),
-    ("d-wg8", "toy_default", (), (6, 5), "workgroup", 8, 8),
-    ("d-tail", "toy_default", (), BMAX, "workgroup", 8, 8),
-    ("d-sweeps", "toy_default", ("RS_NO_TAIL",), BMAX, "workgroup", 8, 8),
-    ("d-perwave-persistent", "toy_default", ("RS_NO_WG",), BMAX, "per_wave", 8, None),
-    ("d-perwave-nopersist", "toy_default", ("RS_NO_WG", "RS_NO_PERSIST"), BMAX, "per_wave", 8, None),
-    ("d-perwave-2", "toy_default", ("RS_NO_WG4",), (3, 2), "per_wave", 2, None),
-    ("d-perwave-1", "toy_default", ("RS_NO_COOP",), (1, 3), "per_wave", 1, None),
-    ("r-coop8", "toy_redsec", (), (1, 0), "coop8", 8, 0),
-    ("r-coop4", "toy_redsec", ("RS_NO_COOP8",), (1, 0), "coop4", 4, 0),
-    ("r-coop2", "toy_redsec", (), (1, 3), "coop2", 2, 0),
-    ("r-duo", "toy_redsec", (), (3, 2), "duo", 8, 4),
-    ("r-perwave-2", "toy_redsec", ("RS_NO_DUO",), (3, 2), "per_wave", 2, None),
-    ("r-wg8", "toy_redsec", (), (6, 5), "workgroup", 8, 8),
-    ("r-tail", "toy_redsec", (), BMAX, "workgroup", 8, 8),
-    ("r-sweeps", "toy_redsec", ("RS_NO_TAIL",), BMAX, "workgroup", 8, 8),
-    ("r-perwave-persistent", "toy_redsec", ("RS_NO_WG",), BMAX, "per_wave", 8, None),
-]
-EXACT_CASES = [
-    ("d-exact-coop2", "toy_default", (), (1, 3), "coop2", 2, 0),
-    ("d-exact-perwave", "toy_default", (), BMAX, "per_wave", 8, None),
-    ("r-exact-coop4", "toy_redsec", (), (1, 0), "coop4", 4, 0),
-    ("r-exact-coop2", "toy_redsec", (), (1, 3), "coop2", 2, 0),
-    ("r-exact-perwave-4", "toy_redsec", (), (6, 5), "per_wave", 4, None),
-    ("r-exact-perwave", "toy_redsec", (), BMAX, "per_wave", 8, None),
-]
-SPLIT_CASES = [
-    ("d-split-coop", "toy_default", (), (1, 0), "split_coop", 2, 0),
-    ("d-split-duo", "toy_default", (), (3, 2), "split_duo", 8, 4),
-    ("d-split-wg4", "toy_default", ("RS_NO_DUO",), (3, 2), "split_workgroup", 4, 4),
-    ("d-split-wg8", "toy_default", (), (6, 5), "split_workgroup", 8, 8),
-    ("d-split-sweeps", "toy_default", (), BMAX, "split_workgroup", 8, 8),
-    ("r-split-coop4", "toy_redsec", (), (1, 0), "split_coop", 4, 0),
-    ("r-split-coop2", "toy_redsec", (), (1, 3), "split_coop", 2, 0),
-    ("r-split-duo", "toy_redsec", (), (3, 2), "split_duo", 8, 4),
-    ("r-split-wg4", "toy_redsec", ("RS_NO_DUO",), (3, 2), "split_workgroup", 4, 4),
-    ("r-split-wg8", "toy_redsec", (), (6, 5), "split_workgroup", 8, 8),
-    ("r-split-sweeps", "toy_redsec", (), BMAX, "split_workgroup", 8, 8),
-]
-CASES = [(c, "fft") for c in FFT_CASES] + [(c, "exact") for c in EXACT_CASES] + [(c, "split") for c in SPLIT_CASES]
-
-
-def _resident(case, B, cus):
-    """What last_launch() must report as the ciphertexts of one key sweep."""
-    form, waves, per_cu = case[4], case[5], case[6]
-    if per_cu == 0:
-        return 1
-    if per_cu is None:                                   # per-wave kernel: the waves resident at once
-        return min(B, waves * cus)
-    groups = (B + per_cu - 1) // per_cu
-    return per_cu * min(groups, cus)
 
 
 @pytest.fixture(scope="module")
@@ -245,9 +183,11 @@ def test_directed_rows_whole_batch_equals_the_oracle(case, mode, request, monkey
     try:
         be.set_mode(mode)
         want = {"form": form, "waves_per_block": waves, "resident": _resident(case, B, cus)}
+        planned, _ = emu_lib.launch_plan(dr.TRAITS[fixture, mode], slab.ks.p.n, B, be.info()["num_cus"], dr.switch_bits(switches))
         for op in OPS:
             got = slab.run(be, op, B)
             assert be.last_launch() == want, (op, be.last_launch())
+            assert be.last_launch() == planned, (op, planned)
             got = got.cpu().numpy()
             ref = slab.ref(op)[:B]
             bad = np.nonzero((got != ref).any(axis=1))[0]
