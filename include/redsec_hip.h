@@ -282,6 +282,45 @@ int rs_gate(rs_ctx* ctx, rs_gate_op op, int32_t* out, const int32_t* a, const in
  * assumes +-1/8: see DESIGN.md "max-pool semantics"). */
 int rs_gate_mu_dev(rs_ctx* ctx, rs_gate_op op, int32_t* out, const int32_t* a, const int32_t* b, int32_t mu, size_t B, void* stream);
 
+/* Three-input gates and indexed gate batches (no reference counterpart: the reference composes
+ * two-input gates, five per full-adder bit). One bootstrap of a linear combination of THREE +-1/8 inputs gives a majority or a parity:
+ * a full adder is XOR3 + MAJ3, a subtractor XOR3 + MAJ3N. With e8 = 2^29 (1/8) and e4 = 2^30 (1/4), row op -> x = c0 a + c1 b + c2 c
+ * + (0, bconst), word-wise mod 2^32, and the result is bootstrap_mu(x):
+ *   0 NAND  (-1, -1, 0) +e8     1 OR    ( 1,  1, 0) +e8     2 AND   ( 1,  1, 0) -e8     3 NOR   (-1, -1, 0) -e8
+ *   4 XOR   ( 2,  2, 0) +e4     5 XNOR  (-2, -2, 0) -e4     6 ANDNY (-1,  1, 0) -e8     7 ANDYN ( 1, -1, 0) -e8
+ *   8 ORNY  (-1,  1, 0) +e8     9 ORYN  ( 1, -1, 0) +e8     (rs_gate_op's constants: the third input is ignored and never read)
+ *   10 MAJ3 ( 1,  1, 1)  0      11 XOR3 (-2, -2, -2)  0     12 MAJ3N (-1, 1, 1)  0
+ * The phase of x lies 1/8 (MAJ3, MAJ3N) or 1/4 (XOR3) from both 0 and 1/2 before noise. */
+typedef enum rs_row_op {            /* 0..9 = rs_gate_op with the same values (third input ignored) */
+  RS_ROW_MAJ3  = 10,                /* majority(a, b, c):      x =  a + b + c          */
+  RS_ROW_XOR3  = 11,                /* a ^ b ^ c:              x = -2a - 2b - 2c       */
+  RS_ROW_MAJ3N = 12                 /* majority(!a, b, c):     x = -a + b + c   (borrow of a - b) */
+} rs_row_op;
+typedef struct rs_row_group { int32_t op; int32_t reserved; uint64_t count; } rs_row_group;
+
+/* out[i] = op(a[i], b[i], c[i]) for op = 10..12 (mu = 1/8 encoding): rs_gate_rows_dev with one group, three base pointers and the
+ * identity index. RS_ERR_INVALID for another op or a null pointer; B = 0 is a no-op. */
+int rs_gate3_dev(rs_ctx* ctx, int op, int32_t* out, const int32_t* a, const int32_t* b, const int32_t* c, size_t B, void* stream);
+
+/* One bootstrap batch of B rows with MIXED ops over rows picked by index. in int32[in_rows][n+1], idx DEVICE int32[B][3],
+ * groups HOST (read before the call returns), out int32[B][n+1]. The rows are cut into n_groups consecutive runs: the first
+ * groups[0].count rows run groups[0].op, and so on. Row r of group g:
+ *   out[r] = bootstrap_mu(sum_j c_j(op_g) s(idx[r][j]) + (0, bconst(op_g))),  s(i) = in[i] for 0 <= i < in_rows,
+ *   s(-2) = the trivial TRUE sample (0, +2^29); s(i) = the trivial FALSE sample (0, -2^29) for every other negative i and every
+ *   i >= in_rows. Nothing validates idx on the device and nothing needs to: the kernel never reads outside `in`.
+ * A constant carry-in is index -1: XOR3(a, b, FALSE) = -2(a + b) + 1/4 decrypts as a ^ b (its words are NOT bootsXOR's: mask and
+ * phase are the negation of 2(a + b) + 1/4); MAJ3(a, b, FALSE) = a + b - 1/8 is exactly bootsAND's combination.
+ * RS_ERR_INVALID: a null pointer, n_groups outside 1..16, an op outside 0..12, reserved != 0, sum of the counts != B. A group
+ * with count 0 is allowed; B = 0 is a no-op that returns RS_OK.
+ * `out` may alias rows of `in`, also rows the same call reads: the combinations are materialised in a per-stream staging buffer
+ * [B][n+1] (grown on demand like the workspace: a device-wide wait; rs_reserve* do not size it) before any output is written,
+ * and the gated exact recomputation of RS_MODE_FFT re-reads that buffer, never `in`.
+ * Asynchronous and stream-ordered like every *_dev call; all three arithmetic modes and every parameter set, with the certificate
+ * rules of the other bootstrapped calls. The pre-pass (4 B (n+1) 4 bytes of traffic) runs in front of the two intervals
+ * rs_last_kernel_ms reports and is in neither. */
+int rs_gate_rows_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, size_t in_rows, const int32_t* idx, const rs_row_group* groups,
+                     int n_groups, int32_t mu, size_t B, void* stream);
+
 /* out[i] = bootsMUX(a[i], b[i], c[i]) = a ? b : c. */
 int rs_mux_dev(rs_ctx* ctx, int32_t* out, const int32_t* a, const int32_t* b, const int32_t* c, size_t B, void* stream);
 int rs_mux(rs_ctx* ctx, int32_t* out, const int32_t* a, const int32_t* b, const int32_t* c, size_t B);

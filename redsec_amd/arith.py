@@ -1,0 +1,53 @@
+"""Integer arithmetic on bit-sliced ciphertext batches at two bootstraps per bit.
+
+A batch of B encrypted integers of `bits` bits is an int32 tensor [bits][B][W], LSB first, every bit an LWE sample encoding
++-1/8 (what the gates produce and consume). A full adder is two bootstraps of linear combinations of three inputs:
+sum = XOR3(a, b, carry), carry' = MAJ3(a, b, carry); with the first input negated the same pair subtracts: difference =
+XOR3(a, b, borrow), borrow' = MAJ3N(a, b, borrow) = majority(!a, b, borrow). Each function below issues exactly `bits` calls of
+Backend.gate_rows, one per bit, each carrying both gates of all B lanes (2 B rows in two groups). The operands and every result
+row live in one arena tensor, addressed through index tables that are built once, on the arena's device; the carry-in of bit 0 is
+the index -1, the constant FALSE. Nothing here computes on ciphertext words: torch only lays rows out.
+
+(The C++ layer mirror's BinOps::add keeps the reference's five-gate sequence: it is the drop-in and is tested against it.)
+"""
+import torch
+
+
+def _ripple(be, a, b, ops):
+    """The ripple chain over the bits of a and b with the row ops `ops` per bit: the LAST op produces the carry (or borrow) the
+    next bit reads. -> the result rows as a view [bits][len(ops)][B][W] of the arena."""
+    assert a.shape == b.shape and a.dim() == 3, "operands must be [bits][B][W]"
+    bits, B, W = a.shape
+    k = len(ops)
+    base = 2 * bits * B                                           # rows of a, rows of b, then k B result rows per bit
+    arena = torch.empty((base + bits * k * B, W), dtype=torch.int32, device=a.device)
+    arena[:bits * B] = a.reshape(bits * B, W)
+    arena[bits * B:base] = b.reshape(bits * B, W)
+    i = torch.arange(bits, dtype=torch.int64, device=a.device)[:, None]
+    r = torch.arange(B, dtype=torch.int64, device=a.device)[None, :]
+    ia = i * B + r
+    carry = base + (i - 1) * k * B + (k - 1) * B + r              # the last result row of the previous bit
+    ic = torch.where(i == 0, torch.full_like(carry, -1), carry)
+    idx = torch.stack([ia, bits * B + ia, ic], dim=-1).repeat(1, k, 1).to(torch.int32).contiguous()   # [bits][k B][3]
+    groups = [(op, B) for op in ops]
+    for bit in range(bits):
+        lo = base + bit * k * B
+        be.gate_rows(arena, idx[bit], groups, out=arena[lo:lo + k * B])
+    return arena[base:].view(bits, k, B, W)
+
+
+def add(be, a, b):
+    """a + b -> [bits + 1][B][W]: the sum bits, then the carry out."""
+    rows = _ripple(be, a, b, ("XOR3", "MAJ3"))
+    return torch.cat([rows[:, 0], rows[-1:, 1]], dim=0)
+
+
+def sub(be, a, b):
+    """a - b mod 2^bits -> (difference [bits][B][W], borrow [B][W]); the borrow is set where a < b."""
+    rows = _ripple(be, a, b, ("XOR3", "MAJ3N"))
+    return rows[:, 0].contiguous(), rows[-1, 1].contiguous()
+
+
+def less_than(be, a, b):
+    """a < b (unsigned) -> [B][W]: the final borrow of a - b; the difference rows are not computed (B rows per bit)."""
+    return _ripple(be, a, b, ("MAJ3N",))[-1, 0].contiguous()

@@ -27,9 +27,13 @@ ABI_SYMBOLS = [
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
     "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
+    "rs_gate3_dev", "rs_gate_rows_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
+
+# rs_row_op (include/redsec_hip.h): the two-input gates with their rs_gate_op values, then the three-input ones
+ROW_OPS = dict(GATES, MAJ3=10, XOR3=11, MAJ3N=12)
 
 
 class RedsecHipError(RuntimeError):
@@ -54,6 +58,10 @@ class RsPoolShape(C.Structure):
 class RsKeyAudit(C.Structure):
     _fields_ = [("bk_max_abs", C.c_uint32), ("ksk_max_abs", C.c_uint32), ("bk_over", C.c_uint64), ("ksk_over", C.c_uint64),
                 ("ksk_zero_bad", C.c_uint64), ("bk_words", C.c_uint64), ("ksk_words", C.c_uint64)]
+
+
+class RsRowGroup(C.Structure):
+    _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("count", C.c_uint64)]
 
 
 _lib = None
@@ -113,6 +121,8 @@ def load_library(path=None):
     L.rs_gate.argtypes = [vp, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]
     L.rs_gate_mu_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_gather_rows_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.rs_gate3_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
+    L.rs_gate_rows_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.POINTER(RsRowGroup), C.c_int, C.c_int32, C.c_size_t, vp]
     L.rs_mux_dev.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.rs_mux.argtypes = [vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]
     L.rs_bootstrap_wo_ks_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
@@ -456,6 +466,31 @@ class Backend:
         out = self.empty(B, self.W)
         _check(self.L, self.L.rs_gather_rows_dev(self.h, self._ck_dev(out), self._ck_dev(x, self.W), C.c_void_p(index.data_ptr()), B,
                                                   self._stream()))
+        return out
+
+    def gate3(self, op, a, b, c, out=None):
+        """out[i] = op(a[i], b[i], c[i]) for op in 'MAJ3' | 'XOR3' | 'MAJ3N' (rs_gate3_dev; +-1/8 in, +-1/8 out)."""
+        B = a.shape[0]
+        out = self.empty(B, self.W) if out is None else out
+        _check(self.L, self.L.rs_gate3_dev(self.h, ROW_OPS[op] if isinstance(op, str) else int(op), self._ck_dev(out, self.W),
+                                            self._ck_dev(a, self.W), self._ck_dev(b, self.W), self._ck_dev(c, self.W), B, self._stream()))
+        return out
+
+    def gate_rows(self, inp, idx, groups, mu=None, out=None):
+        """One bootstrap batch of mixed gates over indexed rows (rs_gate_rows_dev). inp [in_rows][W]; idx int32 CUDA [B][3]: the three
+        source rows of every output row (-2: constant TRUE, any other index outside [0, in_rows): constant FALSE); groups: a list of
+        (op, count) cutting the B rows into consecutive runs, op a ROW_OPS name or number; mu: the output encoding (default 1/8).
+        out [B][W] may be rows of inp, also rows this call reads."""
+        B = idx.numel() // 3
+        assert idx.numel() == 3 * B, "idx must hold [B][3] indices"
+        in_rows = inp.numel() // self.W
+        out = self.empty(B, self.W) if out is None else out
+        assert out.numel() == B * self.W, "out must hold [B][n+1] words"
+        gs = (RsRowGroup * max(1, len(groups)))()
+        for g, (op, count) in zip(gs, groups):
+            g.op, g.reserved, g.count = (ROW_OPS[op] if isinstance(op, str) else int(op)), 0, int(count)
+        _check(self.L, self.L.rs_gate_rows_dev(self.h, self._ck_dev(out, self.W), self._ck_dev(inp, self.W), in_rows, self._ck_dev(idx),
+                                                gs, len(groups), (1 << 29) if mu is None else int(mu), B, self._stream()))
         return out
 
     def mux(self, a, b, c, out=None):

@@ -68,6 +68,8 @@ struct Lane {
   uint32_t* d_ks_scratch = nullptr;       // partial sums of the sliced (small-batch) keyswitch (grown on demand; <= ~50 MB)
   size_t ks_scratch_words = 0;
   int* d_progress = nullptr;              // XCD cohort table of the split lock-step kernel: [8][kCohortSlots] step counts
+  int32_t* d_rows = nullptr;              // materialised combinations of the indexed gate batches: [rows_batch][n + 1] (grown on demand)
+  size_t rows_batch = 0;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   bool ev_valid = false;
   rs::LaunchInfo last;
@@ -149,6 +151,7 @@ void free_lane(Lane* ln) {
   if (ln->h_split_max) (void)hipHostFree(ln->h_split_max);
   (void)hipFree(ln->d_u0); (void)hipFree(ln->d_u1); (void)hipFree(ln->d_counter); (void)hipFree(ln->d_cert);
   (void)hipFree(ln->d_conv_scratch); (void)hipFree(ln->d_ks_scratch); (void)hipFree(ln->d_progress);
+  (void)hipFree(ln->d_rows);
   for (auto& e : ln->ev) if (e) (void)hipEventDestroy(e);
 }
 
@@ -184,6 +187,17 @@ int ensure_ws(Lane* ln, size_t B) {
   RS_HIP(hipMalloc(&ln->d_u0, bytes));
   RS_HIP(hipMalloc(&ln->d_u1, bytes));
   ln->ws_batch = B;
+  return RS_OK;
+}
+
+// staging buffer of the indexed gate batches (rs_gate_rows_dev, rs_gate3_dev), grown under ensure_ws's rule
+int ensure_rows(Lane* ln, size_t B, size_t W) {
+  if (B <= ln->rows_batch) return RS_OK;
+  // hipFree waits for the device: no launch can still be using the old buffer
+  if (ln->d_rows) { (void)hipFree(ln->d_rows); ln->d_rows = nullptr; }
+  ln->rows_batch = 0;
+  RS_HIP(hipMalloc(&ln->d_rows, B * W * sizeof(int32_t)));
+  ln->rows_batch = B;
   return RS_OK;
 }
 
@@ -935,6 +949,79 @@ int rs_gate_mu_dev(rs_ctx* c, rs_gate_op op, int32_t* out, const int32_t* a, con
 
 int rs_gate_dev(rs_ctx* c, rs_gate_op op, int32_t* out, const int32_t* a, const int32_t* b, size_t B, void* stream) {
   return rs_gate_mu_dev(c, op, out, a, b, 1 << 29, B, stream);
+}
+
+namespace {
+
+// without a context nothing can run; say why when the reason is that no device exists (rs_create cannot have succeeded)
+int rows_ready(rs_ctx* c) {
+  if (!c) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { (void)hipGetLastError(); return fail(RS_ERR_NO_DEVICE, "no HIP device visible"); }
+  }
+  return ready(c);
+}
+
+// The one path of the indexed gate batches: the combinations are materialised in the lane's staging buffer (gate_rows_kernel, in
+// front of the timed intervals), then bootstrapped from there as plain ciphertexts. `out` is written by the keyswitch only, after
+// every read of the inputs; the gated exact recomputation of FFT mode re-reads the staging buffer.
+int run_gate_rows(rs_ctx* c, hipStream_t st, int32_t* out, rs::GateRowsArgs& a, int32_t mu) {
+  Lane* ln = nullptr;
+  int rc = lane_of(c, st, &ln);
+  if (rc) return rc;
+  rc = ensure_rows(ln, (size_t)a.B, (size_t)a.W);
+  if (rc) return rc;
+  a.out = ln->d_rows;
+  RS_HIP(rs::launch_gate_rows(a, c->num_cus, st));
+  const Combo x{ln->d_rows, nullptr, 1, 0, 0, nullptr};
+  return run_bootstrap(c, st, out, &x, 1, 0, mu, Lut{}, (size_t)a.B);
+}
+
+}  // namespace
+
+int rs_gate_rows_dev(rs_ctx* c, int32_t* out, const int32_t* in, size_t in_rows, const int32_t* idx, const rs_row_group* groups,
+                     int n_groups, int32_t mu, size_t B, void* stream) {
+  int rc = rows_ready(c);
+  if (rc) return rc;
+  if (!groups) return fail(RS_ERR_INVALID, "null group list");
+  if (n_groups < 1 || n_groups > rs::kRowMaxGroups) return fail(RS_ERR_INVALID, "n_groups %d outside 1..%d", n_groups, rs::kRowMaxGroups);
+  rs::GateRowsArgs a{};
+  uint64_t total = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    rs::RowCoef unused;
+    if (!rs::row_coef(groups[g].op, &unused)) return fail(RS_ERR_INVALID, "group %d: unknown row op %d", g, (int)groups[g].op);
+    if (groups[g].reserved != 0) return fail(RS_ERR_INVALID, "group %d: reserved must be 0", g);
+    if (groups[g].count > (uint64_t)B - total) return fail(RS_ERR_INVALID, "the group counts pass B = %zu", B);
+    total += groups[g].count;
+    a.groups.end[g] = (long)total;
+    a.groups.op[g] = groups[g].op;
+  }
+  if (total != (uint64_t)B) return fail(RS_ERR_INVALID, "the group counts sum to %llu, not B = %zu", (unsigned long long)total, B);
+  if (B == 0) return RS_OK;
+  if (!out || !in || !idx) return fail(RS_ERR_INVALID, "null pointer");
+  if (B > (size_t)LONG_MAX / (size_t)(c->p.n + 1) / 4) return fail(RS_ERR_INVALID, "batch too large");
+  a.groups.count = n_groups;
+  a.src[0] = a.src[1] = a.src[2] = in;
+  a.idx = idx;
+  a.in_rows = (long)std::min<size_t>(in_rows, (size_t)INT32_MAX + 1);   // an int32 index reaches no row past 2^31 - 1
+  a.B = (long)B; a.W = c->p.n + 1;
+  return run_gate_rows(c, (hipStream_t)stream, out, a, mu);
+}
+
+int rs_gate3_dev(rs_ctx* c, int op, int32_t* out, const int32_t* a0, const int32_t* a1, const int32_t* a2, size_t B, void* stream) {
+  int rc = rows_ready(c);
+  if (rc) return rc;
+  if (op < RS_ROW_MAJ3 || op > RS_ROW_MAJ3N) return fail(RS_ERR_INVALID, "row op %d is not a three-input gate (10..12)", op);
+  if (B == 0) return RS_OK;
+  if (!out || !a0 || !a1 || !a2) return fail(RS_ERR_INVALID, "null ciphertext pointer");
+  if (B > (size_t)LONG_MAX / (size_t)(c->p.n + 1) / 4) return fail(RS_ERR_INVALID, "batch too large");
+  rs::GateRowsArgs a{};
+  a.groups.count = 1; a.groups.end[0] = (long)B; a.groups.op[0] = op;
+  a.src[0] = a0; a.src[1] = a1; a.src[2] = a2;
+  a.idx = nullptr;   // the identity: row r of each operand
+  a.in_rows = (long)B;
+  a.B = (long)B; a.W = c->p.n + 1;
+  return run_gate_rows(c, (hipStream_t)stream, out, a, 1 << 29);
 }
 
 int rs_gather_rows_dev(rs_ctx* c, int32_t* out, const int32_t* in, const int32_t* row_index, size_t B, void* stream) {

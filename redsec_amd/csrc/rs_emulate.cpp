@@ -18,6 +18,7 @@
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
 #include "rs_ntt.h"
+#include "rs_rows.h"
 
 namespace {
 
@@ -1328,6 +1329,39 @@ void rs_emu_audit_reduce(const int32_t* noise, long count, uint32_t limit, int p
   for (int p = parts - 1; p >= 0; --p) rs::au_tally_merge(all, tally[(size_t)p]);
   *max_abs = all.max_abs;
   *over = all.over;
+}
+
+// ---- indexed gate batches (rs_gate_rows_dev, rs_gate3_dev) through the functions of rs_rows.h, as gate_rows_kernel places them: a
+// wave of 64 lanes per row ----
+// the row-op table: out4 = (c0, c1, c2, bconst); returns 0 for an op outside the table
+int rs_emu_row_coef(int op, int32_t* out4) {
+  rs::RowCoef g;
+  if (!rs::row_coef(op, &g)) return 0;
+  for (int j = 0; j < 3; ++j) out4[j] = g.c[j];
+  out4[3] = (int32_t)g.bconst;
+  return 1;
+}
+// gate_rows_kernel: the materialised combinations out[B][W]. src0..2: the three bases ([in_rows][W]); idx int32[B][3] or null (identity);
+// n_groups groups of (ops[g], counts[g]) whose counts sum to B. Returns 0, or -1 for arguments the host entry points refuse.
+int rs_emu_gate_rows(const int32_t* src0, const int32_t* src1, const int32_t* src2, long in_rows, const int32_t* idx, const int32_t* ops,
+                     const long* counts, int n_groups, int W, long B, int32_t* out) {
+  if (n_groups < 1 || n_groups > rs::kRowMaxGroups) return -1;
+  rs::GateRowsArgs a{};
+  long total = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    rs::RowCoef unused;
+    if (!rs::row_coef(ops[g], &unused) || counts[g] < 0) return -1;
+    total += counts[g];
+    a.groups.end[g] = total;
+    a.groups.op[g] = ops[g];
+  }
+  if (total != B) return -1;
+  a.groups.count = n_groups;
+  a.src[0] = src0; a.src[1] = src1; a.src[2] = src2;
+  a.idx = idx; a.in_rows = in_rows; a.out = out; a.B = B; a.W = W;
+  for (long r = 0; r < B; ++r)
+    for (int lane = 0; lane < 64; ++lane) rs::row_lane(a, r, lane);
+  return 0;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 
 #include "rs_launch_plan.h"
 #include "rs_ntt.h"
+#include "rs_rows.h"
 
 namespace rs {
 
@@ -156,6 +157,8 @@ struct AuditArgs {
 };
 hipError_t launch_audit_bk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
 hipError_t launch_audit_ksk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
+// indexed gate batches (rs_gate_rows_dev, rs_gate3_dev): the combinations of GateRowsArgs (rs_rows.h) written to a.out
+hipError_t launch_gate_rows(const GateRowsArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,
