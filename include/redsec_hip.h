@@ -425,6 +425,11 @@ int rs_last_kernel_ms_stream(rs_ctx* ctx, void* stream, float* blind_rotate_ms, 
  * 10 the same with the listed step (gadgets with l < 4) -- its waves per workgroup, and `resident` = ciphertexts sharing one sweep of the key (R of the
  * algorithmic-bytes formula). rs_info's waves_per_block is that of the default stream's last launch. */
 int rs_last_launch(rs_ctx* ctx, void* stream, int32_t* form, int32_t* waves_per_block, int64_t* resident);
+/* What the last keyswitch on `stream` ran: form 0 generic gather (one workgroup per ciphertext), 1 tiled (256 ciphertexts x 32
+ * words per workgroup), 2 tiled over `slices` cuts of the input coefficients (small batches), 3 wide (1,024 ciphertexts x 32
+ * words per workgroup, one workgroup per CU: large un-sliced batches); `slices` is 1 except in form 2. The environment variable
+ * RS_KS_FORM=wide|tiled, read once in rs_create, forces or forbids the wide form (diagnostics and tests). */
+int rs_last_keyswitch(rs_ctx* ctx, void* stream, int32_t* form, int32_t* slices);
 int rs_info(rs_ctx* ctx, int64_t* bk_device_bytes, int64_t* ksk_device_bytes, int32_t* waves_per_block,
             int32_t* num_cus);
 

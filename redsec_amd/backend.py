@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "rs_gate_mu_dev", "rs_gather_rows_dev", "rs_bootstrap_wo_ks_dev", "rs_keyswitch_dev", "rs_debug_polymul", "rs_debug_cohort_table", "rs_debug_fp64_rate", "rs_linear_fc_dev", "rs_conv_ternary_dev",
     "rs_sumpool_dev", "rs_lincomb_dev", "rs_dev_alloc", "rs_dev_free", "rs_copy_to_dev", "rs_copy_to_host", "rs_sync",
     "rs_set_timing", "rs_last_kernel_ms", "rs_info", "rs_set_mode", "rs_get_mode", "rs_rounding_certificate", "rs_fft_fallbacks",
-    "rs_bootstrap_lut_dev", "rs_set_certificate_limit", "rs_certify", "rs_reserve_stream", "rs_last_kernel_ms_stream", "rs_last_launch", "rs_copy_dev_to_dev",
+    "rs_bootstrap_lut_dev", "rs_set_certificate_limit", "rs_certify", "rs_reserve_stream", "rs_last_kernel_ms_stream", "rs_last_launch", "rs_last_keyswitch", "rs_copy_dev_to_dev",
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
@@ -155,6 +155,7 @@ def load_library(path=None):
     L.rs_reserve_stream.argtypes = [vp, C.c_size_t, vp]
     L.rs_last_kernel_ms_stream.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rs_last_launch.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.rs_last_keyswitch.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if path is None:
         _lib = L
     return L
@@ -631,6 +632,12 @@ class Backend:
         f, w, r = C.c_int32(), C.c_int32(), C.c_int64()
         _check(self.L, self.L.rs_last_launch(self.h, self._stream(), C.byref(f), C.byref(w), C.byref(r)))
         return {"form": ["per_wave", "workgroup", "duo", "coop2", "coop4", "general", "split_workgroup", "split_coop", "split_duo", "coop8", "coop8_listed"][f.value], "waves_per_block": w.value, "resident": r.value}
+
+    def last_keyswitch(self):
+        """(form, slices of the input coefficients) of the last keyswitch on the current stream."""
+        f, n = C.c_int32(), C.c_int32()
+        _check(self.L, self.L.rs_last_keyswitch(self.h, self._stream(), C.byref(f), C.byref(n)))
+        return {"form": ["gather", "tiled", "sliced", "wide"][f.value], "slices": n.value}
 
     def fp64_rate(self):
         """FP64 FMA lane-operations per second this device sustains right now (box calibration, see include/redsec_hip.h)."""

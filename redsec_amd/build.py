@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 HIP_LIB = os.path.join(HERE, "libredsec_hip.so")
 EMU_LIB = os.path.join(HERE, "librs_emulate.so")
 
-HIP_SOURCES = ["rs_bootstrap.hip", "rs_bootstrap_split.hip", "rs_bootstrap_listed.hip", "rs_general.hip", "rs_kernels.hip", "rs_seeded.hip", "rs_audit.hip", "rs_rows.hip", "rs_api.cpp"]
+HIP_SOURCES = ["rs_bootstrap.hip", "rs_bootstrap_split.hip", "rs_bootstrap_listed.hip", "rs_general.hip", "rs_kernels.hip", "rs_keyswitch_wide.hip", "rs_seeded.hip", "rs_audit.hip", "rs_rows.hip", "rs_api.cpp"]
 HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_audit.h", "rs_rows.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
 # THE recipe of the product library: what every object is compiled with, then (object name, source under csrc/, extra flags).
 # build_tree() below and, through it, tools/build_variant.sh and the ISA tools (--print-flags) read it from here.
@@ -38,6 +38,9 @@ HIP_OBJECTS = [
     # the other files use the default pipeline (the (9, 3) keyswitch in rs_kernels.hip loses 12 % without the post-RA pass)
     ("rs_general", "rs_general.hip", []),
     ("rs_kernels", "rs_kernels.hip", []),
+    # the wide throughput keyswitch (keyswitch_wide_kernel, round 16) in an object of its own: the kernels of rs_kernels keep their
+    # instructions. Default pipeline, as rs_kernels
+    ("rs_keyswitch_wide", "rs_keyswitch_wide.hip", []),
     # seeded ciphertexts (seeded_lwe_kernel) in an object of their own: every kernel of rs_general keeps its instructions
     ("rs_seeded", "rs_seeded.hip", []),
     # device decryption and the key audit (lwe_phase_kernel, audit_bk_kernel, audit_ksk_kernel), likewise in an object of their own

@@ -73,6 +73,7 @@ struct Lane {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   bool ev_valid = false;
   rs::LaunchInfo last;
+  rs::KsPlan last_ks; bool ks_ran = false;   // form of the last keyswitch on this stream (rs_last_keyswitch)
   // enforced split-mode certificate: the lane's running maximum is copied here (pinned host memory) behind every general-kernel
   // call, and looked at by the next call, rs_certify and rs_sync
   unsigned long long* h_split_max = nullptr;
@@ -86,6 +87,7 @@ struct rs_ctx {
   int mode = 1;  // RS_MODE_FFT by default; RS_MODE_EXACT_NTT = 0
   double cert_limit = RS_CERTIFICATE_LIMIT;
   rs::LaunchOpts opts;
+  int ks_force = rs::kKsAuto;      // RS_KS_FORM=wide|tiled (diagnostic, read once in rs_create): rs_host.h keyswitch_form
   double* d_tw = nullptr;          // exact-NTT tables (kTwTotal doubles)
   double* d_tw_fft = nullptr;      // FFT tables (kFftTwDoubles doubles)
   double* d_bk_ntt = nullptr;      // key in the NTT domain
@@ -362,7 +364,8 @@ int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, 
     k.u0 = ln->d_u0; k.u1 = count == 2 ? ln->d_u1 : nullptr; k.bconst = ks_bconst; k.ksk = c->d_ksk;
     k.W = c->p.n + 1; k.t = c->p.ks_t; k.basebit = c->p.ks_basebit; k.B = (long)B; k.out = out; k.N = c->p.N;
     attach_ks_scratch(c, ln, k);
-    RS_HIP(rs::launch_keyswitch(k, st));
+    RS_HIP(rs::launch_keyswitch(k, st, c->num_cus, c->ks_force, &ln->last_ks));
+    ln->ks_ran = true;
   }
   if (c->timing) { RS_HIP(hipEventRecord(ln->ev[2], st)); ln->ev_valid = true; }
   return RS_OK;
@@ -536,6 +539,7 @@ int rs_create(rs_ctx** out, const rs_params* p, int device) {
   c->opts.no_coop = env_on("RS_NO_COOP"); c->opts.no_wg = env_on("RS_NO_WG"); c->opts.no_duo = env_on("RS_NO_DUO");
   c->opts.no_persist = env_on("RS_NO_PERSIST"); c->opts.no_conv_tiled = env_on("RS_NO_CONV_TILED");
   c->opts.no_wg4 = env_on("RS_NO_WG4"); c->opts.no_tail = env_on("RS_NO_TAIL"); c->opts.no_coop8 = env_on("RS_NO_COOP8"); c->opts.no_coop8_listed = env_on("RS_NO_COOP8_LISTED"); c->opts.ks_atomics = env_on("RS_KS_ATOMICS"); c->opts.force_host_staged = env_on("RS_FORCE_HOST_STAGED"); c->opts.no_cohort = env_on("RS_NO_COHORT");
+  if (const char* v = getenv("RS_KS_FORM")) c->ks_force = strcmp(v, "wide") == 0 ? rs::kKsWide : strcmp(v, "tiled") == 0 ? rs::kKsTiled : rs::kKsAuto;
   Lane* ln = nullptr;
   if (lane_of(c, nullptr, &ln) != RS_OK) { destroy_ctx(c); return RS_ERR_HIP; }   // the default stream's lane
   *out = c;
@@ -1073,7 +1077,8 @@ int rs_keyswitch_dev(rs_ctx* c, int32_t* out, const int32_t* u, size_t B, void* 
   rc = lane_of(c, (hipStream_t)stream, &ln);
   if (rc) return rc;
   attach_ks_scratch(c, ln, k);
-  RS_HIP(rs::launch_keyswitch(k, (hipStream_t)stream));
+  RS_HIP(rs::launch_keyswitch(k, (hipStream_t)stream, c->num_cus, c->ks_force, &ln->last_ks));
+  ln->ks_ran = true;
   return RS_OK;
 }
 
@@ -1504,6 +1509,17 @@ int rs_last_launch(rs_ctx* c, void* stream, int32_t* form, int32_t* waves_per_bl
   if (form) *form = ln->last.form;
   if (waves_per_block) *waves_per_block = ln->last.waves_per_block;
   if (resident) *resident = ln->last.resident;
+  return RS_OK;
+}
+
+int rs_last_keyswitch(rs_ctx* c, void* stream, int32_t* form, int32_t* slices) {
+  if (!c) return fail(RS_ERR_INVALID, "null context");
+  Lane* ln = nullptr;
+  int rc = lane_of(c, (hipStream_t)stream, &ln);
+  if (rc) return rc;
+  if (!ln->ks_ran) return fail(RS_ERR_STATE, "no keyswitch launched on this stream yet");
+  if (form) *form = ln->last_ks.form;
+  if (slices) *slices = (int32_t)ln->last_ks.slices;
   return RS_OK;
 }
 

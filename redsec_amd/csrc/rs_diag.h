@@ -1,4 +1,4 @@
-// rs_diag.h -- everything DIAGNOSTIC about the blind-rotation kernels, behind ONE guard: -DRS_DIAG=<bits>.
+// rs_diag.h -- everything DIAGNOSTIC about the kernels (the blind rotation's, and one probe of the wide keyswitch), behind ONE guard: -DRS_DIAG=<bits>.
 // The product build never defines RS_DIAG: every macro below is then empty and diag::kNoKeyProbe is false, so the kernels
 // carry no trace of it (tools/codeobj_digest.py: the code objects are those of the tree before this file existed).
 //
@@ -19,6 +19,9 @@
 //   128           HALF-KEY TIMING PROBE of the general-ring kernels, RESULTS ARE WRONG: only the first four of a row's eight key
 //                 positions are loaded (the other four multiply whatever the position registers hold) -- what halving the bytes on the
 //                 L2 -> CU path is worth, i.e. the most a form that shares every row between two ciphertexts of a CU could gain
+//   512           SAMPLE-LOAD TIMING PROBE of the wide keyswitch (rs_keyswitch_wide.hip), RESULTS ARE WRONG: every lane takes a
+//                 lane-dependent computed word instead of loading its extracted sample -- what the 4-byte-aligned row reads
+//                 (one wave-load touches 64 cache lines) cost that kernel
 //
 // Phase stamps (cdna_hip_programming.md section 7, in-kernel stamps): s_memtime behind s_waitcnt lgkmcnt(0) at up to eight
 // phase boundaries, summed per wave into g_rs_stamps and read back by rs_debug_read_stamps (not part of include/redsec_hip.h).
@@ -41,7 +44,8 @@ constexpr bool kNoKeyProbe = (kBits & 16) != 0;
 constexpr bool kHalfExchangeProbe = (kBits & 32) != 0;
 constexpr bool kHalfExchangeSwaps = (kBits & 64) == 0;
 constexpr bool kHalfKeyProbe = (kBits & 128) != 0;
-constexpr bool kWrongOnPurpose = kNoKeyProbe || kHalfExchangeProbe || kHalfKeyProbe;   // timing probes: rs_api.cpp then gates and enforces nothing
+constexpr bool kKsSampleProbe = (kBits & 512) != 0;
+constexpr bool kWrongOnPurpose = kNoKeyProbe || kHalfExchangeProbe || kHalfKeyProbe || kKsSampleProbe;   // timing probes: rs_api.cpp then gates and enforces nothing
 // key rows of CMUX step i: step 0's under the probe
 #if defined(__HIPCC__)
 __host__ __device__

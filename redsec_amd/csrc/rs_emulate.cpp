@@ -1085,6 +1085,11 @@ long rs_emu_ks_comb_violations(uint32_t aibar, int t, int basebit, int D) {
 // slices of a small-batch keyswitch launch and the scratch they need (rs_host.h)
 long rs_emu_keyswitch_slices(long B, int W, int N) { return (long)rs::keyswitch_slices(B, W, N); }
 long rs_emu_keyswitch_scratch_words(long B, int W, int N) { return (long)rs::keyswitch_scratch_words_for(B, W, N); }
+// form of a keyswitch launch (rs_host.h keyswitch_form): form + 16 * slices; force = -1 (by batch size), 1 (never wide), 3 (wide)
+long rs_emu_keyswitch_form(long B, int W, int N, int t, int basebit, int num_cus, int force) {
+  const rs::KsPlan p = rs::keyswitch_form(B, W, N, t, basebit, num_cus, force);
+  return (long)p.form + 16L * (long)p.slices;
+}
 // the operation list of rs_allgather_rows for n contexts on `devices`, peer[d * n + s] = direct access allowed; rows of
 // (kind, ctx, other, path, lo, hi); returns the number of operations (out may be null)
 long rs_emu_exchange_plan(long rows, int n, const int* devices, const unsigned char* peer, int force_staged, long* out) {

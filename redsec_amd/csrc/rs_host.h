@@ -86,6 +86,35 @@ inline size_t keyswitch_scratch_words_for(long B, int W, int N) {
   return split > 1 ? (size_t)split * (size_t)W * (size_t)B : 0;
 }
 
+// ---- which form a keyswitch launch runs in (launch_keyswitch only dispatches on this; CPU-tested through the emulator library) ----
+//   kKsGather  generic gather form: one workgroup per ciphertext, any (t, basebit), any ring
+//   kKsTiled   256 ciphertexts x 32 words per workgroup, plain stores (rs_kernels.hip)
+//   kKsSliced  the same tiles over `slices` cuts of the N input coefficients (small batches; two-step with a scratch, else atomics)
+//   kKsWide    1,024 ciphertexts x 32 words per workgroup, one workgroup per CU (rs_keyswitch_wide.hip)
+// The wide form is taken by an un-sliced launch of a shape that has it once the batch holds kKsWideMinTilesPerCu full
+// 1,024-ciphertext tiles per CU, counted over all ceil(W / 32) word columns. Its grid is one quarter of the tiled form's in
+// workgroups that each own a whole CU, so below that a partly filled last round costs it more than the shared table saves
+// (sweep of B, profiles/r16/keyswitch_sweep.jsonl: default-128 wins from 16,384 on, loses at 4,096).
+// `force` is the diagnostic switch RS_KS_FORM read once in rs_create: kKsWide = wide whenever the shape has that kernel, at any
+// B (tests reach it at small B); kKsTiled = never wide.
+enum KsForm { kKsAuto = -1, kKsGather = 0, kKsTiled = 1, kKsSliced = 2, kKsWide = 3 };
+constexpr int kKsWideTile = 1024;
+constexpr int kKsWideMinTilesPerCu = 1;
+struct KsPlan { int form = kKsGather; unsigned slices = 1; };
+inline bool ks_tiled_shape(int t, int basebit) { return (t == 8 && basebit == 2) || (t == 9 && basebit == 3) || (t == 18 && basebit == 1); }
+inline bool ks_wide_shape(int t, int basebit) { return (t == 8 && basebit == 2) || (t == 9 && basebit == 3); }
+inline KsPlan keyswitch_form(long B, int W, int N, int t, int basebit, int num_cus, int force = kKsAuto) {
+  KsPlan p;
+  if (B <= 0 || !ks_tiled_shape(t, basebit)) return p;
+  if (force == kKsWide && ks_wide_shape(t, basebit)) { p.form = kKsWide; return p; }
+  p.slices = keyswitch_slices(B, W, N);
+  p.form = p.slices > 1 ? kKsSliced : kKsTiled;
+  const long columns = (W + 31) / 32;
+  if (force == kKsAuto && p.slices == 1 && ks_wide_shape(t, basebit) && (B / kKsWideTile) * columns >= (long)kKsWideMinTilesPerCu * num_cus)
+    p.form = kKsWide;
+  return p;
+}
+
 // How one slice travels from the context that computed it to a context that needs it. Peer access is asked for per device pair
 // (hipDeviceCanAccessPeer + hipDeviceEnablePeerAccess); where it is refused the slice is staged through pinned host memory by
 // this library itself -- source D2H once, every such destination H2D -- instead of relying on what the runtime does then.

@@ -90,7 +90,10 @@ hipError_t launch_blind_rotate(int cfg, int mode, const BlindRotateArgs& a, int 
 hipError_t launch_blind_rotate_split_wg(int cfg, const BlindRotateArgs& a, int num_cus, const LaunchOpts& opts, hipStream_t st, LaunchInfo* info);
 hipError_t launch_bk_transform(int cfg, int mode, const int32_t* bk, double* bk_x, const double* tw, Field f, double scale,
                                long n_polys, hipStream_t st);
-hipError_t launch_keyswitch(const KeyswitchArgs& a, hipStream_t st);
+// Dispatches on keyswitch_form (rs_host.h): `force` is a KsForm (kKsAuto = -1: by batch size), `ran` receives the form taken.
+struct KsPlan;
+hipError_t launch_keyswitch(const KeyswitchArgs& a, hipStream_t st, int num_cus, int force = -1, KsPlan* ran = nullptr);
+hipError_t launch_keyswitch_wide(const KeyswitchArgs& a, hipStream_t st);   // rs_keyswitch_wide.hip: 1,024 ciphertexts per workgroup
 hipError_t launch_gen_blind_rotate(int logn, const GenArgs& a, int num_cus, hipStream_t st);
 long gen_resident_ciphertexts(int logn, int num_cus);   // workgroups (= ciphertexts) the general kernel keeps resident
 hipError_t launch_gen_bk_transform(int logn, const int32_t* bk, double* bk_x, const double* tw, long n_polys, int num_cus, hipStream_t st);

@@ -590,9 +590,7 @@ __global__ __launch_bounds__(256) void sumpool_kernel(int32_t* __restrict__ out,
 // -------------------------------------------------------------------------------------------------
 // Slices of the N input coefficients for a tiled launch of a.B ciphertexts (1 = plain-store throughput form): doubled until
 // ~1024 workgroups exist, at most 64, every slice at least `min_per_slice` staging groups... coefficients long.
-static bool ks_tiled_shape(const KeyswitchArgs& a) {
-  return (a.t == 8 && a.basebit == 2) || (a.t == 9 && a.basebit == 3) || (a.t == 18 && a.basebit == 1);
-}
+static bool ks_tiled_shape(const KeyswitchArgs& a) { return ks_tiled_shape(a.t, a.basebit); }
 static_assert(KS_TILE_THREADS == 256 && KS_CH == 32, "rs_host.h keyswitch_slices() restates this grid");
 static unsigned ks_slices(const KeyswitchArgs& a) {
   if (!ks_tiled_shape(a) || a.B <= 0) return 1;
@@ -603,9 +601,13 @@ size_t keyswitch_scratch_words(const KeyswitchArgs& a) {
   return split > 1 ? (size_t)split * (size_t)a.W * (size_t)a.B : 0;
 }
 
-hipError_t launch_keyswitch(const KeyswitchArgs& a_in, hipStream_t st) {
+hipError_t launch_keyswitch(const KeyswitchArgs& a_in, hipStream_t st, int num_cus, int force, KsPlan* ran) {
   if (a_in.B <= 0) return hipSuccess;
   KeyswitchArgs a = a_in;
+  // which form: keyswitch_form (rs_host.h); this function only dispatches
+  const KsPlan plan = keyswitch_form(a.B, a.W, a.N, a.t, a.basebit, num_cus, force);
+  if (ran) *ran = plan;
+  if (plan.form == kKsWide) return launch_keyswitch_wide(a, st);   // rs_keyswitch_wide.hip
   // (basebit = 1, the (18, 1) keys of redsec_params_small / medium / large: a digit is one bit and the selected row is the same
   // for every lane, so a form that reads the rows with SCALAR loads and adds them under the execution mask -- no LDS at all --
   // was built and measured in round 3: bit-exact, and slower than the tiled kernel, 21.7 against 14.7 ms per 1,024 medium
@@ -613,10 +615,10 @@ hipError_t launch_keyswitch(const KeyswitchArgs& a_in, hipStream_t st) {
   // (i, j) with ~100 scalar registers to keep three rows in flight is latency-bound. Removed again; profiles/r03/t_*.)
   dim3 grid((unsigned)((a.B + KS_TILE_THREADS - 1) / KS_TILE_THREADS), (unsigned)((a.W + KS_CH - 1) / KS_CH), 1);
   // tiled forms: the two shipped shapes and (18, 1) of redsec_params_small / medium / large; any power-of-two ring
-  const bool tiled = ks_tiled_shape(a);
+  const bool tiled = plan.form != kKsGather;
   // small batches: slice the input coefficients until enough workgroups exist (latency form). The slices leave their partial
   // sums in the scratch and a second kernel adds them up; without a scratch they add into a zeroed output with integer atomics.
-  const unsigned split = ks_slices(a);
+  const unsigned split = plan.slices;
   grid.z = split;
   const bool two_step = split > 1 && a.scratch && a.scratch_words >= keyswitch_scratch_words(a);
   if (!two_step) a.scratch = nullptr;
