@@ -321,6 +321,39 @@ int rs_gate3_dev(rs_ctx* ctx, int op, int32_t* out, const int32_t* a, const int3
 int rs_gate_rows_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, size_t in_rows, const int32_t* idx, const rs_row_group* groups,
                      int n_groups, int32_t mu, size_t B, void* stream);
 
+/* Compiled Boolean circuits (no reference counterpart: the reference calls one gate at a time). A
+ * circuit is a table of CELLS sorted by level; rs_circuit_run_dev runs it level by level on `lanes` independent data sets, one
+ * bootstrap batch per level, without synchronising.
+ *   Wires: 0 .. n_inputs-1 are the inputs, cell i defines wire n_inputs + i. Level v is cells [level_end[v-1], level_end[v]).
+ *   Sources: src[j] is a wire, -1 (the trivial FALSE sample (0, -2^29)) or -2 (the trivial TRUE sample (0, +2^29)). Bit j of `neg`
+ *     negates source j: its coefficient is -c_j (a NOT for free; a negated constant is the other constant). A bit on a source whose
+ *     coefficient is 0 is ignored.
+ *   Ops 0..12 are the row ops above with their coefficient table: the cell's value is bootstrap_{1/8}(sum_j +-c_j(op) s(src[j]) +
+ *     (0, bconst(op))); without neg bits its words are those of rs_gate_rows_dev on the same rows.
+ *   Op 13, MUX(a, b, c) = a ? b : c, is bootsMUX as rs_mux_dev computes it: u1 = woKS(a + b - 1/8), u2 = woKS(-a + c - 1/8), value =
+ *     KS(u1 + u2 + (0, 1/8)): two blind rotations, one keyswitch; neg bits flip the sign of their source in both combinations.
+ *   Arena: DEVICE int32[n_inputs + n_cells][lanes][n+1]; wire w of lane l is row w * lanes + l. The caller fills the input rows, the
+ *     call fills every other row (+-1/8 encoding). A circuit does not depend on `lanes`.
+ * rs_circuit_create (HOST pointers, read before it returns) validates everything and copies the table to the device once.
+ * RS_ERR_INVALID: a null pointer; n_levels = 0; an empty level, level_end not increasing, or its last entry != n_cells; an op outside
+ * 0..13; reserved != 0; a src below -2; a src (any of the three, read or not) that is no input, constant or cell of an EARLIER level;
+ * a MUX cell followed in its level by another op (the MUX cells of a level come last); more than 2^31 - 1 wires. The device
+ * therefore validates nothing and never reads outside the table and the arena. A circuit belongs to its context: rs_destroy frees
+ * those still alive, rs_circuit_destroy one (RS_ERR_INVALID for a handle that is not alive: destroyed before, or another context's).
+ * rs_circuit_run_dev: asynchronous and stream-ordered; all three arithmetic modes and every parameter set, with the certificate
+ * rules of the other bootstrapped calls. lanes = 0 is a no-op; RS_ERR_INVALID for a null arena, a handle that is not alive, or
+ * sizes whose row arithmetic would overflow. Per level of C cells, the last M of them MUX: the pre-pass stages (C + M) lanes
+ * combinations in the per-stream staging buffer of rs_gate_rows_dev (grown ahead of the first level, like the workspace), the
+ * unchanged blind rotation runs over them, a fold adds the MUX rows' second samples, and ONE keyswitch of the first C lanes samples
+ * writes the level's arena rows. rs_last_kernel_ms reports the last level. */
+typedef enum rs_cell_op { RS_CELL_MUX = 13 } rs_cell_op;   /* 0..12 = rs_gate_op / rs_row_op values */
+typedef struct rs_cell { int32_t src[3]; uint8_t op; uint8_t neg; uint16_t reserved; } rs_cell;   /* 16 bytes */
+typedef struct rs_circuit rs_circuit;
+int rs_circuit_create(rs_ctx* ctx, rs_circuit** out, const rs_cell* cells, size_t n_cells, const uint32_t* level_end, size_t n_levels,
+                      size_t n_inputs);
+int rs_circuit_destroy(rs_ctx* ctx, rs_circuit* circuit);
+int rs_circuit_run_dev(rs_ctx* ctx, const rs_circuit* circuit, int32_t* arena, size_t lanes, void* stream);
+
 /* out[i] = bootsMUX(a[i], b[i], c[i]) = a ? b : c. */
 int rs_mux_dev(rs_ctx* ctx, int32_t* out, const int32_t* a, const int32_t* b, const int32_t* c, size_t B, void* stream);
 int rs_mux(rs_ctx* ctx, int32_t* out, const int32_t* a, const int32_t* b, const int32_t* c, size_t B);

@@ -9,8 +9,13 @@ row live in one arena tensor, addressed through index tables that are built once
 the index -1, the constant FALSE. Nothing here computes on ciphertext words: torch only lays rows out.
 
 (The C++ layer mirror's BinOps::add keeps the reference's five-gate sequence: it is the drop-in and is tested against it.)
+
+select, maximum, equal and multiply go through compiled circuits instead (redsec_amd/circuit.py): the
+generator's netlist is compiled once per (function, bit count) and bound once per backend, and a call is one Backend.circuit_run.
 """
 import torch
+
+from . import circuit
 
 
 def _ripple(be, a, b, ops):
@@ -51,3 +56,40 @@ def sub(be, a, b):
 def less_than(be, a, b):
     """a < b (unsigned) -> [B][W]: the final borrow of a - b; the difference rows are not computed (B rows per bit)."""
     return _ripple(be, a, b, ("MAJ3N",))[-1, 0].contiguous()
+
+
+def _plan(be, name, bits):
+    """The bound plan of generator `name` at `bits` bits on this backend, made on first use and kept with the backend."""
+    cache = be.__dict__.setdefault("_circuit_plans", {})
+    if (name, bits) not in cache:
+        cache[(name, bits)] = getattr(circuit, name)(bits).compile().bind(be)
+    return cache[(name, bits)]
+
+
+def _pair(a, b):
+    assert a.shape == b.shape and a.dim() == 3, "operands must be [bits][B][W]"
+    return a.shape[0], torch.cat([a, b], dim=0)
+
+
+def select(be, cond, x, y):
+    """cond ? x : y -> [bits][B][W]; cond [B][W], one MUX cell per bit in one level."""
+    assert x.shape == y.shape and x.dim() == 3 and cond.shape == x.shape[1:], "cond must be [B][W], x and y [bits][B][W]"
+    return _plan(be, "select", x.shape[0]).run(torch.cat([cond[None], x, y], dim=0))
+
+
+def maximum(be, a, b):
+    """max(a, b) (unsigned) -> [bits][B][W]: the borrow chain of a - b, then one level of MUX cells."""
+    bits, inputs = _pair(a, b)
+    return _plan(be, "maximum", bits).run(inputs)
+
+
+def equal(be, a, b):
+    """a == b -> [B][W]."""
+    bits, inputs = _pair(a, b)
+    return _plan(be, "equal", bits).run(inputs)[0]
+
+
+def multiply(be, a, b):
+    """a * b -> [2 bits][B][W]."""
+    bits, inputs = _pair(a, b)
+    return _plan(be, "multiplier", bits).run(inputs)

@@ -28,12 +28,16 @@ ABI_SYMBOLS = [
     "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
+    "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
 
 # rs_row_op (include/redsec_hip.h): the two-input gates with their rs_gate_op values, then the three-input ones
 ROW_OPS = dict(GATES, MAJ3=10, XOR3=11, MAJ3N=12)
+
+# ops of a circuit cell (rs_cell_op): the row ops with their values, then MUX
+CELL_OPS = dict(ROW_OPS, MUX=13)
 
 
 class RedsecHipError(RuntimeError):
@@ -63,6 +67,13 @@ class RsKeyAudit(C.Structure):
 class RsRowGroup(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("count", C.c_uint64)]
 
+
+class RsCell(C.Structure):
+    _fields_ = [("src", C.c_int32 * 3), ("op", C.c_uint8), ("neg", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+# numpy view of an rs_cell table (circuit.Plan.table)
+CELL_DTYPE = np.dtype([("src", np.int32, (3,)), ("op", np.uint8), ("neg", np.uint8), ("reserved", np.uint16)])
 
 _lib = None
 
@@ -123,6 +134,9 @@ def load_library(path=None):
     L.rs_gather_rows_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.rs_gate3_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
     L.rs_gate_rows_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.POINTER(RsRowGroup), C.c_int, C.c_int32, C.c_size_t, vp]
+    L.rs_circuit_create.argtypes = [vp, C.POINTER(vp), vp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.c_size_t]
+    L.rs_circuit_destroy.argtypes = [vp, vp]
+    L.rs_circuit_run_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.rs_mux_dev.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.rs_mux.argtypes = [vp, _i32p, _i32p, _i32p, _i32p, C.c_size_t]
     L.rs_bootstrap_wo_ks_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
@@ -493,6 +507,27 @@ class Backend:
         _check(self.L, self.L.rs_gate_rows_dev(self.h, self._ck_dev(out, self.W), self._ck_dev(inp, self.W), in_rows, self._ck_dev(idx),
                                                 gs, len(groups), (1 << 29) if mu is None else int(mu), B, self._stream()))
         return out
+
+    # ---- compiled circuits (redsec_amd/circuit.py builds the tables) ----
+    def circuit_create(self, table, level_end, n_inputs):
+        """rs_circuit_create: table = numpy array of CELL_DTYPE sorted by level, level_end = one past the last cell of every level
+        -> an opaque handle that lives until circuit_destroy or close()."""
+        table = np.ascontiguousarray(table, dtype=CELL_DTYPE)
+        level_end = np.ascontiguousarray(level_end, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(self.L, self.L.rs_circuit_create(self.h, C.byref(h), table.ctypes.data_as(C.c_void_p), len(table),
+                                                 level_end.ctypes.data_as(C.POINTER(C.c_uint32)), len(level_end), int(n_inputs)))
+        return h
+
+    def circuit_destroy(self, handle):
+        _check(self.L, self.L.rs_circuit_destroy(self.h, handle))
+
+    def circuit_run(self, handle, arena, lanes):
+        """rs_circuit_run_dev on torch's current stream: arena int32 CUDA [n_inputs + n_cells][lanes][W] with the input rows
+        filled; every other row is written. -> arena."""
+        assert arena.numel() % (self.W * max(1, int(lanes))) == 0, "arena must hold [wires][lanes][n+1] words"
+        _check(self.L, self.L.rs_circuit_run_dev(self.h, handle, self._ck_dev(arena, self.W), int(lanes), self._stream()))
+        return arena
 
     def mux(self, a, b, c, out=None):
         B = a.shape[0]

@@ -18,9 +18,11 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <set>
 #include <string>
 #include <vector>
 
+#include "rs_circuit.h"
 #include "rs_diag.h"
 #include "rs_host.h"
 #include "rs_general.h"
@@ -79,6 +81,15 @@ struct Lane {
   unsigned long long* h_split_max = nullptr;
 };
 
+// A compiled circuit (rs_circuit_create): the validated cell table on the device and the level cuts on the host. It belongs to
+// its context, which keeps the set of live handles: a handle that is not in the set is refused, never followed.
+struct rs_circuit {
+  rs::Cell* d_cells = nullptr;
+  std::vector<uint32_t> level_end, level_mux;   // per level: one past its last cell, and how many of its cells (the last ones) are MUX
+  size_t n_cells = 0, n_inputs = 0;
+  size_t widest = 0;                            // max over the levels of cells + MUX cells: staged rows per lane
+};
+
 struct rs_ctx {
   rs_params p{};
   int device = 0;
@@ -119,6 +130,8 @@ struct rs_ctx {
   std::vector<int> peers_enabled, peers_denied;
   int32_t* h_stage = nullptr;                       // pinned staging buffer of this context's slice (host-staged exchange only)
   size_t h_stage_bytes = 0;
+  std::mutex circuits_mu;
+  std::set<rs_circuit*> circuits;                   // live handles of rs_circuit_create
 };
 
 namespace {
@@ -294,13 +307,11 @@ rs::BlindRotateArgs br_args(rs_ctx* c, Lane* ln, int mode, const Combo& x, int32
 //               unless the distance reached the limit, in which case they overwrite the extracted samples with
 //               the guaranteed-exact result before the keyswitch reads them. No host round trip, stream-ordered,
 //               so every *_dev result is exact (= RS_MODE_EXACT_NTT = the CPU oracle) by construction.
-int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, int count, int32_t ks_bconst, int32_t mu,
-                  const Lut& lut, size_t B) {
-  Lane* ln = nullptr;
-  int rc = lane_of(c, st, &ln);
-  if (rc) return rc;
-  rc = ensure_ws(ln, B);
-  if (rc) return rc;
+//
+// In two halves, so that a caller may rotate R rows and keyswitch only the first B of them (rs_circuit_run_dev, whose MUX cells
+// take two rotations and one keyswitch): rotate_rows needs ensure_ws(ln, B) before it and leaves the extracted samples of combo k
+// in the lane's d_u0 (k = 0) and d_u1 (k = 1); keyswitch_rows reads them.
+int rotate_rows(rs_ctx* c, hipStream_t st, Lane* ln, const Combo* combos, int count, int32_t mu, const Lut& lut, size_t B) {
   const int mode = c->mode;
   Combo cs[2];
   for (int k = 0; k < count; ++k) { cs[k] = combos[k]; cs[k].u = k == 0 ? ln->d_u0 : ln->d_u1; }
@@ -359,22 +370,46 @@ int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, 
       RS_HIP(rs::launch_blind_rotate(c->cfg, 0, br_args(c, ln, 0, cs[k], mu, lut, B), c->num_cus, c->opts, st, &ln->last));
   }
   if (c->timing) RS_HIP(hipEventRecord(ln->ev[1], st));
-  if (out) {
-    rs::KeyswitchArgs k;
-    k.u0 = ln->d_u0; k.u1 = count == 2 ? ln->d_u1 : nullptr; k.bconst = ks_bconst; k.ksk = c->d_ksk;
-    k.W = c->p.n + 1; k.t = c->p.ks_t; k.basebit = c->p.ks_basebit; k.B = (long)B; k.out = out; k.N = c->p.N;
-    attach_ks_scratch(c, ln, k);
-    RS_HIP(rs::launch_keyswitch(k, st, c->num_cus, c->ks_force, &ln->last_ks));
-    ln->ks_ran = true;
-  }
+  return RS_OK;
+}
+
+// out[B][n+1] = keyswitch of the first B extracted samples of the lane: u0 (+ u1 when two rotations ran) (+ ks_bconst on the b word)
+int keyswitch_rows(rs_ctx* c, hipStream_t st, Lane* ln, int32_t* out, int count, int32_t ks_bconst, size_t B) {
+  rs::KeyswitchArgs k;
+  k.u0 = ln->d_u0; k.u1 = count == 2 ? ln->d_u1 : nullptr; k.bconst = ks_bconst; k.ksk = c->d_ksk;
+  k.W = c->p.n + 1; k.t = c->p.ks_t; k.basebit = c->p.ks_basebit; k.B = (long)B; k.out = out; k.N = c->p.N;
+  attach_ks_scratch(c, ln, k);
+  RS_HIP(rs::launch_keyswitch(k, st, c->num_cus, c->ks_force, &ln->last_ks));
+  ln->ks_ran = true;
+  return RS_OK;
+}
+
+int finish_timing(rs_ctx* c, hipStream_t st, Lane* ln) {
   if (c->timing) { RS_HIP(hipEventRecord(ln->ev[2], st)); ln->ev_valid = true; }
   return RS_OK;
+}
+
+int run_bootstrap(rs_ctx* c, hipStream_t st, int32_t* out, const Combo* combos, int count, int32_t ks_bconst, int32_t mu,
+                  const Lut& lut, size_t B) {
+  Lane* ln = nullptr;
+  int rc = lane_of(c, st, &ln);
+  if (rc) return rc;
+  rc = ensure_ws(ln, B);
+  if (rc) return rc;
+  rc = rotate_rows(c, st, ln, combos, count, mu, lut, B);
+  if (rc) return rc;
+  if (out) {
+    rc = keyswitch_rows(c, st, ln, out, count, ks_bconst, B);
+    if (rc) return rc;
+  }
+  return finish_timing(c, st, ln);
 }
 
 void destroy_ctx(rs_ctx* c) {
   (void)hipFree(c->d_tw); (void)hipFree(c->d_tw_fft); (void)hipFree(c->d_bk_ntt); (void)hipFree(c->d_bk_fft); (void)hipFree(c->d_ksk);
   (void)hipFree(c->d_tw_gen); (void)hipFree(c->d_bk_gen);
   for (auto& kv : c->lanes) free_lane(kv.second.get());
+  for (rs_circuit* q : c->circuits) { (void)hipFree(q->d_cells); delete q; }
   for (auto& p : c->d_io) (void)hipFree(p);
   if (c->ev_slice) (void)hipEventDestroy(c->ev_slice);
   if (c->ev_copied) (void)hipEventDestroy(c->ev_copied);
@@ -1026,6 +1061,112 @@ int rs_gate3_dev(rs_ctx* c, int op, int32_t* out, const int32_t* a0, const int32
   a.in_rows = (long)B;
   a.B = (long)B; a.W = c->p.n + 1;
   return run_gate_rows(c, (hipStream_t)stream, out, a, 1 << 29);
+}
+
+// ---- compiled circuits ----
+static_assert(sizeof(rs_cell) == sizeof(rs::Cell) && offsetof(rs_cell, op) == offsetof(rs::Cell, op) && offsetof(rs_cell, neg) == offsetof(rs::Cell, neg) &&
+              offsetof(rs_cell, reserved) == offsetof(rs::Cell, reserved), "rs_cell and rs::Cell are one layout");
+
+namespace {
+
+// the context of a circuit call that needs no key: as rows_ready, without the key check
+int circuit_ctx(rs_ctx* c) {
+  if (!c) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { (void)hipGetLastError(); return fail(RS_ERR_NO_DEVICE, "no HIP device visible"); }
+  }
+  return use_device(c);
+}
+
+bool circuit_alive(rs_ctx* c, const rs_circuit* q) {
+  std::lock_guard<std::mutex> g(c->circuits_mu);
+  return q && c->circuits.count(const_cast<rs_circuit*>(q)) != 0;
+}
+
+}  // namespace
+
+int rs_circuit_create(rs_ctx* c, rs_circuit** out, const rs_cell* cells, size_t n_cells, const uint32_t* level_end, size_t n_levels,
+                      size_t n_inputs) {
+  int rc = circuit_ctx(c);
+  if (rc) return rc;
+  if (!out) return fail(RS_ERR_INVALID, "null pointer");
+  *out = nullptr;
+  const char* why = "";
+  const rs::Cell* table = reinterpret_cast<const rs::Cell*>(cells);
+  if (rs::circuit_check(table, n_cells, level_end, n_levels, n_inputs, &why) != 0) return fail(RS_ERR_INVALID, "circuit refused: %s", why);
+  std::unique_ptr<rs_circuit> q(new rs_circuit);
+  q->n_cells = n_cells; q->n_inputs = n_inputs;
+  q->level_end.assign(level_end, level_end + n_levels);
+  size_t lo = 0;
+  for (size_t v = 0; v < n_levels; ++v) {
+    size_t mux = 0;
+    for (size_t i = lo; i < level_end[v]; ++i) mux += table[i].op == rs::kCellMux;
+    q->level_mux.push_back((uint32_t)mux);
+    q->widest = std::max(q->widest, level_end[v] - lo + mux);
+    lo = level_end[v];
+  }
+  RS_HIP(hipMalloc((void**)&q->d_cells, n_cells * sizeof(rs::Cell)));
+  if (hipMemcpy(q->d_cells, table, n_cells * sizeof(rs::Cell), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(q->d_cells);
+    return fail(RS_ERR_HIP, "copying the cell table to the device failed");
+  }
+  std::lock_guard<std::mutex> g(c->circuits_mu);
+  c->circuits.insert(q.get());
+  *out = q.release();
+  return RS_OK;
+}
+
+int rs_circuit_destroy(rs_ctx* c, rs_circuit* q) {
+  int rc = circuit_ctx(c);
+  if (rc) return rc;
+  {
+    std::lock_guard<std::mutex> g(c->circuits_mu);
+    if (!q || c->circuits.erase(q) == 0) return fail(RS_ERR_INVALID, "not a live circuit of this context");
+  }
+  (void)hipFree(q->d_cells);   // waits for the device: no launch can still be reading the table
+  delete q;
+  return RS_OK;
+}
+
+int rs_circuit_run_dev(rs_ctx* c, const rs_circuit* q, int32_t* arena, size_t lanes, void* stream) {
+  int rc = rows_ready(c);
+  if (rc) return rc;
+  if (!circuit_alive(c, q)) return fail(RS_ERR_INVALID, "not a live circuit of this context");
+  if (lanes == 0) return RS_OK;
+  if (!arena) return fail(RS_ERR_INVALID, "null arena");
+  const size_t W = (size_t)c->p.n + 1;
+  hipStream_t st = (hipStream_t)stream;
+  Lane* ln = nullptr;
+  rc = lane_of(c, st, &ln);
+  if (rc) return rc;
+  if (!rs::circuit_sizes_ok(q->n_inputs + q->n_cells, q->widest, lanes, W, ln->sample_words)) return fail(RS_ERR_INVALID, "circuit too large for this lane count");
+  // both buffers at the size of the widest level, once: no level below waits for the device
+  rc = ensure_rows(ln, q->widest * lanes, W);
+  if (rc) return rc;
+  rc = ensure_ws(ln, q->widest * lanes);
+  if (rc) return rc;
+  size_t lo = 0;
+  for (size_t v = 0; v < q->level_end.size(); ++v) {
+    const size_t cells = q->level_end[v] - lo, mux = q->level_mux[v], B = cells * lanes, R = B + mux * lanes;
+    rs::CircuitLevelArgs a{};
+    a.cells = q->d_cells; a.arena = arena; a.out = ln->d_rows;
+    a.first = (long)lo; a.C = (long)cells; a.M = (long)mux; a.lanes = (long)lanes; a.W = (int)W;
+    RS_HIP(rs::launch_circuit_rows(a, c->num_cus, st));
+    const Combo x{ln->d_rows, nullptr, 1, 0, 0, nullptr};
+    rc = rotate_rows(c, st, ln, &x, 1, 1 << 29, Lut{}, R);
+    if (rc) return rc;
+    rs::CircuitFoldArgs f{};
+    f.u = ln->d_u0; f.B = (long)B; f.mux_rows = (long)(mux * lanes); f.words = (int)ln->sample_words;
+    RS_HIP(rs::launch_circuit_fold(f, c->num_cus, st));
+    // the level's wires are consecutive rows of the arena, and none of them is a source of the level
+    rc = keyswitch_rows(c, st, ln, arena + (q->n_inputs + lo) * lanes * W, 1, 0, B);
+    if (rc) return rc;
+    rc = finish_timing(c, st, ln);
+    if (rc) return rc;
+    lo = q->level_end[v];
+  }
+  return RS_OK;
 }
 
 int rs_gather_rows_dev(rs_ctx* c, int32_t* out, const int32_t* in, const int32_t* row_index, size_t B, void* stream) {

@@ -18,6 +18,7 @@
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
 #include "rs_ntt.h"
+#include "rs_circuit.h"
 #include "rs_rows.h"
 
 namespace {
@@ -1366,6 +1367,31 @@ int rs_emu_gate_rows(const int32_t* src0, const int32_t* src1, const int32_t* sr
   a.idx = idx; a.in_rows = in_rows; a.out = out; a.B = B; a.W = W;
   for (long r = 0; r < B; ++r)
     for (int lane = 0; lane < 64; ++lane) rs::row_lane(a, r, lane);
+  return 0;
+}
+
+// ---- compiled circuits (rs_circuit_create, rs_circuit_run_dev) through the functions of rs_circuit.h ----
+// the host validation of rs_circuit_create: 0, or -1 for what it refuses. cells: rs_cell[n_cells]
+int rs_emu_circuit_check(const void* cells, size_t n_cells, const uint32_t* level_end, size_t n_levels, size_t n_inputs) {
+  return rs::circuit_check(static_cast<const rs::Cell*>(cells), n_cells, level_end, n_levels, n_inputs, nullptr);
+}
+// circuit_rows_kernel on one level (cells [first, first + C), the last M of them MUX): the staged rows out[(C + M) lanes][W] from
+// arena[wires][lanes][W], a wave of 64 lanes per row. Returns 0, or -1 for a shape the launcher refuses.
+int rs_emu_circuit_rows(const void* cells, long first, long C_, long M, long lanes, const int32_t* arena, int W, int32_t* out) {
+  if (C_ <= 0 || M < 0 || M > C_ || lanes <= 0 || first < 0 || W < 1 || !cells || !arena || !out) return -1;
+  rs::CircuitLevelArgs a{};
+  a.cells = static_cast<const rs::Cell*>(cells); a.arena = arena; a.out = out;
+  a.first = first; a.C = C_; a.M = M; a.lanes = lanes; a.W = W;
+  for (long r = 0; r < rs::circuit_level_rows(a); ++r)
+    for (int lane = 0; lane < 64; ++lane) rs::circuit_row_lane(a, r, lane);
+  return 0;
+}
+// circuit_fold_kernel: u[(B + mux_rows)][words], MUX row m (the row B - mux_rows + m) += row B + m + (0, 1/8)
+int rs_emu_circuit_fold(int32_t* u, long B, long mux_rows, int words) {
+  if (!u || mux_rows < 0 || mux_rows > B || words < 1) return -1;
+  rs::CircuitFoldArgs a{u, B, mux_rows, words};
+  for (long m = 0; m < mux_rows; ++m)
+    for (int lane = 0; lane < 64; ++lane) rs::circuit_fold_lane(a, m, lane);
   return 0;
 }
 

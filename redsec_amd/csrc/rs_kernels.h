@@ -162,6 +162,12 @@ hipError_t launch_audit_bk(const AuditArgs& a, bool seeded, int num_cus, hipStre
 hipError_t launch_audit_ksk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
 // indexed gate batches (rs_gate_rows_dev, rs_gate3_dev): the combinations of GateRowsArgs (rs_rows.h) written to a.out
 hipError_t launch_gate_rows(const GateRowsArgs& a, int num_cus, hipStream_t st);
+// compiled circuits (rs_circuit_run_dev), per level: the staged combinations of CircuitLevelArgs (rs_circuit.h) written to a.out,
+// and the fold of the MUX rows on the extracted samples
+struct CircuitLevelArgs;
+struct CircuitFoldArgs;
+hipError_t launch_circuit_rows(const CircuitLevelArgs& a, int num_cus, hipStream_t st);
+hipError_t launch_circuit_fold(const CircuitFoldArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,
