@@ -167,6 +167,27 @@ int rs_encrypt_seeded_dev(rs_ctx* ctx, int32_t* body, int32_t* ct, const int32_t
 int rs_expand_ciphertexts_dev(rs_ctx* ctx, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body,
                               size_t B, void* stream);
 
+/* Public-key encryption (no reference counterpart: TFHE has no public key). A party WITHOUT the secret
+ * encrypts under a Regev public key: m encryptions of zero, canonically rs_expand_ciphertexts_dev of an rs_encrypt_seeded_dev(mu = 0,
+ * B = m) batch, so a public key travels as a seeded-ciphertext batch (32-byte mask seed + m body words). Each output is the sum of a
+ * secret random subset of the rows; with `base` the same call re-randomises ciphertexts. One more stream, disjoint from domains 1-8:
+ *   domain 9   selection bits   row first + i   bit j of ciphertext i = (word (j >> 5) of the stream >> (j & 31)) & 1,  j < m
+ *   ct[i] = (base ? base[i] : 0) + (0, mu ? mu[i] : 0) + sum over j with bit j set of pk[j]      (word-wise mod 2^32)
+ * pk DEVICE int32[m][n+1]; mu DEVICE int32[B] or NULL; base DEVICE int32[B][n+1] or NULL; ct DEVICE int32[B][n+1]. ct may equal base
+ * (re-randomisation in place); any other overlap is the caller's error. rand_seed: HOST, 32 bytes, the encryptor's PRIVATE randomness
+ * (the ChaCha key of domain 9), read before the call returns; it reaches the device as a kernel argument, the selection bits exist
+ * only in registers and LDS, and nothing secret outlives the call. Needs no loaded key. Asynchronous and ordered on `stream`, like
+ * rs_expand_ciphertexts_dev. B = 0 is a no-op that returns RS_OK.
+ * Rule: a (rand seed, row) pair must never be used twice -- two outputs with the same selection differ by exactly their messages (and
+ * bases). redsec_amd's default is a fresh random rand seed per call.
+ * Noise of an output: about alpha sqrt(m / 2) for rows of deviation alpha (m / 2 rows are added on average). Security rests on LWE at
+ * the rows' alpha and on the leftover hash lemma over m (redsec_amd's default m = 32 (n + 1) + 256 = n log q + 2 lambda); nothing more
+ * is claimed.
+ * RS_ERR_INVALID: a null ct, pk or rand_seed; m outside 1 .. 2^31 - 1; first + B passing 2^64; B or m whose row arithmetic would
+ * overflow. Without a device or context it fails as rs_expand_ciphertexts_dev does. */
+int rs_pk_encrypt_dev(rs_ctx* ctx, int32_t* ct, const int32_t* pk, size_t m, const int32_t* mu, const int32_t* base,
+                      size_t B, const uint8_t* rand_seed, uint64_t first, void* stream);
+
 /* Device decryption and the exact noise audit of evaluation keys. CLIENT side: a server holds no secret.
  * All three are synchronous like rs_keygen_dev and additionally wait for ALL work queued on the context's device, on every stream,
  * before they read their inputs. Secret keys are HOST pointers with words in {0, 1}; their private device copy (packed bits) is

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
-    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev",
+    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
@@ -122,6 +122,7 @@ def load_library(path=None):
     L.rs_load_compressed_keys_dev.argtypes = [vp, C.c_char_p, vp, vp]
     L.rs_encrypt_seeded_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, _i32p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_double]
     L.rs_expand_ciphertexts_dev.argtypes = [vp, vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp]
+    L.rs_pk_encrypt_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, vp]
     L.rs_phase_dev.argtypes = [vp, vp, vp, C.c_size_t, _i32p, C.c_int32]
     L.rs_audit_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
     L.rs_audit_compressed_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, C.c_char_p, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
@@ -369,6 +370,38 @@ class Backend:
         _check(self.L, self.L.rs_expand_ciphertexts_dev(self.h, self._ck_dev(out, self.W), self._seed32(mask_seed, "mask_seed"), int(first),
                                                         self._ck_dev(body), B, self._stream()))
         return out
+
+    # ---- public-key encryption ----
+    def pk_encrypt(self, pk, mu=None, rand_seed=None, first=0, base=None, out=None):
+        """Encryption under a public key without the secret (rs_pk_encrypt_dev, on torch's current stream): out[i] = base[i] + (0, mu[i])
+        + a random subset of the rows of pk, the subset of row first + i of rand_seed (32 bytes, PRIVATE; default a fresh os.urandom(32)
+        per call: a (rand seed, row) pair must never be used twice). pk: int32 CUDA tensor [m][n+1] of encryptions of zero, or the
+        client.SeededCiphertexts of SecretKeySet.public_key (expanded on the device first). mu: int32 CUDA tensor [B] of torus words or
+        None; base: int32 CUDA tensor [B][n+1] or None (re-randomisation; out=base works in place). -> int32 CUDA tensor [B][n+1]."""
+        if hasattr(pk, "mask_seed"):
+            import torch
+            body = pk.body if hasattr(pk.body, "is_cuda") else torch.from_numpy(np.ascontiguousarray(pk.body, np.int32)).to("cuda:%d" % self.device)
+            pk = self.expand_ciphertexts(pk.mask_seed, body, pk.first)
+        m = pk.numel() // self.W
+        assert m >= 1 and pk.numel() == m * self.W, "pk must hold [m][n+1] words"
+        given = mu if mu is not None else base if base is not None else out
+        assert given is not None, "one of mu, base and out must give the batch size"
+        B = given.numel() if mu is not None else given.numel() // self.W
+        assert base is None or base.numel() == B * self.W, "base must hold [B][n+1] words"
+        out = self.empty(B, self.W) if out is None else out
+        assert out.numel() == B * self.W, "out must hold [B][n+1] words"
+        seed = os.urandom(32) if rand_seed is None else self._seed32(rand_seed, "rand_seed")
+        dev = lambda t, cols=None: None if t is None else self._ck_dev(t, cols)
+        _check(self.L, self.L.rs_pk_encrypt_dev(self.h, self._ck_dev(out, self.W), self._ck_dev(pk, self.W), m, dev(mu), dev(base, self.W), B,
+                                                seed, int(first), self._stream()))
+        return out
+
+    def pk_encrypt_bits(self, pk, bits, rand_seed=None, first=0, out=None):
+        """pk_encrypt of the bits (host array of 0 / 1) in the gates' +-1/8 encoding -> int32 CUDA tensor [B][n+1]."""
+        import torch
+        e8 = 1 << 29
+        mu = torch.from_numpy(np.where(np.asarray(bits).ravel() != 0, e8, -e8).astype(np.int32)).to("cuda:%d" % self.device)
+        return self.pk_encrypt(pk, mu, rand_seed, first, out=out)
 
     # ---- device decryption and the noise audit of evaluation keys (INTEGRATION.md section 13; CLIENT side) ----
     def phase(self, ct, key):

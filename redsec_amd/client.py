@@ -177,6 +177,14 @@ class SecretKeySet:
         v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
         return self.encrypt_torus_seeded(v * (1 << 20), SECALPHA, mask_seed, noise_seed, first)
 
+    def public_key(self, m=None, mask_seed=None, noise_seed=None, first=0, alpha=SECALPHA):
+        """A Regev public key for this secret (include/redsec_hip.h rs_pk_encrypt_dev): m seeded encryptions
+        of zero (default keygen.pk_rows(n) = 32 (n + 1) + 256) -> SeededCiphertexts, written and read as an RSC1 file like any other
+        seeded batch. Anyone holding it encrypts with Backend.pk_encrypt / keygen.pk_encrypt; only this secret decrypts."""
+        from . import keygen
+        m = keygen.pk_rows(self.n) if m is None else int(m)
+        return self.encrypt_torus_seeded(np.zeros(m, np.int64), alpha, mask_seed, noise_seed, first)
+
     def phase(self, ct, backend=None):
         """Phases b - sum_k a_k s_k of ct [B][n+1]; with backend= (a redsec_amd.Backend) ct is an int32 CUDA tensor and the phase is
         taken on the device (rs_phase_dev)."""

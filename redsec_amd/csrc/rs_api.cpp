@@ -872,6 +872,28 @@ int rs_expand_ciphertexts_dev(rs_ctx* c, int32_t* ct, const uint8_t* mask_seed, 
   return RS_OK;
 }
 
+// public-key encryption (include/redsec_hip.h; kernel of rs_pubkey.hip): needs no key, the rand seed travels as a kernel argument
+int rs_pk_encrypt_dev(rs_ctx* c, int32_t* ct, const int32_t* pk, size_t m, const int32_t* mu, const int32_t* base, size_t B,
+                      const uint8_t* rand_seed, uint64_t first, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!ct || !pk || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (m < 1 || m > (size_t)INT32_MAX) return fail(RS_ERR_INVALID, "m = %zu is outside 1 .. 2^31 - 1", m);
+  if (B > 0 && B - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + B = %llu + %zu passes 2^64", (unsigned long long)first, B);
+  const size_t row_bytes = ((size_t)c->p.n + 1) * sizeof(int32_t);
+  if (B > (size_t)LONG_MAX / row_bytes || m > (size_t)LONG_MAX / row_bytes || (B + rs::kPkTile - 1) / rs::kPkTile > (size_t)INT32_MAX)
+    return fail(RS_ERR_INVALID, "B = %zu or m = %zu is too large for rows of %zu bytes", B, m, row_bytes);
+  if (B == 0) return RS_OK;
+  rs::PkArgs a{};
+  a.ct = ct; a.pk = pk; a.mu = mu; a.base = base;
+  rs::kg_seed_words(rand_seed, a.seed);
+  a.first = first; a.B = (long)B; a.m = (long)m; a.n = c->p.n;
+  const hipError_t e = rs::launch_pk_encrypt(a, (hipStream_t)stream);
+  for (uint32_t& w : a.seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the seed words does not outlive the call
+  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pk_encrypt failed: %s", hipGetErrorString(e));
+  return RS_OK;
+}
+
 // ---- device decryption and the noise audit of evaluation keys (CLIENT side; kernels of rs_audit.hip, integer arithmetic only) ----
 
 int rs_phase_dev(rs_ctx* c, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim) {

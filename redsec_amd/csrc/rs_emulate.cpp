@@ -1245,6 +1245,21 @@ void rs_emu_expand_ciphertext(const uint8_t* mask_seed, int n, uint64_t first, l
 }
 int rs_emu_ct_tile(int n) { return rs::kg_ct_tile(n); }
 
+// public-key encryption (rs_pk_encrypt_dev): the selection words of ciphertext row `row` through kg_pk_select_block, chunk by chunk
+// as pk_encrypt_kernel walks them -> words_out[ceil(m / 32)] (bit j of the ciphertext = bit j & 31 of word j >> 5; bits at j >= m of
+// the last word are whatever the stream holds), and the kernel's tile of ciphertexts
+void rs_emu_pk_select(const uint8_t* seed, uint64_t row, long m, uint32_t* words_out) {
+  uint32_t key[8];
+  rs::kg_seed_words(seed, key);
+  const long words = (m + 31) / 32;
+  for (long j0 = 0; j0 < m; j0 += rs::kPkChunk) {
+    uint32_t w[16];
+    rs::kg_pk_select_block(key, row, (uint32_t)(j0 / rs::kPkChunk), w);
+    for (int q = 0; q < 16 && j0 / 32 + q < words; ++q) words_out[j0 / 32 + q] = w[q];
+  }
+}
+int rs_emu_pk_tile() { return rs::kPkTile; }
+
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of
 // rs_audit.h, as the kernels of rs_audit.hip place them: a wave of 64 lanes per LWE sample, a workgroup of kAuThreads per bk row ----
 static std::vector<uint32_t> emu_pack_bits(const int32_t* key, int count) {

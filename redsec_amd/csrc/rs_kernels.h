@@ -137,6 +137,19 @@ struct SeededArgs {
 };
 hipError_t launch_encrypt_seeded(const SeededArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_expand_ciphertexts(const SeededArgs& a, int num_cus, hipStream_t st);
+// public-key encryption (rs_pk_encrypt_dev; selection stream and placement of rs_keygen.h): ciphertext i has row first + i, its
+// selection bits the domain-9 words of the rand seed; ct[i] = base[i] + (0, mu[i]) + the selected rows of pk
+struct PkArgs {
+  int32_t* ct;                                        // [B][n+1]; may be `base`
+  const int32_t* pk;                                  // [m][n+1] encryptions of zero
+  const int32_t* mu;                                  // [B] torus messages, or nullptr
+  const int32_t* base;                                // [B][n+1], or nullptr
+  uint32_t seed[8];                                   // the encryptor's rand seed (domain 9): travels as a kernel argument only
+  uint64_t first;
+  long B, m;
+  int n;
+};
+hipError_t launch_pk_encrypt(const PkArgs& a, hipStream_t st);
 // device decryption and the exact noise audit of evaluation keys (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev;
 // per-word arithmetic of rs_audit.h, 32-bit integer only). Secret keys are private device copies packed 32 bits per word.
 constexpr int kAuMaxDim = 16384;                      // largest LWE dimension a packed key in LDS serves (rs_create's limit on n)

@@ -23,7 +23,7 @@
 namespace rs {
 
 // domains (the table of include/redsec_hip.h, rs_keygen_dev)
-enum { kKgLweSecret = 1, kKgTlweSecret = 2, kKgBkMask = 3, kKgBkNoise = 4, kKgKsMask = 5, kKgKsNoise = 6, kKgCtMask = 7, kKgCtNoise = 8 };
+enum { kKgLweSecret = 1, kKgTlweSecret = 2, kKgBkMask = 3, kKgBkNoise = 4, kKgKsMask = 5, kKgKsNoise = 6, kKgCtMask = 7, kKgCtNoise = 8, kKgPkSelect = 9 };
 
 RS_HD uint32_t kg_rotl(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
 RS_HD void kg_quarter(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) {
@@ -127,6 +127,19 @@ RS_HD int kg_ct_tile(int n) {
   return best;
 }
 RS_HD int kg_ct_lds_word(int c, int k, int n) { return c * (n + 1) + k; }
+
+// ---- public-key encryption (rs_pk_encrypt_dev), shared by pk_encrypt_kernel (rs_pubkey.hip) and the lane emulator ----
+
+// Selection bits of ciphertext row `row` for the public-key rows 512 chunk .. 512 chunk + 511: block `chunk` of stream (9, row) of
+// the encryptor's private rand seed. Bit j of the ciphertext (row j of the key is added when it is set) is bit j & 31 of stream word
+// j >> 5, i.e. of w[(j >> 5) & 15] of chunk j >> 9; bits at j >= m are never looked at.
+constexpr int kPkChunk = 512;
+RS_HD void kg_pk_select_block(const uint32_t (&key)[8], uint64_t row, uint32_t chunk, uint32_t (&w)[16]) {
+  kg_chacha_block(key, kKgPkSelect, row, chunk, w);
+}
+// Placement of pk_encrypt_kernel: a workgroup of kPkThreads threads owns kPkTile ciphertexts x kPkThreads words of the row (lane =
+// word), one accumulator per ciphertext in registers; the grid runs over (ciphertext tile, word tile).
+constexpr int kPkTile = 16, kPkThreads = 256;
 
 // seed bytes -> the 8 little-endian key words
 RS_HD void kg_seed_words(const uint8_t* seed, uint32_t (&key)[8]) {

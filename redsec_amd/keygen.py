@@ -40,6 +40,15 @@ row first + i (a uint64):
   body = sum_k a_k s_k + e + mu_i (mod 2^32); expanded, the sample is the usual int32 [B][n+1] with the body at word n. Equal seeds
   are refused; first + B must not pass 2^64; a (mask seed, row) pair must never encrypt two messages.
 
+Public-key encryption (rs_pk_encrypt_dev; include/redsec_hip.h): a public key is m encryptions of zero
+(a seeded batch with mu = 0); ciphertext i of a call has row first + i (a uint64) of the encryptor's PRIVATE rand seed:
+
+  domain 9   selection bits   row first + i   bit j of ciphertext i = (word (j >> 5) of the stream >> (j & 31)) & 1,  j < m
+  ct[i] = (base ? base[i] : 0) + (0, mu ? mu[i] : 0) + sum over j with bit j set of pk[j]      (word-wise mod 2^32)
+
+  Domain 9 is disjoint from domains 1-8. A (rand seed, row) pair must never be used twice; first + B must not pass 2^64.
+  pk_selection / pk_encrypt restate it; pk_rows(n) = 32 (n + 1) + 256 is the default m (n log q + 2 lambda).
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -59,6 +68,7 @@ from . import client
 
 DOMAIN_LWE_SECRET, DOMAIN_TLWE_SECRET, DOMAIN_BK_MASK, DOMAIN_BK_NOISE, DOMAIN_KS_MASK, DOMAIN_KS_NOISE = 1, 2, 3, 4, 5, 6
 DOMAIN_CT_MASK, DOMAIN_CT_NOISE = 7, 8
+DOMAIN_PK_SELECT = 9
 _SIGMA = b"expand 32-byte k"
 
 
@@ -416,6 +426,55 @@ def expand_ciphertexts(mask_seed, body, n, first=0):
     out[:, :int(n)] = ct_masks(mask_seed, n, first, body.size).view(np.int32)
     out[:, int(n)] = body
     return out
+
+
+# ---- public-key encryption (rs_pk_encrypt_dev restated) ----
+
+def pk_rows(n):
+    """Default number m of rows of a public key for LWE dimension n: n log q + 2 lambda with q = 2^32 and lambda = 128 (the textbook
+    leftover-hash-lemma size), counting the body word: 32 (n + 1) + 256."""
+    return 32 * (int(n) + 1) + 256
+
+
+def pk_selection(rand_seed, m, first, B):
+    """Selection bits of ciphertexts first .. first + B - 1 over m public-key rows: the domain-9 stream of the rand seed, bit j =
+    bit j & 31 of word j >> 5 -> uint8 [B][m] of 0 / 1."""
+    m = int(m)
+    if not 1 <= m <= (1 << 31) - 1:
+        raise ValueError("m = %d is outside 1 .. 2^31 - 1" % m)
+    rows = _ct_rows(first, B)
+    words = chacha20_words(rand_seed, DOMAIN_PK_SELECT, rows, (m + 31) // 32).reshape(len(rows), -1)
+    bits = (words[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+    return bits.reshape(len(rows), -1)[:, :m].astype(np.uint8)
+
+
+def pk_encrypt(pk, mu, rand_seed, first=0, base=None, B=None):
+    """rs_pk_encrypt_dev restated: ct[i] = base[i] + (0, mu[i]) + the rows of pk (int32 [m][n+1], encryptions of zero) whose selection
+    bit is set for ciphertext i -> int32 [B][n+1]. mu [B] and base [B][n+1] may each be None; B is taken from mu, else base, else B.
+    The subset sums are taken as exact float64 products of the 0 / 1 matrix with the 16-bit halves of the rows (every partial sum stays
+    below m 2^16 < 2^53), nothing like the device's integer adds."""
+    pk = np.ascontiguousarray(pk, np.int32)
+    assert pk.ndim == 2 and pk.shape[0] >= 1, "pk must hold [m][n+1] words"
+    m, W = pk.shape
+    if mu is not None:
+        mu = np.asarray(mu).astype(np.int64).ravel()
+        B = mu.size
+    if base is not None:
+        base = np.asarray(base, np.int32).reshape(-1, W)
+        B = base.shape[0] if mu is None else B
+        assert base.shape[0] == B, "base must hold [B][n+1] words"
+    B = int(B or 0)
+    u = pk.view(np.uint32)
+    lo, hi = (u & np.uint32(0xFFFF)).astype(np.float64), (u >> np.uint32(16)).astype(np.float64)
+    out = np.empty((B, W), np.uint64)
+    for i0 in range(0, B, 256):
+        sel = pk_selection(rand_seed, m, int(first) + i0, min(256, B - i0)).astype(np.float64)
+        out[i0:i0 + 256] = (sel @ lo).astype(np.uint64) + ((sel @ hi).astype(np.uint64) << np.uint64(16))
+    if base is not None:
+        out += base.view(np.uint32)
+    if mu is not None:
+        out[:, W - 1] += (mu & 0xFFFFFFFF).astype(np.uint64)
+    return (out & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----

@@ -30,7 +30,7 @@ grc=$?
 box_tree=$(cat "gpurun_out/${label}_tree_on_box.txt" 2>/dev/null)
 log="profiles/$ROUND/gpu_suite_${label}.log"
 {
-  echo "# final_check: python -m pytest tests -m gpu -x -q on a fresh MI355X box (gpurun rc $grc)"
+  echo "# final_check: python -m pytest tests -m gpu -x -q on a fresh MI355X box (exit status $grc)"
   echo "# date: $(date -u +%Y-%m-%dT%H:%M:%SZ)"
   echo "# head: $head"
   echo "# git status --short (code paths): clean"
