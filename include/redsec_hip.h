@@ -188,6 +188,39 @@ int rs_expand_ciphertexts_dev(rs_ctx* ctx, int32_t* ct, const uint8_t* mask_seed
 int rs_pk_encrypt_dev(rs_ctx* ctx, int32_t* ct, const int32_t* pk, size_t m, const int32_t* mu, const int32_t* base,
                       size_t B, const uint8_t* rand_seed, uint64_t first, void* stream);
 
+/* Compact RLWE public keys (no reference counterpart). The Regev key above costs 32 (n + 1) + 256 rows and
+ * gives outputs of noise alpha sqrt(m / 2), too much for the 1/4096-scale inputs of the networks. An RLWE public key is ONE ring sample
+ * (a, b = a*S + e) under the ring secret S, negacyclic mod 2^32: a 32-byte mask seed plus the N body words (4 KB at N = 1024). A party
+ * WITHOUT the secret encrypts N messages per ciphertext, (a*u + e1, b*u + e2 + m) with u uniform binary, of phase error e*u + e2 - e1*S:
+ * deviation alpha sqrt(N + 1). The server extracts one LWE sample per coefficient and keyswitches it with the key it has loaded.
+ * Four more streams, disjoint from domains 1-9 (Gaussians as everywhere: Gaussian g from words 4g .. 4g+3, kg_noise32):
+ *   domain 10  public-key mask    row 0          mask seed (public)          a_k = word k, k < N
+ *   domain 11  public-key noise   row 0          owner's noise seed (private) e_k = Gaussian k, k < N
+ *   domain 12  selector u         row first + r  rand seed (private)         u_k = (word (k >> 5) >> (k & 31)) & 1, k < N
+ *   domain 13  encryption noise   row first + r  rand seed                   Gaussians 0 .. N-1 are e1, N .. 2N-1 are e2
+ * Key generation (domains 10, 11) is the owner's and has no device code (redsec_amd/keygen.py rlwe_public_key).
+ *
+ * rs_rlwe_pk_encrypt_dev: R = ceil(count / N) ciphertexts, N the context's ring; ciphertext r has row first + r and carries messages
+ * mu[rN] .. mu[rN + N - 1] in its coefficients, slots at or past count carry 0:
+ *   rlwe[r][0] = a*u_r + e1,   rlwe[r][1] = b*u_r + e2 + m_r      (negacyclic, word-wise mod 2^32)
+ * rlwe DEVICE int32[R][2][N]; pk DEVICE int32[2][N] (a, then b); mu DEVICE int32[count] torus words. rand_seed: HOST, 32 bytes, the
+ * encryptor's PRIVATE randomness, read before the call returns (its host copy is cleared); u exists only in registers and LDS.
+ * stdev: deviation of e1 and e2, any finite value >= 0 (0 is for word-identity tests; policy lives in redsec_amd). Needs no loaded
+ * key. Asynchronous and ordered on `stream`. count = 0 is a no-op that returns RS_OK.
+ * Rule: a (rand seed, row) pair must never be used twice. Security rests on RLWE at the key's alpha with a binary ephemeral secret;
+ * nothing more is claimed (no circuit privacy, no CCA security).
+ * RS_ERR_INVALID: a null rlwe, pk, mu or rand_seed; a negative or non-finite stdev; first + R passing 2^64; a count whose row
+ * arithmetic would overflow. Without a device or context it fails as rs_pk_encrypt_dev does. */
+int rs_rlwe_pk_encrypt_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* pk, const int32_t* mu, size_t count, const uint8_t* rand_seed,
+                           uint64_t first, double stdev, void* stream);
+
+/* rs_rlwe_extract_dev: sample i = rN + c of u is the extraction of coefficient c of ciphertext r, in the convention of
+ * rs_bootstrap_wo_ks_dev's output, so that rs_keyswitch_dev and rs_phase_dev(dim = N) apply unchanged:
+ *   word j = rlwe[r][0][c - j] for j <= c,   word j = -rlwe[r][0][N + c - j] for c < j < N,   word N = rlwe[r][1][c]
+ * u DEVICE int32[count][N+1]; rlwe DEVICE int32[ceil(count / N)][2][N]; u must not overlap rlwe. Needs no key. Asynchronous and
+ * ordered on `stream`. count = 0 is a no-op. RS_ERR_INVALID: a null u or rlwe; a count whose row arithmetic would overflow. */
+int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t count, void* stream);
+
 /* Device decryption and the exact noise audit of evaluation keys. CLIENT side: a server holds no secret.
  * All three are synchronous like rs_keygen_dev and additionally wait for ALL work queued on the context's device, on every stream,
  * before they read their inputs. Secret keys are HOST pointers with words in {0, 1}; their private device copy (packed bits) is

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
-    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev",
+    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev", "rs_rlwe_pk_encrypt_dev", "rs_rlwe_extract_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
@@ -123,6 +123,8 @@ def load_library(path=None):
     L.rs_encrypt_seeded_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, _i32p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_double]
     L.rs_expand_ciphertexts_dev.argtypes = [vp, vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp]
     L.rs_pk_encrypt_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, vp]
+    L.rs_rlwe_pk_encrypt_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, C.c_double, vp]
+    L.rs_rlwe_extract_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.rs_phase_dev.argtypes = [vp, vp, vp, C.c_size_t, _i32p, C.c_int32]
     L.rs_audit_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
     L.rs_audit_compressed_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, C.c_char_p, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
@@ -402,6 +404,57 @@ class Backend:
         e8 = 1 << 29
         mu = torch.from_numpy(np.where(np.asarray(bits).ravel() != 0, e8, -e8).astype(np.int32)).to("cuda:%d" % self.device)
         return self.pk_encrypt(pk, mu, rand_seed, first, out=out)
+
+    # ---- compact RLWE public keys ----
+    def rlwe_pk_encrypt(self, pk, mu, rand_seed=None, first=0, stdev=None, out=None):
+        """Encryption under a compact RLWE public key without the secret (rs_rlwe_pk_encrypt_dev, on torch's current stream): ciphertext
+        r = (a*u_r + e1, b*u_r + e2 + m_r) carries messages mu[rN .. rN + N - 1], the last one padded with zeros; u_r, e1, e2 are row
+        first + r of rand_seed (32 bytes, PRIVATE; default a fresh os.urandom(32) per call: a (rand seed, row) pair must never be used
+        twice). pk: int32 CUDA tensor [2][N] (a, then b) or the client.RlwePublicKey (expanded on the host first). mu: int32 CUDA tensor
+        [count] of torus words. stdev: deviation of e1, e2; default the set's bk_stdev (ValueError on redsec_medium / redsec_large, where
+        it truncates to zero: pass one). -> int32 CUDA tensor [ceil(count / N)][2][N]."""
+        from . import keygen
+        N = self.p.N
+        if hasattr(pk, "mask_seed"):
+            import torch
+            if pk.name != keygen.set_name(self.p):    # same N is not enough: the default deviation is the set's
+                raise ValueError("the public key is of %s, the context of %s" % (pk.name, keygen.set_name(self.p)))
+            pk = torch.from_numpy(pk.expand()).to("cuda:%d" % self.device)
+        assert pk.numel() == 2 * N, "pk must hold [2][N] words"
+        count = mu.numel()
+        R = -(-count // N)
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [ceil(count / N)][2][N] words"
+        stdev = keygen.rlwe_default_stdev(keygen.set_name(self.p)) if stdev is None else float(stdev)
+        seed = os.urandom(32) if rand_seed is None else self._seed32(rand_seed, "rand_seed")
+        _check(self.L, self.L.rs_rlwe_pk_encrypt_dev(self.h, self._ck_dev(out), self._ck_dev(pk), self._ck_dev(mu), count, seed, int(first),
+                                                     stdev, self._stream()))
+        return out
+
+    def rlwe_extract(self, rlwe, count, out=None):
+        """The LWE samples of the first `count` slots of RLWE ciphertexts [R][2][N] (rs_rlwe_extract_dev, on torch's current stream):
+        sample rN + c is coefficient c of ciphertext r under the ring key read as an LWE key, the convention of bootstrap_wo_ks
+        -> int32 CUDA tensor [count][N+1], ready for keyswitch and phase(dim = N)."""
+        N, count = self.p.N, int(count)
+        assert 0 <= count and rlwe.numel() == -(-count // N) * 2 * N, "rlwe must hold [ceil(count / N)][2][N] words"
+        out = self.empty(count, N + 1) if out is None else out
+        assert out.numel() == count * (N + 1), "out must hold [count][N+1] words"
+        _check(self.L, self.L.rs_rlwe_extract_dev(self.h, self._ck_dev(out), self._ck_dev(rlwe), count, self._stream()))
+        return out
+
+    def rlwe_unpack(self, rlwe, count):
+        """rlwe_extract followed by keyswitch (needs the loaded key): the first `count` messages of RLWE ciphertexts as LWE samples
+        under the LWE key -> int32 CUDA tensor [count][n+1], ready for the gates and nets.*.run."""
+        return self.keyswitch(self.rlwe_extract(rlwe, count))
+
+    def rlwe_pk_encrypt_image(self, pk, pixels, preprocess="sign", rand_seed=None, first=0, stdev=None):
+        """rlwe_pk_encrypt of client.SecretKeySet.encrypt_image's messages (2 pixel - 255, or the ReLU nets' pixel / 100 - 1, over
+        4096) for the pixels (host array) -> int32 CUDA tensor [ceil(count / N)][2][N]; the server side is rlwe_unpack(., count)."""
+        import torch
+        px = np.asarray(pixels, dtype=np.int64).ravel()
+        v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
+        mu = torch.from_numpy((v * (1 << 20)).astype(np.int32)).to("cuda:%d" % self.device)
+        return self.rlwe_pk_encrypt(pk, mu, rand_seed, first, stdev)
 
     # ---- device decryption and the noise audit of evaluation keys (INTEGRATION.md section 13; CLIENT side) ----
     def phase(self, ct, key):

@@ -185,6 +185,17 @@ class SecretKeySet:
         m = keygen.pk_rows(self.n) if m is None else int(m)
         return self.encrypt_torus_seeded(np.zeros(m, np.int64), alpha, mask_seed, noise_seed, first)
 
+    def rlwe_public_key(self, mask_seed=None, noise_seed=None, stdev=None):
+        """The compact RLWE public key of this secret's ring key (include/redsec_hip.h rs_rlwe_pk_encrypt_dev; INTEGRATION.md section
+        17): (a, b = a*S + e) with a the domain-10 stream of the public mask seed -> RlwePublicKey (32 bytes + 4N bytes), written and
+        read as an RSP1 file. stdev defaults to the set's bk_stdev; on redsec_medium / redsec_large, where that truncates to zero in a
+        32-bit torus, it must be given (ValueError otherwise: a noise-free key publishes S). Anyone holding the key encrypts with
+        Backend.rlwe_pk_encrypt / keygen.rlwe_pk_encrypt; the server unpacks with the keyswitching key it has loaded."""
+        from . import keygen
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        return RlwePublicKey(self.name, mask_seed, keygen.rlwe_public_key(self.name, self.tlwe_key, mask_seed, noise_seed, stdev))
+
     def phase(self, ct, backend=None):
         """Phases b - sum_k a_k s_k of ct [B][n+1]; with backend= (a redsec_amd.Backend) ct is an int32 CUDA tensor and the phase is
         taken on the device (rs_phase_dev)."""
@@ -282,7 +293,7 @@ def read_tfhe_keyset(f, secret):
 _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
-RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352}
+RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -383,6 +394,58 @@ def read_seeded_ciphertexts(f, n=None):
     if len(rest) % 4:
         raise ValueError("truncated seeded ciphertext file: %d bytes of bodies is not a whole number of words" % len(rest))
     return SeededCiphertexts(name, hn, seed, int(np.frombuffer(first, "<u8")[0]), np.frombuffer(rest, np.int32).copy())
+
+
+class RlwePublicKey:
+    """A compact RLWE public key (include/redsec_hip.h): the set name, the public 32-byte mask seed and the
+    body b = a*S + e (int32 [N], numpy). nbytes: what travels (seed + body)."""
+
+    def __init__(self, name, mask_seed, body):
+        self.name, self.mask_seed = name, bytes(mask_seed)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        self.body = np.ascontiguousarray(body, np.int32).ravel()
+        self.N = PARAM_SETS[name][1]
+        assert self.body.size == self.N, "body must have N = %d words" % self.N
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.N
+
+    def expand(self):
+        """(a, b): the domain-10 mask of the seed, then the body -> int32 [2][N], what rs_rlwe_pk_encrypt_dev takes."""
+        from . import keygen
+        return np.stack([keygen.rlwe_pk_mask(self.mask_seed, self.N), self.body])
+
+
+def write_rlwe_public_key(f, pk, max_stdev=0.012467):
+    """An RSP1 file (binary file object): the RSK1 header with magic RSP1, the 32-byte mask seed, then the N int32 body words.
+    pk: RlwePublicKey."""
+    (n, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = PARAM_SETS[pk.name]
+    h = np.zeros((), _RS_HEADER)
+    h["magic"], h["n"], h["N"], h["k"], h["l"], h["Bgbit"], h["ks_t"], h["ks_basebit"] = RS_MAGIC["RSP1"], n, N, k, l, Bgbit, t, basebit
+    h["lwe_alpha_min"], h["lwe_alpha_max"], h["tlwe_alpha_min"], h["tlwe_alpha_max"] = ks_stdev, max_stdev, bk_stdev, max_stdev
+    f.write(h.tobytes())
+    f.write(pk.mask_seed)
+    f.write(pk.body.tobytes())
+
+
+def read_rlwe_public_key(f):
+    """-> RlwePublicKey of an RSP1 file. Raises ValueError for a truncated file, another magic, a parameter shape no set has, or a
+    body that is not exactly N words."""
+    raw = f.read(_RS_HEADER.itemsize)
+    if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSP1"]:
+        raise ValueError("not an RLWE public key (RSP1) file")
+    if len(raw) < _RS_HEADER.itemsize:
+        raise ValueError("truncated RLWE public key file: short header")
+    h = np.frombuffer(raw, _RS_HEADER)[0]
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    if name is None:
+        raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,))
+    seed, rest = f.read(32), f.read()
+    if len(seed) < 32 or len(rest) != 4 * shape[0]:
+        raise ValueError("truncated RLWE public key file: %d bytes after the header, expected 32 + %d" % (len(seed) + len(rest), 4 * shape[0]))
+    return RlwePublicKey(name, seed, np.frombuffer(rest, np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

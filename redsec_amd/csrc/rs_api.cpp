@@ -28,6 +28,7 @@
 #include "rs_general.h"
 #include "rs_kernels.h"
 #include "rs_keygen.h"
+#include "rs_rlwe.h"
 
 namespace {
 
@@ -891,6 +892,43 @@ int rs_pk_encrypt_dev(rs_ctx* c, int32_t* ct, const int32_t* pk, size_t m, const
   const hipError_t e = rs::launch_pk_encrypt(a, (hipStream_t)stream);
   for (uint32_t& w : a.seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the seed words does not outlive the call
   if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pk_encrypt failed: %s", hipGetErrorString(e));
+  return RS_OK;
+}
+
+// compact RLWE public keys (include/redsec_hip.h; kernels of rs_rlwe.hip): neither call needs a key, the ring is the context's
+int rs_rlwe_pk_encrypt_dev(rs_ctx* c, int32_t* rlwe, const int32_t* pk, const int32_t* mu, size_t count, const uint8_t* rand_seed,
+                           uint64_t first, double stdev, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!rlwe || !pk || !mu || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kRlMinN || N > (size_t)rs::kRlMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  const size_t R = count / N + (count % N ? 1 : 0), tiles = N / rs::kRlTile;
+  if (R > 0 && R - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + R = %llu + %zu passes 2^64", (unsigned long long)first, R);
+  if (count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N || R > (size_t)INT32_MAX / (2 * tiles))
+    return fail(RS_ERR_INVALID, "count = %zu is too large for ciphertexts of 2 x %zu words", count, N);
+  if (count == 0) return RS_OK;
+  rs::RlweEncArgs a{};
+  a.rlwe = rlwe; a.pk = pk; a.mu = mu;
+  rs::kg_seed_words(rand_seed, a.seed);
+  a.first = first; a.count = (long)count; a.N = (int)N; a.sigma = stdev;
+  const hipError_t e = rs::launch_rlwe_pk_encrypt(a, (hipStream_t)stream);
+  for (uint32_t& w : a.seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the seed words does not outlive the call
+  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_rlwe_pk_encrypt failed: %s", hipGetErrorString(e));
+  return RS_OK;
+}
+
+int rs_rlwe_extract_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t count, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!u || !rlwe) return fail(RS_ERR_INVALID, "null pointer");
+  const size_t row_bytes = ((size_t)c->p.N + 1) * sizeof(int32_t);
+  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)INT32_MAX)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
+  if (count == 0) return RS_OK;
+  const rs::RlweExtractArgs x{u, rlwe, (long)count, c->p.N};
+  RS_HIP(rs::launch_rlwe_extract(x, (hipStream_t)stream));
   return RS_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "rs_general.h"
 #include "rs_host.h"
 #include "rs_keygen.h"
+#include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
 #include "rs_ntt.h"
@@ -1259,6 +1260,79 @@ void rs_emu_pk_select(const uint8_t* seed, uint64_t row, long m, uint32_t* words
   }
 }
 int rs_emu_pk_tile() { return rs::kPkTile; }
+
+// ---- compact RLWE public keys (rs_rlwe_pk_encrypt_dev, rs_rlwe_extract_dev) through the functions of rs_rlwe.h ----
+// the selector words of ciphertext row `row` through rl_select_block, block by block as rlwe_pk_encrypt_kernel stages them
+// -> words_out[N / 32] (u_k = bit k & 31 of word k >> 5)
+void rs_emu_rlwe_select(const uint8_t* seed, uint64_t row, int N, uint32_t* words_out) {
+  uint32_t key[8];
+  rs::kg_seed_words(seed, key);
+  for (int blk = 0; blk < N / 512; ++blk) {
+    uint32_t w[16];
+    rs::rl_select_block(key, row, (uint32_t)blk, w);
+    for (int q = 0; q < 16; ++q) words_out[16 * blk + q] = w[q];
+  }
+}
+int rs_emu_rlwe_term_index(int N, int k, int j) { return rs::rl_term_index(N, k, j); }
+// source index in the mask polynomial of word j < N of the sample of coefficient c; *negate: the word is the negated coefficient
+int rs_emu_rlwe_extract_word(int N, int c, int j, int* negate) {
+  bool neg;
+  const int idx = rs::rl_extract_index(N, c, j, neg);
+  *negate = neg ? 1 : 0;
+  return idx;
+}
+int rs_emu_rlwe_tile() { return rs::kRlTile; }
+// rlwe_pk_encrypt_kernel, workgroup by workgroup and thread by thread as the kernel places them: the window of ext = (-p, p) a tile
+// stages, one 4-word chunk per thread and four selector bits, the masked adds on the seven live words, noise and message at the store
+void rs_emu_rlwe_pk_encrypt(const int32_t* pk, const int32_t* mu, long count, int N, const uint8_t* seed, uint64_t first, double sigma,
+                            int32_t* rlwe) {
+  uint32_t key[8];
+  rs::kg_seed_words(seed, key);
+  const long R = (count + N - 1) / N;
+  const int tiles = N / rs::kRlTile;
+  std::vector<uint32_t> win((size_t)N + rs::kRlTile), sel((size_t)N / 32);
+  for (long blk = 0; blk < R * 2 * tiles; ++blk) {
+    const int tile = (int)(blk % tiles), poly = (int)((blk / tiles) & 1);
+    const long r = blk / (2 * tiles);
+    const int k0 = tile * rs::kRlTile;
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(pk) + (size_t)poly * N;
+    for (int i = 0; i < N + rs::kRlTile; ++i) win[i] = rs::rl_ext_word(p, N, k0 + i);
+    rs_emu_rlwe_select(seed, first + (uint64_t)r, N, sel.data());
+    for (int t = 0; t < rs::kRlThreads; ++t) {
+      uint32_t acc[rs::kRlKpt] = {0u, 0u, 0u, 0u};
+      int c4 = t + N / 4;
+      const uint32_t* hi = &win[4 * (size_t)c4];
+      for (int wd = 0; wd < N / 32; ++wd)
+        for (int g = 0; g < 8; ++g) {
+          const uint32_t* lo = &win[4 * (size_t)(--c4)];
+          const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          for (int b = 0; b < 4; ++b) {
+            const uint32_t m = 0u - ((sel[wd] >> (4 * g + b)) & 1u);
+            for (int q = 0; q < rs::kRlKpt; ++q) acc[q] += w[4 + q - b] & m;
+          }
+          hi = lo;
+        }
+      const int k = k0 + rs::kRlKpt * t;
+      int32_t e[4];
+      rs::rl_noise4(key, first + (uint64_t)r, poly, N, k, sigma, e);
+      for (int q = 0; q < rs::kRlKpt; ++q) {
+        uint32_t v = acc[q] + (uint32_t)e[q];
+        const long i = r * (long)N + k + q;
+        if (poly == 1 && i < count) v += (uint32_t)mu[i];
+        rlwe[((size_t)r * 2 + poly) * N + k + q] = (int32_t)v;
+      }
+    }
+  }
+}
+// rlwe_extract_kernel: rlwe [ceil(count / N)][2][N] -> u [count][N+1]
+void rs_emu_rlwe_extract(const int32_t* rlwe, long count, int N, int32_t* u) {
+  for (long i = 0; i < count; ++i) {
+    const long r = i / N;
+    const int c = (int)(i - r * N);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rlwe) + (size_t)r * 2 * N;
+    for (int j = 0; j <= N; ++j) u[(size_t)i * (N + 1) + j] = (int32_t)rs::rl_extract_word(a, a + N, N, c, j);
+  }
+}
 
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of
 // rs_audit.h, as the kernels of rs_audit.hip place them: a wave of 64 lanes per LWE sample, a workgroup of kAuThreads per bk row ----

@@ -150,6 +150,26 @@ struct PkArgs {
   int n;
 };
 hipError_t launch_pk_encrypt(const PkArgs& a, hipStream_t st);
+// compact RLWE public keys (rs_rlwe_pk_encrypt_dev, rs_rlwe_extract_dev; streams, placement and index arithmetic of rs_rlwe.h):
+// ciphertext r has row first + r of the rand seed and carries messages rN .. rN + N - 1
+struct RlweEncArgs {
+  int32_t* rlwe;                                      // [ceil(count / N)][2][N]
+  const int32_t* pk;                                  // [2][N]: a, then b = a*S + e
+  const int32_t* mu;                                  // [count] torus messages
+  uint32_t seed[8];                                   // the encryptor's rand seed (domains 12, 13): travels as a kernel argument only
+  uint64_t first;
+  long count;
+  int N;
+  double sigma;
+};
+hipError_t launch_rlwe_pk_encrypt(const RlweEncArgs& a, hipStream_t st);
+struct RlweExtractArgs {
+  int32_t* u;                                         // [count][N+1]
+  const int32_t* rlwe;                                // [ceil(count / N)][2][N]
+  long count;
+  int N;
+};
+hipError_t launch_rlwe_extract(const RlweExtractArgs& x, hipStream_t st);
 // device decryption and the exact noise audit of evaluation keys (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev;
 // per-word arithmetic of rs_audit.h, 32-bit integer only). Secret keys are private device copies packed 32 bits per word.
 constexpr int kAuMaxDim = 16384;                      // largest LWE dimension a packed key in LDS serves (rs_create's limit on n)

@@ -49,6 +49,20 @@ Public-key encryption (rs_pk_encrypt_dev; include/redsec_hip.h; INTEGRATION.md s
   Domain 9 is disjoint from domains 1-8. A (rand seed, row) pair must never be used twice; first + B must not pass 2^64.
   pk_selection / pk_encrypt restate it; pk_rows(n) = 32 (n + 1) + 256 is the default m (n log q + 2 lambda).
 
+Compact RLWE public keys (rs_rlwe_pk_encrypt_dev, rs_rlwe_extract_dev; include/redsec_hip.h): the key
+is one ring sample (a, b = a*S + e) under the ring secret S, negacyclic mod 2^32; ciphertext r of a call has row first + r of the
+encryptor's PRIVATE rand seed and carries N messages:
+
+  domain 10  public-key mask    row 0          mask seed (public)             a_k = word k, k < N
+  domain 11  public-key noise   row 0          owner's noise seed (private)   e_k = Gaussian k (words 4k .. 4k+3), k < N
+  domain 12  selector u         row first + r  rand seed (private)            u_k = (word (k >> 5) >> (k & 31)) & 1, k < N
+  domain 13  encryption noise   row first + r  rand seed                      Gaussians 0 .. N-1 are e1, N .. 2N-1 are e2
+  rlwe[r] = (a*u_r + e1, b*u_r + e2 + m_r), m_r = mu[rN .. rN + N - 1] padded with zeros; extraction of coefficient c: word j =
+  a'[c - j] (j <= c), -a'[N + c - j] (j > c), word N = b'[c].
+
+  Domains 10-13 are disjoint from domains 1-9. Equal mask and noise seeds are refused; a (rand seed, row) pair must never be used
+  twice. rlwe_pk_mask / rlwe_public_key / rlwe_pk_selector / rlwe_pk_encrypt / rlwe_extract / rlwe_phase restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -69,6 +83,7 @@ from . import client
 DOMAIN_LWE_SECRET, DOMAIN_TLWE_SECRET, DOMAIN_BK_MASK, DOMAIN_BK_NOISE, DOMAIN_KS_MASK, DOMAIN_KS_NOISE = 1, 2, 3, 4, 5, 6
 DOMAIN_CT_MASK, DOMAIN_CT_NOISE = 7, 8
 DOMAIN_PK_SELECT = 9
+DOMAIN_RLWE_MASK, DOMAIN_RLWE_NOISE, DOMAIN_RLWE_SELECT, DOMAIN_RLWE_ENC_NOISE = 10, 11, 12, 13
 _SIGMA = b"expand 32-byte k"
 
 
@@ -475,6 +490,115 @@ def pk_encrypt(pk, mu, rand_seed, first=0, base=None, B=None):
     if mu is not None:
         out[:, W - 1] += (mu & 0xFFFFFFFF).astype(np.uint64)
     return (out & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+
+
+# ---- compact RLWE public keys (rs_rlwe_pk_encrypt_dev / rs_rlwe_extract_dev restated) ----
+
+MIN_STDEV = 2.0 ** -31   # below this dtot32 truncates most noise words to zero: a noise-free (a, a*S) publishes S by linear algebra
+
+
+def rlwe_default_stdev(name):
+    """The default deviation of an RLWE public key and of its ciphertexts: the set's bk_stdev (the ring's alpha). ValueError on the
+    sets whose bk_stdev truncates to zero in a 32-bit torus (redsec_medium, redsec_large): they need an explicit stdev."""
+    stdev = _shape(name)["bk_stdev"]
+    if stdev < MIN_STDEV:
+        raise ValueError("the bk_stdev of %s (%.3g) truncates to zero in a 32-bit torus and a noise-free key publishes the secret: "
+                         "pass an explicit stdev >= 2^-31" % (name, stdev))
+    return stdev
+
+
+def rlwe_pk_mask(mask_seed, N):
+    """The mask polynomial a of an RLWE public key: words 0 .. N-1 of stream (10, 0) of the mask seed -> int32 [N]."""
+    return chacha20_words(mask_seed, DOMAIN_RLWE_MASK, 0, int(N)).view(np.int32)
+
+
+def rlwe_public_key(name, tlwe_key, mask_seed, noise_seed, stdev=None):
+    """The body b = a*S + e (negacyclic, mod 2^32) of the RLWE public key of the ring secret tlwe_key: a = rlwe_pk_mask(mask_seed, N),
+    e = the N Gaussians of stream (11, 0) of the private noise seed -> int32 [N]. stdev defaults to rlwe_default_stdev(name)."""
+    _check_seeds(mask_seed, noise_seed)
+    stdev = rlwe_default_stdev(name) if stdev is None else float(stdev)
+    N = _shape(name)["N"]
+    S = np.asarray(tlwe_key).ravel()
+    assert S.size == N, "tlwe_key must have N = %d words" % N
+    a = rlwe_pk_mask(mask_seed, N).view(np.uint32)
+    b = _times_binary(a[None, :], S)[0]
+    with np.errstate(over="ignore"):
+        b = b + noise32(chacha20_words(noise_seed, DOMAIN_RLWE_NOISE, 0, 4 * N), stdev).view(np.uint32)
+    return b.view(np.int32)
+
+
+def _rlwe_rows(first, count, N):
+    count = int(count)
+    if count < 0:
+        raise ValueError("count = %d is negative" % count)
+    return _ct_rows(first, -(-count // int(N)))
+
+
+def rlwe_pk_selector(rand_seed, N, first, R):
+    """The binary polynomials u of ciphertexts first .. first + R - 1: the domain-12 stream of the rand seed, u_k = bit k & 31 of word
+    k >> 5 -> uint8 [R][N] of 0 / 1."""
+    rows = _ct_rows(first, R)
+    words = chacha20_words(rand_seed, DOMAIN_RLWE_SELECT, rows, int(N) // 32).reshape(len(rows), -1)
+    bits = (words[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+    return bits.reshape(len(rows), -1).astype(np.uint8)
+
+
+def rlwe_pk_noise(rand_seed, N, first, R, stdev):
+    """(e1, e2) of ciphertexts first .. first + R - 1: Gaussians 0 .. N-1 and N .. 2N-1 of stream (13, row) -> int32 [R][2][N]."""
+    rows = _ct_rows(first, R)
+    if stdev == 0 or len(rows) == 0:
+        return np.zeros((len(rows), 2, int(N)), np.int32)
+    return noise32(chacha20_words(rand_seed, DOMAIN_RLWE_ENC_NOISE, rows, 8 * int(N)), stdev).reshape(len(rows), 2, int(N))
+
+
+def rlwe_pk_encrypt(pk, mu, rand_seed, first=0, *, stdev):
+    """rs_rlwe_pk_encrypt_dev restated: ciphertext r = (a*u_r + e1, b*u_r + e2 + m_r) for pk = (a, b) int32 [2][N] and the torus words
+    mu [count], N per ciphertext, the last one padded with zeros -> int32 [ceil(count / N)][2][N]. The products are _times_binary's
+    (float64 matrix products on 16-bit halves for N <= 1024, shifted slices above): nothing like the device's tiled integer adds."""
+    pk = np.ascontiguousarray(pk, np.int32)
+    assert pk.ndim == 2 and pk.shape[0] == 2, "pk must hold [2][N] words"
+    N = pk.shape[1]
+    mu = np.asarray(mu).astype(np.int64).ravel()
+    rows = _rlwe_rows(first, mu.size, N)
+    R = len(rows)
+    m = np.zeros(R * N, np.uint32)
+    m[:mu.size] = (mu & 0xFFFFFFFF).astype(np.uint32)
+    out = np.empty((R, 2, N), np.uint32)
+    for r in range(R):
+        u = rlwe_pk_selector(rand_seed, N, int(rows[r]), 1)[0]
+        out[r] = _times_binary(pk.view(np.uint32), u)
+    with np.errstate(over="ignore"):
+        out += rlwe_pk_noise(rand_seed, N, first, R, stdev).view(np.uint32)
+        out[:, 1, :] += m.reshape(R, N)
+    return out.view(np.int32)
+
+
+def rlwe_extract(rlwe, count):
+    """rs_rlwe_extract_dev restated: sample i = rN + c is the LWE sample of coefficient c of ciphertext r under the ring key read as
+    an LWE key -> int32 [count][N+1]."""
+    rlwe = np.ascontiguousarray(rlwe, np.int32)
+    N = rlwe.shape[-1]
+    rlwe = rlwe.reshape(-1, 2, N)
+    count = int(count)
+    assert 0 <= count <= rlwe.shape[0] * N, "count exceeds the slots of the ciphertexts"
+    out = np.empty((count, N + 1), np.int32)
+    j = np.arange(N)[None, :]
+    with np.errstate(over="ignore"):
+        for r in range(-(-count // N)):
+            c = np.arange(min(N, count - r * N))[:, None]
+            words = rlwe[r, 0].view(np.uint32)[(c - j) % N]
+            out[r * N:r * N + len(c), :N] = np.where(j > c, np.uint32(0) - words, words).view(np.int32)
+            out[r * N:r * N + len(c), N] = rlwe[r, 1, :len(c)]
+    return out
+
+
+def rlwe_phase(rlwe, tlwe_key):
+    """Phases b' - a'*S of RLWE ciphertexts [R][2][N] under the ring secret -> int32 [R][N]."""
+    rlwe = np.ascontiguousarray(rlwe, np.int32)
+    N = rlwe.shape[-1]
+    rlwe = rlwe.reshape(-1, 2, N).view(np.uint32)
+    with np.errstate(over="ignore"):
+        return (rlwe[:, 1] - _times_binary(np.ascontiguousarray(rlwe[:, 0]), np.asarray(tlwe_key).ravel())).view(np.int32)
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
