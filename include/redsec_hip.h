@@ -221,6 +221,33 @@ int rs_rlwe_pk_encrypt_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* pk, const 
  * ordered on `stream`. count = 0 is a no-op. RS_ERR_INVALID: a null u or rlwe; a count whose row arithmetic would overflow. */
 int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t count, void* stream);
 
+/* Packed results (TFHE's TLWE keyswitch with the identity function): a public keyswitch from the LWE key s
+ * to the ring key S that puts up to N LWE samples into the coefficients of ONE RLWE ciphertext of section 17's format, 8N bytes
+ * instead of N 4 (n + 1). The packing key holds, per key bit s_i and digit j, a ring sample under S whose message is s_i times the
+ * digit's weight; two more streams, disjoint from domains 1-13 (owner's side only, redsec_amd/keygen.py pack_key; no device code):
+ *   domain 14  packing-key mask    row i t + j   mask seed (public)             a_ij[k] = word k, k < N
+ *   domain 15  packing-key noise   row i t + j   owner's noise seed (private)   e_ij[k] = Gaussian k (words 4k .. 4k+3, kg_noise32)
+ *
+ * rs_pack_dev: R = ceil(count / N) ciphertexts, N and n the context's; ciphertext r packs samples rN .. rN + count_r - 1 into
+ * coefficients 0 .. count_r - 1, count_r = min(N, count - rN). Word-wise mod 2^32, negacyclic products, the digit convention of
+ * lweKeySwitch / rs_keyswitch_dev:
+ *   K[i][j]   = (a_ij, b_ij = a_ij*S + e_ij + s_i 2^(32-(j+1) basebit) X^0)        i < n, j < t
+ *   abar      = a + off,  off = 2^(31 - t basebit)  (0 when t basebit = 32)
+ *   D_ij(X)   = sum over c < count_r of ((abar_i of sample rN+c) >> (32-(j+1) basebit) & (2^basebit - 1)) X^c
+ *   rlwe[r]   = (0, sum_c b_(rN+c) X^c) - sum_{i,j} D_ij(X) K[i][j]
+ * Under S, coefficient c of the result has phase (b - a*S) equal to the phase of sample rN + c plus the packing error, of variance
+ *   sigma^2 = n t count_r (2^basebit - 1)(2^(basebit+1) - 1)/6 sigma_k^2  +  (n/2) 2^(-2 t basebit)/12
+ * (sigma_k the key's deviation; the first term is the key noise under the digits, the second the digits' rounding). Slots at or
+ * past count hold noise around 0. rs_rlwe_extract_dev + rs_keyswitch_dev turn a packed ciphertext back into LWE inputs, and
+ * rs_rlwe_extract_dev + rs_phase_dev(dim = N) decrypt it on the device.
+ * ct DEVICE int32[count][n+1]; rlwe DEVICE int32[R][2][N], must not overlap ct; pack_key DEVICE int32[n][t][2][N]. Integer
+ * arithmetic only, exact: the words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on
+ * `stream`; no allocation. count = 0 is a no-op that returns RS_OK.
+ * RS_ERR_INVALID: a null rlwe, ct or pack_key; basebit outside 1 .. 8; t < 1; t basebit > 32; a count whose row arithmetic would
+ * overflow. Without a device or context it fails as rs_rlwe_extract_dev does. */
+int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
+                const int32_t* pack_key, int32_t basebit, int32_t t, void* stream);
+
 /* Device decryption and the exact noise audit of evaluation keys. CLIENT side: a server holds no secret.
  * All three are synchronous like rs_keygen_dev and additionally wait for ALL work queued on the context's device, on every stream,
  * before they read their inputs. Secret keys are HOST pointers with words in {0, 1}; their private device copy (packed bits) is

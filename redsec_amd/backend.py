@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rs_params_redsec_small", "rs_params_redsec_medium", "rs_params_redsec_large", "rs_split_bound",
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
-    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev", "rs_rlwe_pk_encrypt_dev", "rs_rlwe_extract_dev",
+    "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev", "rs_rlwe_pk_encrypt_dev", "rs_rlwe_extract_dev", "rs_pack_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
@@ -125,6 +125,7 @@ def load_library(path=None):
     L.rs_pk_encrypt_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, vp]
     L.rs_rlwe_pk_encrypt_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, C.c_double, vp]
     L.rs_rlwe_extract_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    L.rs_pack_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_phase_dev.argtypes = [vp, vp, vp, C.c_size_t, _i32p, C.c_int32]
     L.rs_audit_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
     L.rs_audit_compressed_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, C.c_char_p, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
@@ -455,6 +456,39 @@ class Backend:
         v = (px // 100 - 1) if preprocess == "relu" else 2 * px - 255
         mu = torch.from_numpy((v * (1 << 20)).astype(np.int32)).to("cuda:%d" % self.device)
         return self.rlwe_pk_encrypt(pk, mu, rand_seed, first, stdev)
+
+    # ---- packed results ----
+    def pack(self, ct, key, basebit=None, t=None, out=None):
+        """LWE samples ct (int32 CUDA tensor [count][n+1]) keyswitched into the coefficients of RLWE ciphertexts (rs_pack_dev, on
+        torch's current stream): ciphertext r packs samples rN .. rN + N - 1 -> int32 CUDA tensor [ceil(count / N)][2][N], the format
+        of section 17 (rlwe_extract, rlwe_unpack, client.SecretKeySet.packed_phase). key: a client.PackingKey (expanded on the host
+        and uploaded: keep the tensor of upload_packing_key for repeated calls; ValueError for a key of another set or another n) or
+        an int32 CUDA tensor [n][t][2][N] with explicit basebit and t. Needs no loaded key."""
+        from . import keygen
+        N, n = self.p.N, self.p.n
+        if hasattr(key, "mask_seed"):
+            basebit, t, key = key.basebit, key.t, self.upload_packing_key(key)
+        if basebit is None or t is None:
+            raise ValueError("a packing key given as a tensor needs explicit basebit and t")
+        basebit, t = keygen._check_digits(basebit, t)
+        assert key.numel() == n * t * 2 * N, "key must hold [n][t][2][N] words"
+        assert ct.numel() % (n + 1) == 0, "ct must hold [count][n+1] words"
+        count = ct.numel() // (n + 1)
+        R = -(-count // N)
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [ceil(count / N)][2][N] words"
+        _check(self.L, self.L.rs_pack_dev(self.h, self._ck_dev(out), self._ck_dev(ct), count, self._ck_dev(key), basebit, t, self._stream()))
+        return out
+
+    def upload_packing_key(self, key):
+        """The expanded client.PackingKey on this context's device -> int32 CUDA tensor [n][t][2][N] (pass it to pack with key.basebit
+        and key.t). ValueError for a key of another set or another n."""
+        import torch
+        from . import keygen
+        if key.name != keygen.set_name(self.p) or key.n != self.p.n:
+            raise ValueError("the packing key is of %s with n = %d, the context of %s with n = %d"
+                             % (key.name, key.n, keygen.set_name(self.p), self.p.n))
+        return torch.from_numpy(key.expand()).to("cuda:%d" % self.device)
 
     # ---- device decryption and the noise audit of evaluation keys (INTEGRATION.md section 13; CLIENT side) ----
     def phase(self, ct, key):

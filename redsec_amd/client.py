@@ -72,6 +72,15 @@ def _mul_by_binary_poly(A, T):
     return _wrap32(((ph << 16) + pl).astype(np.uint64))
 
 
+def _round_phase(ph, msize):
+    """client/decrypt_image.cpp:52-58: phases (int32) rounded to multiples of 1/msize, signed."""
+    ph = np.asarray(ph, np.int32).view(np.uint32).astype(np.uint64)
+    interv = 1 << (32 - int(np.log2(msize)))
+    m = ((ph + interv // 2) // interv) % msize
+    m = m.astype(np.int64)
+    return np.where(m > msize // 2, m - msize, m)
+
+
 class SecretKeySet:
     """TFheGateBootstrappingSecretKeySet: lwe_key, tlwe_key and the cloud (evaluation) key."""
 
@@ -196,6 +205,38 @@ class SecretKeySet:
         noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
         return RlwePublicKey(self.name, mask_seed, keygen.rlwe_public_key(self.name, self.tlwe_key, mask_seed, noise_seed, stdev))
 
+    def packing_key(self, basebit=None, t=None, mask_seed=None, noise_seed=None, stdev=None):
+        """The packing key from this secret's LWE key to its ring key (include/redsec_hip.h rs_pack_dev)
+        -> PackingKey (32 bytes + 4 n t N bytes), written and read as an RSK1 file. basebit, t default to keygen.pack_default(name),
+        stdev to the set's bk_stdev (ValueError where that truncates to zero: pass one). A server holding the key packs results with
+        Backend.pack; only this secret decrypts them (packed_phase, decrypt_packed_bits, decrypt_packed_ints)."""
+        from . import keygen
+        d = keygen.pack_default(self.name)
+        basebit, t = d[0] if basebit is None else int(basebit), d[1] if t is None else int(t)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        body = keygen.pack_key(self.name, self.lwe_key, self.tlwe_key, mask_seed, noise_seed, basebit, t, stdev)
+        return PackingKey(self.name, self.n, basebit, t, mask_seed, body)
+
+    def packed_phase(self, rlwe, count, backend=None):
+        """Phases of the first `count` slots of packed ciphertexts [R][2][N] under the ring key (slot rN + c is coefficient c of
+        ciphertext r) -> int32 [count]; with backend= rlwe is an int32 CUDA tensor and the phase is taken on the device
+        (rs_rlwe_extract_dev + rs_phase_dev with dim = N)."""
+        from . import keygen
+        count = int(count)
+        if backend is not None:
+            return backend.phase(backend.rlwe_extract(rlwe, count), self.tlwe_key).cpu().numpy()
+        ph = keygen.rlwe_phase(rlwe, self.tlwe_key).ravel()
+        assert 0 <= count <= ph.size, "count exceeds the slots of the ciphertexts"
+        return ph[:count]
+
+    def decrypt_packed_bits(self, rlwe, count, backend=None):
+        return (self.packed_phase(rlwe, count, backend) > 0).astype(np.int64)
+
+    def decrypt_packed_ints(self, rlwe, count, msize=MSG_SPACE, backend=None):
+        """decrypt_ints of the first `count` slots of packed ciphertexts."""
+        return _round_phase(self.packed_phase(rlwe, count, backend), msize)
+
     def phase(self, ct, backend=None):
         """Phases b - sum_k a_k s_k of ct [B][n+1]; with backend= (a redsec_amd.Backend) ct is an int32 CUDA tensor and the phase is
         taken on the device (rs_phase_dev)."""
@@ -210,11 +251,7 @@ class SecretKeySet:
 
     def decrypt_ints(self, ct, msize=MSG_SPACE, backend=None):
         """client/decrypt_image.cpp:52-58: round the phase to multiples of 1/msize, signed."""
-        ph = self.phase(ct, backend).view(np.uint32).astype(np.uint64)
-        interv = 1 << (32 - int(np.log2(msize)))
-        m = ((ph + interv // 2) // interv) % msize
-        m = m.astype(np.int64)
-        return np.where(m > msize // 2, m - msize, m)
+        return _round_phase(self.phase(ct, backend), msize)
 
     def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
@@ -446,6 +483,72 @@ def read_rlwe_public_key(f):
     if len(seed) < 32 or len(rest) != 4 * shape[0]:
         raise ValueError("truncated RLWE public key file: %d bytes after the header, expected 32 + %d" % (len(seed) + len(rest), 4 * shape[0]))
     return RlwePublicKey(name, seed, np.frombuffer(rest, np.int32).copy())
+
+
+class PackingKey:
+    """A packing key (include/redsec_hip.h rs_pack_dev): the set name, the LWE dimension n, the digit
+    shape (basebit, t), the public 32-byte mask seed and the bodies b_ij (int32 [n][t][N], numpy). nbytes: what travels (seed +
+    bodies); the masks are the domain-14 streams of the seed."""
+
+    def __init__(self, name, n, basebit, t, mask_seed, body):
+        self.name, self.n, self.basebit, self.t, self.mask_seed = name, int(n), int(basebit), int(t), bytes(mask_seed)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        assert 1 <= self.basebit <= 8 and self.t >= 1 and self.t * self.basebit <= 32, "basebit in 1 .. 8, t >= 1, t basebit <= 32"
+        self.N = PARAM_SETS[name][1]
+        self.body = np.ascontiguousarray(body, np.int32).reshape(-1)
+        assert self.body.size == self.n * self.t * self.N, "body must have n t N = %d words" % (self.n * self.t * self.N)
+        self.body = self.body.reshape(self.n, self.t, self.N)
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.n * self.t * self.N
+
+    def expand(self):
+        """K[i][j] = (a_ij, b_ij): the domain-14 masks of the seed beside the bodies -> int32 [n][t][2][N], what rs_pack_dev takes."""
+        from . import keygen
+        out = np.empty((self.n, self.t, 2, self.N), np.int32)
+        out[:, :, 0] = keygen.pack_key_mask(self.mask_seed, self.N, np.arange(self.n * self.t)).reshape(self.n, self.t, self.N)
+        out[:, :, 1] = self.body
+        return out
+
+
+def write_packing_key(f, key, max_stdev=0.012467):
+    """A packing key file (binary file object): the RS header with magic RSK1 -- its n the key's LWE dimension, its ks_t and
+    ks_basebit the set's -- then int32 basebit, int32 t of the packing digits, the 32-byte mask seed and the n t N int32 body words.
+    key: PackingKey."""
+    (_, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = PARAM_SETS[key.name]
+    h = np.zeros((), _RS_HEADER)
+    h["magic"], h["n"], h["N"], h["k"], h["l"], h["Bgbit"], h["ks_t"], h["ks_basebit"] = RS_MAGIC["RSK1"], key.n, N, k, l, Bgbit, t, basebit
+    h["lwe_alpha_min"], h["lwe_alpha_max"], h["tlwe_alpha_min"], h["tlwe_alpha_max"] = ks_stdev, max_stdev, bk_stdev, max_stdev
+    f.write(h.tobytes())
+    f.write(np.array([key.basebit, key.t], "<i4").tobytes())
+    f.write(key.mask_seed)
+    f.write(key.body.tobytes())
+
+
+def read_packing_key(f):
+    """-> PackingKey of a packing key file. Raises ValueError for a truncated file, another magic, a parameter shape no set has, an n
+    below 1, digits outside basebit 1 .. 8, t >= 1, t basebit <= 32, or a body that is not exactly n t N words."""
+    raw = f.read(_RS_HEADER.itemsize)
+    if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSK1"]:
+        raise ValueError("not a packing key (RSK1) file")
+    if len(raw) < _RS_HEADER.itemsize:
+        raise ValueError("truncated packing key file: short header")
+    h = np.frombuffer(raw, _RS_HEADER)[0]
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    if name is None:
+        raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,))
+    n = int(h["n"])
+    digits, seed, rest = f.read(8), f.read(32), f.read()
+    if len(digits) < 8 or len(seed) < 32:
+        raise ValueError("truncated packing key file: %d bytes after the header" % (len(digits) + len(seed)))
+    basebit, t = (int(v) for v in np.frombuffer(digits, "<i4"))
+    if n < 1 or not (1 <= basebit <= 8 and t >= 1 and t * basebit <= 32):
+        raise ValueError("packing key file with n = %d, basebit = %d, t = %d" % (n, basebit, t))
+    if len(rest) != 4 * n * t * shape[0]:
+        raise ValueError("truncated packing key file: %d body bytes, expected %d" % (len(rest), 4 * n * t * shape[0]))
+    return PackingKey(name, n, basebit, t, seed, np.frombuffer(rest, np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

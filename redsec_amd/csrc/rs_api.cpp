@@ -28,6 +28,7 @@
 #include "rs_general.h"
 #include "rs_kernels.h"
 #include "rs_keygen.h"
+#include "rs_pack.h"
 #include "rs_rlwe.h"
 
 namespace {
@@ -929,6 +930,29 @@ int rs_rlwe_extract_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t count
   if (count == 0) return RS_OK;
   const rs::RlweExtractArgs x{u, rlwe, (long)count, c->p.N};
   RS_HIP(rs::launch_rlwe_extract(x, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// packed results (include/redsec_hip.h; kernels of rs_pack.hip, integer arithmetic only): needs no key, the ring and n are the context's
+int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const int32_t* pack_key, int32_t basebit, int32_t t,
+                void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!rlwe || !ct || !pack_key) return fail(RS_ERR_INVALID, "null pointer");
+  if (basebit < 1 || basebit > 8) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
+  if (t < 1) return fail(RS_ERR_INVALID, "t = %d is below 1", (int)t);
+  if ((int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
+  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
+  if (N < (size_t)rs::kPaMinN || N > (size_t)rs::kPaMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  const size_t row_bytes = (n + 1) * sizeof(int32_t), R = count / N + (count % N ? 1 : 0);
+  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
+  if (count == 0) return RS_OK;
+  const size_t per_r = 2 * (N / rs::kPaTile) * (size_t)rs::pa_slot_blocks((long)count, (int)N) * (size_t)rs::pa_chunks((int)n);
+  if (R > (size_t)INT32_MAX / per_r)                                        // workgroups of one launch (rs::pa_groups)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for one launch", count);
+  const rs::PackArgs a{rlwe, ct, pack_key, (long)count, (int)n, (int)N, (int)basebit, (int)t};
+  RS_HIP(rs::launch_pack(a, (hipStream_t)stream));
   return RS_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "rs_general.h"
 #include "rs_host.h"
 #include "rs_keygen.h"
+#include "rs_pack.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
@@ -1331,6 +1332,80 @@ void rs_emu_rlwe_extract(const int32_t* rlwe, long count, int N, int32_t* u) {
     const int c = (int)(i - r * N);
     const uint32_t* a = reinterpret_cast<const uint32_t*>(rlwe) + (size_t)r * 2 * N;
     for (int j = 0; j <= N; ++j) u[(size_t)i * (N + 1) + j] = (int32_t)rs::rl_extract_word(a, a + N, N, c, j);
+  }
+}
+
+// ---- packed results (rs_pack_dev) through the functions of rs_pack.h ----
+uint32_t rs_emu_pack_offset(int basebit, int t) { return rs::pa_offset(basebit, t); }
+uint32_t rs_emu_pack_digit(uint32_t abar, int basebit, int j) { return rs::pa_digit(abar, basebit, j); }
+int rs_emu_pack_slot_blocks(long count, int N) { return rs::pa_slot_blocks(count, N); }
+int rs_emu_pack_chunks(int n) { return rs::pa_chunks(n); }
+long rs_emu_pack_groups(long count, int n, int N) { return rs::pa_groups(count, n, N); }
+// window word of coefficient k0 + x and slot c0 + cc as an index into ext = (-p, p)
+int rs_emu_pack_window_word(int N, int k0, int c0, int cpad, int x, int cc) {
+  return rs::pa_window_base(N, k0, c0, cpad) + rs::pa_window_index(cpad, x, cc);
+}
+int rs_emu_pack_tile() { return rs::kPaTile; }
+int rs_emu_pack_slots() { return rs::kPaSlots; }
+// pack_init_kernel, then pack_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over (tile,
+// polynomial, slot block, index chunk, ciphertext), the transposed sample words of the chunk, the staged window per key row, a 4-word
+// chunk per thread and four scalar digits, the negated partial sums added into the output
+void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pack_key, int basebit, int t, int32_t* rlwe) {
+  if (count <= 0) return;
+  const long R = (count + N - 1) / N;
+  uint32_t* out = reinterpret_cast<uint32_t*>(rlwe);
+  for (long idx = 0; idx < R * 2 * (long)N; ++idx) {
+    const long r = idx / (2 * (long)N);
+    const int w = (int)(idx - r * 2 * (long)N);
+    const long s = r * (long)N + (w - N);
+    out[idx] = (w >= N && s < count) ? (uint32_t)ct[(size_t)s * ((size_t)n + 1) + n] : 0u;
+  }
+  const int tiles = N / rs::kPaTile, sbs = rs::pa_slot_blocks(count, N), chunks = rs::pa_chunks(n);
+  const uint32_t off = rs::pa_offset(basebit, t), mask = (1u << basebit) - 1u;
+  const uint32_t* key = reinterpret_cast<const uint32_t*>(pack_key);
+  std::vector<uint32_t> win((size_t)rs::kPaSlots + rs::kPaTile), sa((size_t)rs::kPaSeg * rs::kPaSlots);
+  std::vector<uint32_t> acc((size_t)rs::kPaTile);
+  for (long blk = 0; blk < rs::pa_groups(count, n, N); ++blk) {
+    long g = blk;
+    const int tile = (int)(g % tiles); g /= tiles;
+    const int poly = (int)(g & 1); g >>= 1;
+    const int sb = (int)(g % sbs); g /= sbs;
+    const int chunk = (int)(g % chunks);
+    const long r = g / chunks;
+    const int c0 = sb * rs::kPaSlots, slots = rs::pa_slots(count, N, r);
+    if (c0 >= slots) continue;
+    const int cn = slots - c0 < rs::kPaSlots ? slots - c0 : rs::kPaSlots, cpad = rs::pa_pad4(cn);
+    const int i0 = chunk * rs::kPaSeg, segn = n - i0 < rs::kPaSeg ? n - i0 : rs::kPaSeg;
+    const int k0 = tile * rs::kPaTile, wb = rs::pa_window_base(N, k0, c0, cpad);
+    const uint32_t* cts = reinterpret_cast<const uint32_t*>(ct) + ((size_t)r * N + c0) * ((size_t)n + 1);
+    std::fill(acc.begin(), acc.end(), 0u);
+    for (int idx = 0; idx < segn * cpad; ++idx) {
+      const int cc = idx / segn, ii = idx - cc * segn;
+      sa[(size_t)ii * cpad + cc] = cc < cn ? cts[(size_t)cc * ((size_t)n + 1) + i0 + ii] + off : 0u;
+    }
+    for (int ii = 0; ii < segn; ++ii)
+      for (int j = 0; j < t; ++j) {
+        const uint32_t* p = key + rs::pa_key_offset(N, t, i0 + ii, j, poly);
+        for (int x = 0; x < cpad + rs::kPaTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
+        const int shift = 32 - (j + 1) * basebit;
+        for (int th = 0; th < rs::kPaThreads; ++th) {
+          uint32_t* a4 = &acc[(size_t)rs::kPaKpt * th];
+          int c4 = th + cpad / 4;
+          const uint32_t* hi = &win[4 * (size_t)c4];
+          for (int q4 = 0; q4 < cpad / 4; ++q4) {
+            const uint32_t* av = &sa[(size_t)ii * cpad + 4 * q4];
+            const uint32_t* lo = &win[4 * (size_t)(--c4)];
+            const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            for (int b = 0; b < 4; ++b) {
+              const uint32_t d = (av[b] >> shift) & mask;
+              for (int q = 0; q < rs::kPaKpt; ++q) a4[q] += w[4 + q - b] * d;
+            }
+            hi = lo;
+          }
+        }
+      }
+    uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0;
+    for (int x = 0; x < rs::kPaTile; ++x) o[x] += 0u - acc[x];
   }
 }
 

@@ -170,6 +170,15 @@ struct RlweExtractArgs {
   int N;
 };
 hipError_t launch_rlwe_extract(const RlweExtractArgs& x, hipStream_t st);
+// packed results (rs_pack_dev; placement and index arithmetic of rs_pack.h): ciphertext r packs samples rN .. rN + N - 1
+struct PackArgs {
+  int32_t* rlwe;                                      // [ceil(count / N)][2][N]
+  const int32_t* ct;                                  // [count][n+1]
+  const int32_t* key;                                 // [n][t][2][N]: the packing key
+  long count;
+  int n, N, basebit, t;
+};
+hipError_t launch_pack(const PackArgs& a, hipStream_t st);
 // device decryption and the exact noise audit of evaluation keys (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev;
 // per-word arithmetic of rs_audit.h, 32-bit integer only). Secret keys are private device copies packed 32 bits per word.
 constexpr int kAuMaxDim = 16384;                      // largest LWE dimension a packed key in LDS serves (rs_create's limit on n)

@@ -63,6 +63,18 @@ encryptor's PRIVATE rand seed and carries N messages:
   Domains 10-13 are disjoint from domains 1-9. Equal mask and noise seeds are refused; a (rand seed, row) pair must never be used
   twice. rlwe_pk_mask / rlwe_public_key / rlwe_pk_selector / rlwe_pk_encrypt / rlwe_extract / rlwe_phase restate it.
 
+Packed results (rs_pack_dev; include/redsec_hip.h): a public keyswitch from the LWE key s to the ring
+key S puts up to N LWE samples into the coefficients of one RLWE ciphertext of the format above. The packing key has, per key bit
+s_i and digit j < t, the ring sample K[i][j] = (a_ij, b_ij = a_ij*S + e_ij + s_i 2^(32-(j+1) basebit) X^0):
+
+  domain 14  packing-key mask    row i t + j   mask seed (public)             a_ij[k] = word k, k < N
+  domain 15  packing-key noise   row i t + j   owner's noise seed (private)   e_ij[k] = Gaussian k (words 4k .. 4k+3, kg_noise32)
+  rlwe[r] = (0, sum_c b_(rN+c) X^c) - sum_{i,j} D_ij(X) K[i][j], D_ij(X) = sum_c ((a_i + off of sample rN+c) >> (32-(j+1) basebit)
+  & (2^basebit - 1)) X^c, off = 2^(31 - t basebit) (0 at 32 bits): the digits of lweKeySwitch.
+
+  Domains 14 and 15 are disjoint from domains 1-13. Equal mask and noise seeds are refused. pack_key_mask / pack_key / pack /
+  pack_sigma / pack_default restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -84,6 +96,7 @@ DOMAIN_LWE_SECRET, DOMAIN_TLWE_SECRET, DOMAIN_BK_MASK, DOMAIN_BK_NOISE, DOMAIN_K
 DOMAIN_CT_MASK, DOMAIN_CT_NOISE = 7, 8
 DOMAIN_PK_SELECT = 9
 DOMAIN_RLWE_MASK, DOMAIN_RLWE_NOISE, DOMAIN_RLWE_SELECT, DOMAIN_RLWE_ENC_NOISE = 10, 11, 12, 13
+DOMAIN_PACK_MASK, DOMAIN_PACK_NOISE = 14, 15
 _SIGMA = b"expand 32-byte k"
 
 
@@ -599,6 +612,118 @@ def rlwe_phase(rlwe, tlwe_key):
     rlwe = rlwe.reshape(-1, 2, N).view(np.uint32)
     with np.errstate(over="ignore"):
         return (rlwe[:, 1] - _times_binary(np.ascontiguousarray(rlwe[:, 0]), np.asarray(tlwe_key).ravel())).view(np.int32)
+
+
+# ---- packed results (rs_pack_dev restated) ----
+
+def pack_default(name):
+    """(basebit, t) of a set's packing key: basebit 4; t = 4 (16 bits) where results are +-1/8 bits (default-128), t = 5 (20 bits) on
+    the REDsec sets, whose 1/4096-scale values need the digits' rounding sqrt(n / 24) 2^(-t basebit) well under the half step 1.2e-4
+    (16 bits: 7e-5; 20 bits: 4e-6)."""
+    _shape(name)
+    return (4, 4) if name == "default128" else (4, 5)
+
+
+def _check_digits(basebit, t):
+    basebit, t = int(basebit), int(t)
+    if not (1 <= basebit <= 8 and t >= 1 and t * basebit <= 32):
+        raise ValueError("basebit = %d, t = %d: basebit must lie in 1 .. 8, t >= 1 and t basebit <= 32" % (basebit, t))
+    return basebit, t
+
+
+def pack_key_mask(mask_seed, N, rows):
+    """The mask polynomials a_ij of packing-key rows i t + j: words 0 .. N-1 of stream (14, row) of the mask seed -> int32 [R][N]."""
+    rows = np.asarray(rows, np.int64).ravel()
+    return chacha20_words(mask_seed, DOMAIN_PACK_MASK, rows.astype(np.uint64), int(N)).reshape(len(rows), int(N)).view(np.int32)
+
+
+def pack_key(name, lwe_key, tlwe_key, mask_seed, noise_seed, basebit, t, stdev=None, rows=None, chunk=256):
+    """The bodies b_ij = a_ij*S + e_ij + s_i 2^(32-(j+1) basebit) X^0 of the packing key from lwe_key to tlwe_key: a_ij =
+    pack_key_mask(mask_seed, N, i t + j), e_ij the N Gaussians of stream (15, i t + j) of the private noise seed -> int32 [n][t][N]
+    (rows=None), or [len(rows)][N] for the rows i t + j listed. The LWE dimension is len(lwe_key). stdev defaults to
+    rlwe_default_stdev(name): the ring's alpha, refused where it truncates to zero."""
+    _check_seeds(mask_seed, noise_seed)
+    basebit, t = _check_digits(basebit, t)
+    stdev = rlwe_default_stdev(name) if stdev is None else float(stdev)
+    N = _shape(name)["N"]
+    lwe = np.asarray(lwe_key).ravel().astype(np.uint32)
+    S = np.asarray(tlwe_key).ravel()
+    assert S.size == N, "tlwe_key must have N = %d words" % N
+    whole = rows is None
+    rows = np.arange(lwe.size * t) if whole else np.asarray(rows, np.int64).ravel()
+    out = np.empty((len(rows), N), np.int32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(rows), chunk):
+            r = rows[lo:lo + chunk]
+            B = _times_binary(np.ascontiguousarray(pack_key_mask(mask_seed, N, r)).view(np.uint32), S)
+            if stdev:
+                B += noise32(chacha20_words(noise_seed, DOMAIN_PACK_NOISE, r.astype(np.uint64), 4 * N), stdev).reshape(len(r), N).view(np.uint32)
+            B[:, 0] += lwe[r // t] * (np.uint32(1) << (32 - (r % t + 1) * basebit).astype(np.uint32))
+            out[lo:lo + chunk] = B.view(np.int32)
+    return out.reshape(lwe.size, t, N) if whole else out
+
+
+def pack_digits(a, basebit, t):
+    """The t digits of the mask words a (any shape, int32 / uint32) in lweKeySwitch's convention: abar = a + 2^(31 - t basebit) (no
+    offset at 32 bits), digit j = (abar >> (32 - (j+1) basebit)) & (2^basebit - 1) -> uint32 [..., t]."""
+    basebit, t = _check_digits(basebit, t)
+    a = np.asarray(a).astype(np.int64) & 0xFFFFFFFF
+    off = (1 << (31 - t * basebit)) if t * basebit < 32 else 0
+    abar = (a + off) & 0xFFFFFFFF
+    return np.stack([(abar >> (32 - (j + 1) * basebit)) & ((1 << basebit) - 1) for j in range(t)], axis=-1).astype(np.uint32)
+
+
+def pack(ct, key, basebit, t):
+    """rs_pack_dev restated: ct int32 [count][n+1], key int32 [n][t][2][N] -> int32 [ceil(count / N)][2][N], ciphertext r =
+    (0, sum_c b_(rN+c) X^c) - sum_{i,j} D_ij(X) K[i][j]. Per polynomial the sum over the n t rows is ONE float64 matrix product per
+    16-bit half of the key words, G[c][x] = sum_rows digit[row][c] ext[row][x] over ext = (-p, p) (every entry below 2^8 2^16 n t
+    < 2^53: exact), and coefficient k is the sum over c of G[c][k - c + N], taken in 64-bit integers: nothing like the device's tiled
+    32-bit multiply-adds."""
+    basebit, t = _check_digits(basebit, t)
+    key = np.ascontiguousarray(key, np.int32)
+    assert key.ndim == 4 and key.shape[1] == t and key.shape[2] == 2, "key must hold [n][t][2][N] words"
+    n, N = key.shape[0], key.shape[3]
+    assert n * t < 1 << 28, "n t is too large for the exact float64 sums"
+    ct = np.ascontiguousarray(ct, np.int32).reshape(-1, n + 1)
+    count = ct.shape[0]
+    R = -(-count // N)
+    out = np.zeros((R, 2, N), np.uint32)
+    if count == 0:
+        return out.view(np.int32)
+    ku = key.view(np.uint32).reshape(n * t, 2, N)
+    halves = []
+    for poly in range(2):
+        ext = np.concatenate([np.uint32(0) - ku[:, poly], ku[:, poly]], axis=1)                   # [n t][2N]
+        halves.append(((ext & np.uint32(0xFFFF)).astype(np.float64), (ext >> np.uint32(16)).astype(np.float64)))
+    step = max(4, (1 << 22) // (2 * N))                                                        # slots per product: G of 32 MB
+    for r in range(R):
+        rows = ct[r * N:(r + 1) * N]
+        cr = rows.shape[0]
+        out[r, 1, :cr] = rows[:, n].view(np.uint32)
+        D = pack_digits(rows[:, :n], basebit, t).reshape(cr, n * t).astype(np.float64)          # [c][i t + j]
+        for poly in range(2):
+            acc = np.zeros(N, np.uint64)
+            for c0 in range(0, cr, step):
+                d = D[c0:c0 + step]
+                G = (d @ halves[poly][0]).astype(np.uint64) + ((d @ halves[poly][1]).astype(np.uint64) << np.uint64(16))
+                flat = np.ascontiguousarray(G).ravel()
+                # element (c, k) = G[c][k - (c0 + c) + N] = flat[c (2N - 1) + N - c0 + k]
+                view = np.lib.stride_tricks.as_strided(flat[N - c0:], shape=(len(d), N), strides=((2 * N - 1) * 8, 8))
+                acc += view.sum(axis=0, dtype=np.uint64)
+            with np.errstate(over="ignore"):
+                out[r, poly] -= (acc & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return out.view(np.int32)
+
+
+def pack_sigma(n, N, basebit, t, count, stdev):
+    """Deviation of the packing error of one slot, as a real in [-1/2, 1/2): the key noise under the n t digit polynomials of
+    count_r = min(count, N) slots (a uniform digit has mean square (2^basebit - 1)(2^(basebit+1) - 1) / 6) and the rounding of the
+    digits over the n / 2 set key bits:
+      sigma^2 = n t count_r (2^basebit - 1)(2^(basebit+1) - 1)/6 sigma_k^2  +  (n/2) 2^(-2 t basebit)/12"""
+    basebit, t = _check_digits(basebit, t)
+    cr = min(int(count), int(N))
+    base = 1 << basebit
+    return float(np.sqrt(n * t * cr * (base - 1) * (2 * base - 1) / 6.0 * float(stdev) ** 2 + (n / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
