@@ -224,7 +224,7 @@ int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t cou
 /* Packed results (TFHE's TLWE keyswitch with the identity function): a public keyswitch from the LWE key s
  * to the ring key S that puts up to N LWE samples into the coefficients of ONE RLWE ciphertext of section 17's format, 8N bytes
  * instead of N 4 (n + 1). The packing key holds, per key bit s_i and digit j, a ring sample under S whose message is s_i times the
- * digit's weight; two more streams, disjoint from domains 1-13 (owner's side only, redsec_amd/keygen.py pack_key; no device code):
+ * digit's weight; two more streams, disjoint from domains 1-13 (owner's side only: redsec_amd/keygen.py pack_key, rs_pack_keygen_dev):
  *   domain 14  packing-key mask    row i t + j   mask seed (public)             a_ij[k] = word k, k < N
  *   domain 15  packing-key noise   row i t + j   owner's noise seed (private)   e_ij[k] = Gaussian k (words 4k .. 4k+3, kg_noise32)
  *
@@ -247,6 +247,27 @@ int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t cou
  * overflow. Without a device or context it fails as rs_rlwe_extract_dev does. */
 int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
                 const int32_t* pack_key, int32_t basebit, int32_t t, void* stream);
+
+/* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
+ * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three
+ * need no loaded key and work on every context, N = 1024 .. 8192: 32-bit integer adds, no product, no transform, no mode dependence.
+ *
+ * rs_pack_keygen_dev (CLIENT): body[i t + j] = a*S + e + s_i 2^(32-(j+1) basebit) X^0, negacyclic mod 2^32, a = words 0 .. N-1 of
+ * stream (14, i t + j) of the mask seed, e_k = Gaussian k of stream (15, i t + j) of the noise seed through kg_noise32: word for
+ * word redsec_amd/keygen.py pack_key (up to its note on the last bit of numpy's log / cos). body DEVICE int32[n][t][N]. lwe_key,
+ * tlwe_key HOST int32[n], int32[N] with words in {0, 1}; their private device copy (packed bits) is zeroed and freed on every path.
+ * The mask never reaches global memory. stdev: any finite value >= 0 (0 for word-identity tests; what deviation a key may have is the
+ * caller's policy, redsec_amd/client.py). Synchronous, like rs_keygen_dev.
+ * RS_ERR_INVALID: null pointer; key word outside {0, 1}; equal seeds; basebit outside 1 .. 8; t < 1; t basebit > 32; negative or
+ * non-finite stdev; n t whose row arithmetic would overflow.
+ *
+ * rs_pack_expand_dev (SERVER): pack_key[i][j] = (the domain-14 stream of row i t + j of the mask seed, body[i][j]): the key
+ * rs_pack_dev takes, from the seed and the bodies that travel. pack_key DEVICE int32[n][t][2][N], must not overlap body; body DEVICE
+ * int32[n][t][N]. Asynchronous and ordered on `stream`; no allocation. RS_ERR_INVALID: null pointer; t < 1; overflow as above.
+ * Without a device or context both fail as rs_pack_dev does. */
+int rs_pack_keygen_dev(rs_ctx* ctx, int32_t* body, const int32_t* lwe_key, const int32_t* tlwe_key,
+                       const uint8_t* mask_seed, const uint8_t* noise_seed, int32_t basebit, int32_t t, double stdev);
+int rs_pack_expand_dev(rs_ctx* ctx, int32_t* pack_key, const uint8_t* mask_seed, const int32_t* body, int32_t t, void* stream);
 
 /* Device decryption and the exact noise audit of evaluation keys. CLIENT side: a server holds no secret.
  * All three are synchronous like rs_keygen_dev and additionally wait for ALL work queued on the context's device, on every stream,
@@ -288,6 +309,23 @@ int rs_audit_keys_dev(rs_ctx* ctx, rs_key_audit* report, int32_t* bk_noise, int3
 int rs_audit_compressed_keys_dev(rs_ctx* ctx, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise,
                                  const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body,
                                  const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit, uint32_t ksk_limit);
+
+/* rs_audit_pack_key_dev (CLIENT): the same question for a packing key, the only other key material a
+ * server holds; a bad row publishes a bit of the LWE secret. Noise word of row i t + j: e = b - a*S - s_i 2^(32-(j+1) basebit) X^0.
+ * mask_seed NULL: key is the full key DEVICE int32[n][t][2][N] (what rs_pack_dev reads). With a mask seed: key is the bodies DEVICE
+ * int32[n][t][N] and a is regenerated from the seed, without expanding. noise: optional DEVICE int32[n][t][N]. report is HOST.
+ * A correctly generated key returns exactly the generator's domain-15 words; a noiseless key returns zeros. Integer arithmetic only,
+ * a signed sum of rotations over the set bits of S: another loop than the generator's. Synchronous; waits for ALL work queued on the
+ * device before it reads, as the audits above; secrets are HOST pointers handled as there. redsec_amd/keygen.py restates it
+ * (pack_key_noise; pack_noise_limit gives a default limit).
+ * RS_ERR_INVALID: a null report, key or secret; key words outside {0, 1}; basebit, t as for rs_pack_keygen_dev. */
+typedef struct rs_pack_key_audit {
+  uint32_t max_abs;   /* largest |noise word| read as signed 32-bit (|INT32_MIN| = 2^31) */
+  uint64_t over;      /* noise words with |e| > limit */
+  uint64_t words;     /* noise words looked at: n t N */
+} rs_pack_key_audit;
+int rs_audit_pack_key_dev(rs_ctx* ctx, rs_pack_key_audit* report, int32_t* noise, const int32_t* key, const uint8_t* mask_seed,
+                          const int32_t* lwe_key, const int32_t* tlwe_key, int32_t basebit, int32_t t, uint32_t limit);
 
 /* Arithmetic of the external product (both keys are resident after rs_load_keys; switching is free):
  *   RS_MODE_FFT        folded 512-point complex FP64 FFT -- the arithmetic class of TFHE's own

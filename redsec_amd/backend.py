@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "rs_allgather_rows", "rs_release_stream", "rs_load_synthetic_keys", "rs_keygen_dev", "rs_load_keys_dev",
     "rs_keygen_compressed_dev", "rs_expand_keys_dev", "rs_load_compressed_keys", "rs_load_compressed_keys_dev",
     "rs_encrypt_seeded_dev", "rs_expand_ciphertexts_dev", "rs_pk_encrypt_dev", "rs_rlwe_pk_encrypt_dev", "rs_rlwe_extract_dev", "rs_pack_dev",
+    "rs_pack_keygen_dev", "rs_pack_expand_dev", "rs_audit_pack_key_dev",
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
@@ -62,6 +63,10 @@ class RsPoolShape(C.Structure):
 class RsKeyAudit(C.Structure):
     _fields_ = [("bk_max_abs", C.c_uint32), ("ksk_max_abs", C.c_uint32), ("bk_over", C.c_uint64), ("ksk_over", C.c_uint64),
                 ("ksk_zero_bad", C.c_uint64), ("bk_words", C.c_uint64), ("ksk_words", C.c_uint64)]
+
+
+class RsPackKeyAudit(C.Structure):
+    _fields_ = [("max_abs", C.c_uint32), ("over", C.c_uint64), ("words", C.c_uint64)]
 
 
 class RsRowGroup(C.Structure):
@@ -126,6 +131,9 @@ def load_library(path=None):
     L.rs_rlwe_pk_encrypt_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, C.c_double, vp]
     L.rs_rlwe_extract_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.rs_pack_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
+    L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
+    L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
+    L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
     L.rs_phase_dev.argtypes = [vp, vp, vp, C.c_size_t, _i32p, C.c_int32]
     L.rs_audit_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
     L.rs_audit_compressed_keys_dev.argtypes = [vp, C.POINTER(RsKeyAudit), vp, vp, C.c_char_p, vp, vp, _i32p, _i32p, C.c_uint32, C.c_uint32]
@@ -461,8 +469,8 @@ class Backend:
     def pack(self, ct, key, basebit=None, t=None, out=None):
         """LWE samples ct (int32 CUDA tensor [count][n+1]) keyswitched into the coefficients of RLWE ciphertexts (rs_pack_dev, on
         torch's current stream): ciphertext r packs samples rN .. rN + N - 1 -> int32 CUDA tensor [ceil(count / N)][2][N], the format
-        of section 17 (rlwe_extract, rlwe_unpack, client.SecretKeySet.packed_phase). key: a client.PackingKey (expanded on the host
-        and uploaded: keep the tensor of upload_packing_key for repeated calls; ValueError for a key of another set or another n) or
+        of section 17 (rlwe_extract, rlwe_unpack, client.SecretKeySet.packed_phase). key: a client.PackingKey (uploaded and
+        expanded on the device: keep the tensor of upload_packing_key for repeated calls; ValueError for a key of another set or another n) or
         an int32 CUDA tensor [n][t][2][N] with explicit basebit and t. Needs no loaded key."""
         from . import keygen
         N, n = self.p.N, self.p.n
@@ -482,13 +490,67 @@ class Backend:
 
     def upload_packing_key(self, key):
         """The expanded client.PackingKey on this context's device -> int32 CUDA tensor [n][t][2][N] (pass it to pack with key.basebit
-        and key.t). ValueError for a key of another set or another n."""
+        and key.t): the bodies are uploaded and the masks regenerated beside them on the device (expand_packing_key), half the bytes
+        of the expanded key over the bus. ValueError for a key of another set or another n."""
         import torch
         from . import keygen
         if key.name != keygen.set_name(self.p) or key.n != self.p.n:
             raise ValueError("the packing key is of %s with n = %d, the context of %s with n = %d"
                              % (key.name, key.n, keygen.set_name(self.p), self.p.n))
-        return torch.from_numpy(key.expand()).to("cuda:%d" % self.device)
+        return self.expand_packing_key(key.mask_seed, torch.from_numpy(key.body).to("cuda:%d" % self.device), key.t)
+
+    # ---- the packing key on the device (INTEGRATION.md section 19) ----
+    def _secrets(self, lwe_key, tlwe_key):
+        lwe, plwe = _np_i32(lwe_key)
+        tlwe, ptlwe = _np_i32(tlwe_key)
+        assert lwe.size == self.p.n and tlwe.size == self.p.N, "secret keys have the wrong size"
+        return (lwe, tlwe), plwe, ptlwe
+
+    def pack_keygen(self, lwe_key, tlwe_key, mask_seed, noise_seed, basebit, t, stdev, out=None):
+        """Bodies of the packing key from lwe_key to tlwe_key (host, 0/1) generated on the device (rs_pack_keygen_dev, synchronous)
+        -> int32 CUDA tensor [n][t][N] (or into `out`), the words of keygen.pack_key. stdev is taken as given (any finite value
+        >= 0): the policy is client.SecretKeySet.packing_key's."""
+        from . import keygen
+        basebit, t = keygen._check_digits(basebit, t)
+        keep, plwe, ptlwe = self._secrets(lwe_key, tlwe_key)
+        out = self.empty(self.p.n, t, self.p.N) if out is None else out
+        assert out.numel() == self.p.n * t * self.p.N, "out must hold [n][t][N] words"
+        _check(self.L, self.L.rs_pack_keygen_dev(self.h, self._ck_dev(out), plwe, ptlwe, self._seed32(mask_seed, "mask_seed"),
+                                                 self._seed32(noise_seed, "noise_seed"), basebit, t, float(stdev)))
+        return out
+
+    def expand_packing_key(self, mask_seed, body, t, out=None):
+        """The full packing key of the bodies `body` (int32 CUDA tensor [n][t][N]) and the public mask seed, expanded on the device
+        on torch's current stream (rs_pack_expand_dev) -> int32 CUDA tensor [n][t][2][N] (or into `out`), what pack takes."""
+        t = int(t)
+        assert t >= 1 and body.numel() == self.p.n * t * self.p.N, "body must hold [n][t][N] words"
+        out = self.empty(self.p.n, t, 2, self.p.N) if out is None else out
+        assert out.numel() == 2 * body.numel(), "out must hold [n][t][2][N] words"
+        _check(self.L, self.L.rs_pack_expand_dev(self.h, self._ck_dev(out), self._seed32(mask_seed, "mask_seed"), self._ck_dev(body), t,
+                                                 self._stream()))
+        return out
+
+    def audit_packing_key(self, lwe_key, tlwe_key, key, basebit, t, mask_seed=None, limit=None, noise=False):
+        """Exact noise audit of a packing key in device memory under its secret (rs_audit_pack_key_dev, synchronous; CLIENT side): key
+        is the full key [n][t][2][N], or with mask_seed= the bodies [n][t][N] (the masks are regenerated, nothing is expanded).
+        limit defaults to keygen.pack_noise_limit of the set's default deviation (ValueError where that vanishes: pass one).
+        -> a dict of the rs_pack_key_audit fields, plus noise [n][t][N] (int32 CUDA tensor) with noise=True."""
+        from . import keygen
+        basebit, t = keygen._check_digits(basebit, t)
+        keep, plwe, ptlwe = self._secrets(lwe_key, tlwe_key)
+        words = self.p.n * t * self.p.N
+        assert key.numel() == (words if mask_seed is not None else 2 * words), "key has the wrong size"
+        if limit is None:
+            limit = keygen.pack_noise_limit(keygen.rlwe_default_stdev(keygen.set_name(self.p)))
+        e = self.empty(self.p.n, t, self.p.N) if noise else None
+        rep = RsPackKeyAudit()
+        _check(self.L, self.L.rs_audit_pack_key_dev(self.h, C.byref(rep), None if e is None else self._ck_dev(e), self._ck_dev(key),
+                                                    None if mask_seed is None else self._seed32(mask_seed, "mask_seed"), plwe, ptlwe,
+                                                    basebit, t, int(limit)))
+        out = {f: int(getattr(rep, f)) for f, _ in RsPackKeyAudit._fields_}
+        if noise:
+            out["noise"] = e
+        return out
 
     # ---- device decryption and the noise audit of evaluation keys (INTEGRATION.md section 13; CLIENT side) ----
     def phase(self, ct, key):

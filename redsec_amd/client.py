@@ -205,18 +205,44 @@ class SecretKeySet:
         noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
         return RlwePublicKey(self.name, mask_seed, keygen.rlwe_public_key(self.name, self.tlwe_key, mask_seed, noise_seed, stdev))
 
-    def packing_key(self, basebit=None, t=None, mask_seed=None, noise_seed=None, stdev=None):
+    def packing_key(self, basebit=None, t=None, mask_seed=None, noise_seed=None, stdev=None, backend=None):
         """The packing key from this secret's LWE key to its ring key (include/redsec_hip.h rs_pack_dev)
         -> PackingKey (32 bytes + 4 n t N bytes), written and read as an RSK1 file. basebit, t default to keygen.pack_default(name),
         stdev to the set's bk_stdev (ValueError where that truncates to zero: pass one). A server holding the key packs results with
-        Backend.pack; only this secret decrypts them (packed_phase, decrypt_packed_bits, decrypt_packed_ints)."""
+        Backend.pack; only this secret decrypts them (packed_phase, decrypt_packed_bits, decrypt_packed_ints). With backend= (a
+        redsec_amd.Backend of this set and n) the bodies are generated on the device (rs_pack_keygen_dev):
+        the same words, the same PackingKey, the same rules for the seeds and the deviation."""
         from . import keygen
         d = keygen.pack_default(self.name)
-        basebit, t = d[0] if basebit is None else int(basebit), d[1] if t is None else int(t)
+        basebit, t = keygen._check_digits(d[0] if basebit is None else basebit, d[1] if t is None else t)
         mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
         noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
-        body = keygen.pack_key(self.name, self.lwe_key, self.tlwe_key, mask_seed, noise_seed, basebit, t, stdev)
+        if backend is None:
+            body = keygen.pack_key(self.name, self.lwe_key, self.tlwe_key, mask_seed, noise_seed, basebit, t, stdev)
+        else:
+            self._check_backend(backend)
+            keygen._check_seeds(mask_seed, noise_seed)
+            stdev = keygen.rlwe_default_stdev(self.name) if stdev is None else float(stdev)
+            body = backend.pack_keygen(self.lwe_key, self.tlwe_key, mask_seed, noise_seed, basebit, t, stdev).cpu().numpy()
         return PackingKey(self.name, self.n, basebit, t, mask_seed, body)
+
+    def _check_backend(self, backend):
+        from . import keygen
+        if keygen.set_name(backend.p) != self.name or backend.p.n != self.n:
+            raise ValueError("the secret is of %s with n = %d, the context of %s with n = %d"
+                             % (self.name, self.n, keygen.set_name(backend.p), backend.p.n))
+
+    def audit_packing_key(self, key, backend, limit=None):
+        """Exact noise audit of the PackingKey `key` under this secret on the device (rs_audit_pack_key_dev): the bodies are uploaded
+        and the masks regenerated from the key's seed, nothing is expanded. limit defaults to keygen.pack_noise_limit of the set's
+        default deviation (ValueError where that vanishes: pass one) -> the dict of Backend.audit_packing_key; a key made for this
+        secret with a deviation within the limit has over == 0."""
+        import torch
+        self._check_backend(backend)
+        if key.name != self.name or key.n != self.n:
+            raise ValueError("the packing key is of %s with n = %d, the secret of %s with n = %d" % (key.name, key.n, self.name, self.n))
+        body = torch.from_numpy(key.body).to("cuda:%d" % backend.device)
+        return backend.audit_packing_key(self.lwe_key, self.tlwe_key, body, key.basebit, key.t, mask_seed=key.mask_seed, limit=limit)
 
     def packed_phase(self, rlwe, count, backend=None):
         """Phases of the first `count` slots of packed ciphertexts [R][2][N] under the ring key (slot rN + c is coefficient c of

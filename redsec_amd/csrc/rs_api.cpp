@@ -29,6 +29,7 @@
 #include "rs_kernels.h"
 #include "rs_keygen.h"
 #include "rs_pack.h"
+#include "rs_packkey.h"
 #include "rs_rlwe.h"
 
 namespace {
@@ -956,6 +957,67 @@ int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const
   return RS_OK;
 }
 
+// the packing key on the device (include/redsec_hip.h; kernels of rs_packkey.hip): the checks the three calls share. rows = n t.
+static int pack_key_shape(const rs_ctx* c, int32_t basebit, int32_t t, bool digits, size_t* rows) {
+  if (digits && (basebit < 1 || basebit > 8)) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
+  if (t < 1) return fail(RS_ERR_INVALID, "t = %d is below 1", (int)t);
+  if (digits && (int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
+  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
+  if (N < (size_t)rs::kPgMinN || N > (size_t)rs::kPgMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  // rows x tiles workgroups of the generator, rows N / 16 threads of the expansion and 2 rows N words of the key, all below 2^31 x 256
+  if (n < 1 || (size_t)t > (size_t)INT32_MAX / (N / 16) / n)
+    return fail(RS_ERR_INVALID, "n t = %zu x %d is too large for rows of %zu words", n, (int)t, N);
+  *rows = n * (size_t)t;
+  return RS_OK;
+}
+
+int rs_pack_keygen_dev(rs_ctx* c, int32_t* body, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* mask_seed,
+                       const uint8_t* noise_seed, int32_t basebit, int32_t t, double stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!body || !lwe_key || !tlwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (memcmp(mask_seed, noise_seed, 32) == 0)
+    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
+  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
+  size_t rows = 0;
+  rc = pack_key_shape(c, basebit, t, true, &rows);
+  if (rc) return rc;
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  int bad = pack_key_bits(lwe_key, p.n, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
+  const size_t lwe_words = bits.size();
+  bad = pack_key_bits(tlwe_key, p.N, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
+  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
+    rs::PackKeygenArgs a{};
+    a.body = body; a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    rs::kg_seed_words(mask_seed, a.seed);
+    rs::kg_seed_words(noise_seed, a.noise_seed);
+    a.n = p.n; a.N = p.N; a.basebit = basebit; a.t = t; a.sigma = stdev;
+    const hipError_t e = rs::launch_pack_keygen(a, nullptr);
+    for (uint32_t& w : a.noise_seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the private seed words does not outlive the call
+    if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pack_keygen failed: %s", hipGetErrorString(e));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  });
+}
+
+int rs_pack_expand_dev(rs_ctx* c, int32_t* pack_key, const uint8_t* mask_seed, const int32_t* body, int32_t t, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!pack_key || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
+  size_t rows = 0;
+  rc = pack_key_shape(c, 0, t, false, &rows);
+  if (rc) return rc;
+  rs::PackExpandArgs a{};
+  a.key = pack_key; a.body = body;
+  rs::kg_seed_words(mask_seed, a.seed);
+  a.rows = (long)rows; a.N = c->p.N;
+  RS_HIP(rs::launch_pack_expand(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
 // ---- device decryption and the noise audit of evaluation keys (CLIENT side; kernels of rs_audit.hip, integer arithmetic only) ----
 
 int rs_phase_dev(rs_ctx* c, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim) {
@@ -1024,6 +1086,43 @@ int rs_audit_compressed_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_no
                                  const int32_t* bk_body, const int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
                                  uint32_t bk_limit, uint32_t ksk_limit) {
   return audit_impl(c, report, bk_noise, ksk_noise, mask_seed, true, bk_body, ksk_body, lwe_key, tlwe_key, bk_limit, ksk_limit);
+}
+
+// the same audit of a packing key (mask_seed null: key is the full key [n][t][2][N]; else the bodies, the masks regenerated)
+int rs_audit_pack_key_dev(rs_ctx* c, rs_pack_key_audit* report, int32_t* noise, const int32_t* key, const uint8_t* mask_seed,
+                          const int32_t* lwe_key, const int32_t* tlwe_key, int32_t basebit, int32_t t, uint32_t limit) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!report || !key || !lwe_key || !tlwe_key) return fail(RS_ERR_INVALID, "null pointer");
+  size_t rows = 0;
+  rc = pack_key_shape(c, basebit, t, true, &rows);
+  if (rc) return rc;
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  int bad = pack_key_bits(lwe_key, p.n, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
+  const size_t lwe_words = bits.size();
+  bad = pack_key_bits(tlwe_key, p.N, bits);
+  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
+  rs::AuditReportDev dev{};
+  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
+    rs::AuditPackArgs a{};
+    a.key = key; a.noise = noise;
+    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    if (mask_seed) rs::kg_seed_words(mask_seed, a.seed);
+    a.n = p.n; a.N = p.N; a.t = t; a.basebit = basebit; a.limit = limit;
+    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
+    RS_HIP(rs::launch_audit_pack(a, mask_seed != nullptr, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
+    return RS_OK;
+  });
+  if (rc != RS_OK) return rc;
+  report->max_abs = dev.bk_max_abs;
+  report->over = dev.bk_over;
+  report->words = (uint64_t)rows * (uint64_t)p.N;
+  return RS_OK;
 }
 
 int rs_reserve(rs_ctx* c, size_t max_batch) { return rs_reserve_stream(c, max_batch, nullptr); }

@@ -89,6 +89,18 @@ RS_HD uint32_t au_bk_message(int c, uint32_t s, uint32_t g, int k, uint32_t S_k)
 }
 RS_HD uint32_t au_bk_noise(uint32_t b, uint32_t a_times_S, uint32_t message) { return b - a_times_S - message; }
 
+// ---- packing key (rs_audit_pack_key_dev): row i t + j is (a, b = a*S + e + s_i g_j X^0), the c = 1 formula above with t digits of
+// basebit bits; a seeded key's mask is the domain-14 stream of the mask seed (kKgPackMask of rs_pack.h, restated here so that the
+// audit includes nothing of the generator's) ----
+constexpr uint32_t kAuPackMask = 14;
+RS_HD void au_pack_row(uint64_t row, int t, int& i, int& j) {
+  i = (int)(row / (uint64_t)t);
+  j = (int)(row - (uint64_t)i * (uint64_t)t);
+}
+RS_HD void au_pack_mask_block(const uint32_t (&key)[8], uint64_t row, int blk, uint32_t (&w)[16]) {
+  kg_chacha_block(key, kAuPackMask, row, (uint32_t)blk, w);
+}
+
 // ---- keyswitching key ----
 // sample s = (i t + j) 2^basebit + v
 RS_HD void au_ksk_sample(uint64_t s, int t, int basebit, int& i, int& j, int& v) {

@@ -3,6 +3,7 @@
 //   lwe_phase_kernel           phase = b - sum_k a_k key_k of LWE samples of any dimension up to kAuMaxDim
 //   audit_bk_kernel<SEEDED>    the noise words of TGSW rows: e = b - a'*S - message, a' from HBM or from the mask seed
 //   audit_ksk_kernel<SEEDED>   the noise word of every keyswitching sample, and the all-zero check of the v = 0 samples
+//   audit_pack_kernel<SEEDED>  the noise words of packing-key rows (rs_audit_pack_key_dev): the c = 1 formula with t digits of basebit bits
 // An object of its own, so that every other kernel keeps its instructions.
 //
 // All arithmetic is 32-bit integer (rs_audit.h): nothing here includes the split-key FP64 product that generated the key. The
@@ -186,6 +187,77 @@ __global__ __launch_bounds__(kAuThreads) void audit_bk_kernel(AuditArgs a) {
   }
 }
 
+// The packing key: audit_bk_kernel's walk (the set bits of S listed once per workgroup, the row's mask in LDS, a signed sum of
+// rotations per coefficient) on rows i t + j with the message s_i g_j X^0. A sparse sweep over the listed bits, on purpose another
+// loop than the generator's dense scalar-masked sweep (rs_packkey.hip): the two share the ChaCha streams and nothing else.
+template <bool SEEDED>
+__global__ __launch_bounds__(kAuThreads) void audit_pack_kernel(AuditPackArgs a) {
+  extern __shared__ uint32_t s_lds[];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, N = a.N, SW = N / 32;
+  uint32_t* s_a = s_lds + kAuBkHead;
+  uint32_t* s_S = s_a + N;
+  int* s_off = reinterpret_cast<int*>(s_S + SW);
+  uint16_t* s_list = reinterpret_cast<uint16_t*>(s_off + SW + 1);
+  for (int w = t; w < SW; w += kAuThreads) s_S[w] = a.tlwe_bits[w];
+  __syncthreads();
+  if (t == 0) {
+    int at = 0;
+    for (int w = 0; w < SW; ++w) { s_off[w] = at; at += __popc(s_S[w]); }
+    s_off[SW] = at;
+  }
+  __syncthreads();
+  for (int w = t; w < SW; w += kAuThreads) au_list_word(s_S[w], w, s_off[w], s_list);
+  __syncthreads();
+  const int cnt = s_off[SW];
+  uint32_t key[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) key[k] = a.seed[k];
+  AuTally tally{0u, 0ull};
+  const long rows = (long)a.n * a.t;
+  for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+    int i, j;
+    au_pack_row((uint64_t)row, a.t, i, j);
+    const uint32_t s = au_key_bit(a.lwe_bits, i), g = au_gadget(j, a.basebit);
+    const uint32_t* b_row;
+    if (SEEDED) {
+      for (int blk = t; blk < N / 16; blk += kAuThreads) {
+        uint32_t w[16];
+        au_pack_mask_block(key, (uint64_t)row, blk, w);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s_a[16 * blk + q] = w[q];
+      }
+      b_row = reinterpret_cast<const uint32_t*>(a.key) + row * N;
+    } else {
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.key) + row * 2 * N;
+      for (int k = t; k < N; k += kAuThreads) s_a[k] = src[k];
+      b_row = src + N;
+    }
+    __syncthreads();
+    for (int k0 = t; k0 < N; k0 += kAuThreads * kAuKpt) {
+      uint32_t acc[kAuKpt];
+      au_bk_products(s_a, N, s_list, cnt, k0, acc);
+#pragma unroll
+      for (int q = 0; q < kAuKpt; ++q) {
+        const int k = k0 + kAuThreads * q;
+        const uint32_t e = au_bk_noise(b_row[k], acc[q], au_bk_message(1, s, g, k, 0u));
+        au_tally_word(tally, e, a.limit);
+        if (a.noise) a.noise[row * N + k] = (int32_t)e;
+      }
+    }
+    __syncthreads();   // the mask is read to the end before the next row overwrites it
+  }
+  const uint32_t wmax = wave_max(tally.max_abs);
+  const unsigned long long wover = wave_sum64(tally.over);
+  if (lane == 0) { s_lds[wave] = wmax; s_lds[4 + 2 * wave] = (uint32_t)wover; s_lds[5 + 2 * wave] = (uint32_t)(wover >> 32); }
+  __syncthreads();
+  if (t == 0) {
+    AuTally all{0u, 0ull};
+    for (int w = 0; w < kAuWaves; ++w) au_tally_merge(all, AuTally{s_lds[w], ((unsigned long long)s_lds[5 + 2 * w] << 32) | s_lds[4 + 2 * w]});
+    if (all.max_abs) atomicMax(&a.report->bk_max_abs, all.max_abs);
+    if (all.over) atomicAdd(&a.report->bk_over, all.over);
+  }
+}
+
 hipError_t launch_lwe_phase(const PhaseArgs& a, int num_cus, hipStream_t st) {
   if (a.B <= 0) return hipSuccess;
   if (a.dim < 1 || a.dim > kAuMaxDim) return hipErrorInvalidValue;
@@ -204,6 +276,17 @@ hipError_t launch_audit_bk(const AuditArgs& a, bool seeded, int num_cus, hipStre
   const size_t lds = audit_bk_lds_bytes(a.N);
   if (seeded) hipLaunchKernelGGL(audit_bk_kernel<true>, grid, block, lds, st, a);
   else hipLaunchKernelGGL(audit_bk_kernel<false>, grid, block, lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_audit_pack(const AuditPackArgs& a, bool seeded, int num_cus, hipStream_t st) {
+  const long rows = (long)a.n * a.t;
+  if (rows <= 0) return hipSuccess;
+  if (a.N < kAuThreads * kAuKpt || a.N > 65536 || (a.N & (a.N - 1)) != 0) return hipErrorInvalidValue;   // the list holds uint16 positions
+  const dim3 grid((unsigned)std::min<long>(rows, 4L * num_cus)), block(kAuThreads);   // the placement of launch_audit_bk
+  const size_t lds = audit_bk_lds_bytes(a.N);
+  if (seeded) hipLaunchKernelGGL(audit_pack_kernel<true>, grid, block, lds, st, a);
+  else hipLaunchKernelGGL(audit_pack_kernel<false>, grid, block, lds, st, a);
   return hipGetLastError();
 }
 

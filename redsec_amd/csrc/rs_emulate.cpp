@@ -16,6 +16,7 @@
 #include "rs_host.h"
 #include "rs_keygen.h"
 #include "rs_pack.h"
+#include "rs_packkey.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
@@ -1499,6 +1500,108 @@ void rs_emu_audit_reduce(const int32_t* noise, long count, uint32_t limit, int p
   for (int p = parts - 1; p >= 0; --p) rs::au_tally_merge(all, tally[(size_t)p]);
   *max_abs = all.max_abs;
   *over = all.over;
+}
+
+// ---- the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev, rs_audit_pack_key_dev) through the functions of
+// rs_packkey.h and rs_audit.h ----
+static_assert(rs::kAuPackMask == (uint32_t)rs::kKgPackMask, "the audit restates the packing-key mask domain");
+int rs_emu_pack_keygen_tile() { return rs::kPgTile; }
+// pack_keygen_kernel for one row, tile by tile and thread by thread as the kernel places them: the window of ext = (-a, a) filled
+// block by block from the row's ChaCha stream, one 4-word chunk per thread and four bits of S, the masked adds on the seven live
+// words, noise and gadget word at the store -> body_row[N]
+void rs_emu_pack_keygen_row(const uint8_t* mask_seed, const uint8_t* noise_seed, int N, int basebit, int t, uint64_t row,
+                            const int32_t* lwe_key, int n, const int32_t* tlwe_key, double sigma, int32_t* body_row) {
+  uint32_t key[8], nkey[8];
+  rs::kg_seed_words(mask_seed, key);
+  rs::kg_seed_words(noise_seed, nkey);
+  const std::vector<uint32_t> lwe = emu_pack_bits(lwe_key, n), S = emu_pack_bits(tlwe_key, N);
+  const int tiles = N / rs::kPgTile;
+  std::vector<uint32_t> win((size_t)N + rs::kPgTile);
+  for (int tile = 0; tile < tiles; ++tile) {
+    const int k0 = tile * rs::kPgTile;
+    for (int th = 0; th < rs::kPgThreads; ++th)
+      for (int wb = th; wb < rs::pg_window_blocks(N); wb += rs::kPgThreads) {
+        uint32_t w[16];
+        rs::pg_window_block(key, row, N, k0, wb, w);
+        for (int q = 0; q < 16; ++q) win[16 * (size_t)wb + q] = w[q];
+      }
+    for (int th = 0; th < rs::kPgThreads; ++th) {
+      uint32_t acc[rs::kPgKpt] = {0u, 0u, 0u, 0u};
+      int c4 = th + N / 4;
+      const uint32_t* hi = &win[4 * (size_t)c4];
+      for (int wd = 0; wd < N / 32; ++wd)
+        for (int g = 0; g < 8; ++g) {
+          const uint32_t* lo = &win[4 * (size_t)(--c4)];
+          const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          for (int b = 0; b < 4; ++b) {
+            const uint32_t m = 0u - ((S[wd] >> (4 * g + b)) & 1u);
+            for (int q = 0; q < rs::kPgKpt; ++q) acc[q] += w[4 + q - b] & m;
+          }
+          hi = lo;
+        }
+      const int k = k0 + rs::kPgKpt * th;
+      int32_t e[4];
+      rs::pg_noise4(nkey, row, k, sigma, e);
+      uint32_t v[rs::kPgKpt];
+      for (int q = 0; q < rs::kPgKpt; ++q) v[q] = acc[q] + (uint32_t)e[q];
+      if (k == 0) {
+        int i, j;
+        rs::pg_row(row, t, i, j);
+        v[0] += rs::pg_key_bit(lwe.data(), i) * rs::pg_gadget(j, basebit);
+      }
+      for (int q = 0; q < rs::kPgKpt; ++q) body_row[k + q] = (int32_t)v[q];
+    }
+  }
+}
+// pack_expand_kernel for one row (the items row N/16 + blk of the flat grid): thread blk stores mask block blk, the body is copied
+// word blk + T r -> out[2][N]
+void rs_emu_pack_expand_row(const uint8_t* mask_seed, int N, uint64_t row, const int32_t* body_row, int32_t* out) {
+  uint32_t key[8];
+  rs::kg_seed_words(mask_seed, key);
+  const int T = N / 16;
+  for (int blk = 0; blk < T; ++blk) {
+    uint32_t w[16];
+    rs::pg_mask_block(key, row, blk, w);
+    for (int q = 0; q < 16; ++q) out[16 * blk + q] = (int32_t)w[q];
+    for (int r = 0; r < 16; ++r) out[N + blk + T * r] = body_row[blk + T * r];
+  }
+}
+// audit_pack_kernel: the noise words of packing-key row `row`. seeded = 0: stored = the full key's row int32[2][N]; seeded = 1:
+// stored = the body row int32[N], the mask regenerated from mask_seed. -> noise[N]
+void rs_emu_audit_pack_row(int seeded, const uint8_t* mask_seed, int N, int t, int basebit, uint64_t row, const int32_t* stored,
+                           const int32_t* lwe_key, int n, const int32_t* tlwe_key, int32_t* noise) {
+  const std::vector<uint32_t> lwe = emu_pack_bits(lwe_key, n), S = emu_pack_bits(tlwe_key, N);
+  std::vector<uint16_t> list((size_t)N);
+  int cnt = 0;
+  for (int w = 0; w < N / 32; ++w) cnt = rs::au_list_word(S[w], w, cnt, list.data());
+  std::vector<uint32_t> a((size_t)N);
+  const uint32_t* b_row;
+  if (seeded) {
+    uint32_t key[8];
+    rs::kg_seed_words(mask_seed, key);
+    for (int th = 0; th < rs::kAuThreads; ++th)
+      for (int blk = th; blk < N / 16; blk += rs::kAuThreads) {
+        uint32_t w[16];
+        rs::au_pack_mask_block(key, row, blk, w);
+        for (int q = 0; q < 16; ++q) a[16 * blk + q] = w[q];
+      }
+    b_row = reinterpret_cast<const uint32_t*>(stored);
+  } else {
+    for (int k = 0; k < N; ++k) a[k] = (uint32_t)stored[k];
+    b_row = reinterpret_cast<const uint32_t*>(stored) + N;
+  }
+  int i, j;
+  rs::au_pack_row(row, t, i, j);
+  const uint32_t s = rs::au_key_bit(lwe.data(), i), g = rs::au_gadget(j, basebit);
+  for (int th = 0; th < rs::kAuThreads; ++th)
+    for (int k0 = th; k0 < N; k0 += rs::kAuThreads * rs::kAuKpt) {
+      uint32_t acc[rs::kAuKpt];
+      rs::au_bk_products(a.data(), N, list.data(), cnt, k0, acc);
+      for (int q = 0; q < rs::kAuKpt; ++q) {
+        const int k = k0 + rs::kAuThreads * q;
+        noise[k] = (int32_t)rs::au_bk_noise(b_row[k], acc[q], rs::au_bk_message(1, s, g, k, 0u));
+      }
+    }
 }
 
 // ---- indexed gate batches (rs_gate_rows_dev, rs_gate3_dev) through the functions of rs_rows.h, as gate_rows_kernel places them: a

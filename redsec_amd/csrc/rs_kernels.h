@@ -179,6 +179,25 @@ struct PackArgs {
   int n, N, basebit, t;
 };
 hipError_t launch_pack(const PackArgs& a, hipStream_t st);
+// the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev; streams and placement of rs_packkey.h): row i t + j is
+// (a, a*S + e + s_i g_j X^0), a the domain-14 words of the mask seed, e the domain-15 Gaussians of the noise seed
+struct PackKeygenArgs {
+  int32_t* body;                                      // [n][t][N]
+  const uint32_t* lwe_bits; const uint32_t* tlwe_bits;   // private device copies, 32 bits per word: [ceil(n / 32)], [N / 32]
+  uint32_t seed[8];                                   // mask seed (domain 14)
+  uint32_t noise_seed[8];                             // noise seed (domain 15): travels as a kernel argument only
+  int n, N, basebit, t;
+  double sigma;
+};
+hipError_t launch_pack_keygen(const PackKeygenArgs& a, hipStream_t st);
+struct PackExpandArgs {
+  int32_t* key;                                       // [n][t][2][N]
+  const int32_t* body;                                // [n][t][N]
+  uint32_t seed[8];                                   // mask seed (domain 14)
+  long rows;                                          // n t
+  int N;
+};
+hipError_t launch_pack_expand(const PackExpandArgs& a, hipStream_t st);
 // device decryption and the exact noise audit of evaluation keys (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev;
 // per-word arithmetic of rs_audit.h, 32-bit integer only). Secret keys are private device copies packed 32 bits per word.
 constexpr int kAuMaxDim = 16384;                      // largest LWE dimension a packed key in LDS serves (rs_create's limit on n)
@@ -202,6 +221,18 @@ struct AuditArgs {
 };
 hipError_t launch_audit_bk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
 hipError_t launch_audit_ksk(const AuditArgs& a, bool seeded, int num_cus, hipStream_t st);
+// the same audit of a packing key (rs_audit_pack_key_dev): the c = 1 formula of a bk row with t digits of basebit bits; the tallies
+// go to the bk fields of the report
+struct AuditPackArgs {
+  const int32_t* key;                                 // full key [n][t][2][N]; seeded: the bodies [n][t][N]
+  int32_t* noise;                                     // optional output [n][t][N]
+  const uint32_t* lwe_bits; const uint32_t* tlwe_bits;   // [ceil(n / 32)], [N / 32]
+  uint32_t seed[8];                                   // seeded: the mask seed (domain 14)
+  int n, N, t, basebit;
+  uint32_t limit;
+  AuditReportDev* report;
+};
+hipError_t launch_audit_pack(const AuditPackArgs& a, bool seeded, int num_cus, hipStream_t st);
 // indexed gate batches (rs_gate_rows_dev, rs_gate3_dev): the combinations of GateRowsArgs (rs_rows.h) written to a.out
 hipError_t launch_gate_rows(const GateRowsArgs& a, int num_cus, hipStream_t st);
 // compiled circuits (rs_circuit_run_dev), per level: the staged combinations of CircuitLevelArgs (rs_circuit.h) written to a.out,

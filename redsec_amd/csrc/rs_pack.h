@@ -6,7 +6,7 @@
 //     rlwe[r] = (0, sum_c b_c X^c) - sum_{i < n, j < t} D_ij(X) K[i][j],    D_ij(X) = sum_c digit_j(a_i of sample rN + c) X^c,
 // K[i][j] = (a_ij, a_ij*S + e_ij + s_i 2^(32 - (j+1) basebit)) the packing key. Everything is 32-bit integer arithmetic: a
 // basebit-bit digit times a 32-bit word, accumulated mod 2^32, exact in any order. No floating point and no transform.
-// Streams of the key (owner's side only, redsec_amd/keygen.py pack_key; there is no device code for them):
+// Streams of the key (owner's side only: redsec_amd/keygen.py pack_key and, on the device, rs_packkey.h; none of it is in this file):
 //     domain 14  packing-key mask    row i t + j   mask seed (public)             a_ij[k] = word k, k < N
 //     domain 15  packing-key noise   row i t + j   owner's noise seed (private)   e_ij[k] = Gaussian k (words 4k .. 4k+3, kg_noise32)
 #pragma once

@@ -75,6 +75,11 @@ s_i and digit j < t, the ring sample K[i][j] = (a_ij, b_ij = a_ij*S + e_ij + s_i
   Domains 14 and 15 are disjoint from domains 1-13. Equal mask and noise seeds are refused. pack_key_mask / pack_key / pack /
   pack_sigma / pack_default restate it.
 
+The packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev, rs_audit_pack_key_dev; include/redsec_hip.h; INTEGRATION.md
+section 19): the bodies above generated by the device word for word, the full key [n][t][2][N] expanded from the seed and the
+bodies, and the noise words e_ij = b_ij - a_ij*S - s_i 2^(32-(j+1) basebit) X^0 of a key under its secret. pack_key_noise restates
+the audit (through _times_binary, a third arithmetic beside the device's two loops); pack_noise_limit gives the default limit.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -661,6 +666,35 @@ def pack_key(name, lwe_key, tlwe_key, mask_seed, noise_seed, basebit, t, stdev=N
             B[:, 0] += lwe[r // t] * (np.uint32(1) << (32 - (r % t + 1) * basebit).astype(np.uint32))
             out[lo:lo + chunk] = B.view(np.int32)
     return out.reshape(lwe.size, t, N) if whole else out
+
+
+def pack_key_noise(name, lwe_key, tlwe_key, key, basebit, t, mask_seed=None, rows=None, chunk=256):
+    """rs_audit_pack_key_dev restated: the noise words e = b - a*S - s_i 2^(32-(j+1) basebit) X^0 of packing-key rows i t + j (all n t
+    rows if rows is None) -> int32 [R][N]. Full key (mask_seed None): key holds the rows [R][2][N]; with a mask seed key holds the
+    body rows [R][N] and the masks are pack_key_mask's. The LWE dimension is len(lwe_key). A key of pack_key returns exactly its
+    domain-15 noise32 words."""
+    basebit, t = _check_digits(basebit, t)
+    N = _shape(name)["N"]
+    lwe = np.asarray(lwe_key).ravel().astype(np.uint32)
+    S = np.asarray(tlwe_key).ravel()
+    assert S.size == N, "tlwe_key must have N = %d words" % N
+    rows = np.arange(lwe.size * t) if rows is None else np.asarray(rows, np.int64).ravel()
+    stored = np.asarray(key, np.int32).reshape(len(rows), -1, N)
+    assert stored.shape[1] == (2 if mask_seed is None else 1), "stored rows have the wrong shape"
+    out = np.empty((len(rows), N), np.int32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(rows), chunk):
+            r = rows[lo:lo + chunk]
+            A = stored[lo:lo + chunk, 0] if mask_seed is None else pack_key_mask(mask_seed, N, r)
+            E = np.ascontiguousarray(stored[lo:lo + chunk, -1]).view(np.uint32) - _times_binary(np.ascontiguousarray(A).view(np.uint32), S)
+            E[:, 0] -= lwe[r // t] * (np.uint32(1) << (32 - (r % t + 1) * basebit).astype(np.uint32))
+            out[lo:lo + chunk] = E.view(np.int32)
+    return out
+
+
+def pack_noise_limit(stdev):
+    """Default limit of the packing-key audit = floor(8.58 stdev 2^32) + 1: the bound of noise_limits (|z| <= 8.572), not a statistic."""
+    return int(np.floor(GAUSS_BOUND * float(stdev) * 2.0 ** 32)) + 1
 
 
 def pack_digits(a, basebit, t):
