@@ -382,6 +382,29 @@ int rs_reserve_stream(rs_ctx* ctx, size_t max_batch, void* stream);
 int rs_bootstrap_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, int32_t mu, size_t B, void* stream);
 int rs_bootstrap(rs_ctx* ctx, int32_t* out, const int32_t* in, int32_t mu, size_t B);
 
+/* Sparse bootstraps: rs_bootstrap_dev for a batch of which the caller KNOWS most rows to be trivial
+ * samples (0, ..., 0, b), e.g. the output channels of a convolution whose ternary weights are all zero. in, out DEVICE
+ * int32[B][n+1] (out == in is allowed; any other overlap is the caller's error); live DEVICE int32[n_live]: the rows that are
+ * really bootstrapped; n_live a HOST value: the launch form is planned from it exactly as rs_bootstrap_dev plans from B.
+ *   A row named in live gets the words of rs_bootstrap_dev(in[r], mu).
+ *   AN UNLISTED ROW IS READ AT WORD n ONLY: it is the caller's promise of a trivial sample and gets (0, ..., 0, b'), b' =
+ *   coefficient 0 of the test vector rotated by the mod-switched in[r][n] (+-mu) -- the words the dense call produces for
+ *   (0, ..., 0, in[r][n]), where no CMUX runs and the keyswitch of a zero mask subtracts nothing.
+ * Entries of live outside [0, B) are ignored on the device; a repeated entry is harmless (the same words are written twice).
+ * Nothing else is validated on the device, and it never reads or writes outside in, out, live and the context's own buffers.
+ * n_live = 0 launches no rotation and no keyswitch (rs_last_launch and rs_last_kernel_ms then answer RS_ERR_STATE: nothing was
+ * launched); n_live = B with the identity list gives the dense call's words; B = 0 is a no-op that returns RS_OK.
+ * RS_ERR_INVALID: a null in or out, a null live with n_live > 0, n_live > B, row arithmetic that overflows.
+ * On the stream: in[live[i]] is gathered into the per-stream staging buffer of rs_gate_rows_dev (grown on demand to 2 n_live
+ * rows: a device-wide wait), all B rows of out are filled with the trivial result (each row reads its own word n before it is
+ * overwritten), the unchanged blind rotation and keyswitch take the n_live staged rows into the second half of the staging
+ * buffer, and that half is scattered into out[live[i]]. Asynchronous and stream-ordered; all three arithmetic modes and every
+ * parameter set, with the certificate rules of the other bootstrapped calls (the gated exact recomputation re-reads the staged
+ * rows, never in). rs_last_launch and rs_last_kernel_ms describe the compact launch of n_live rows; the gather and the fill run
+ * in front of the two timed intervals, the scatter behind them. */
+int rs_bootstrap_sparse_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, int32_t mu, size_t B, const int32_t* live, size_t n_live,
+                            void* stream);
+
 /* Programmable bootstrap: tfhe_blindRotateAndExtract_FFT with the test polynomial lut[(lut_first + b) % lut_count]
  * (DEVICE int32[lut_count][N]; lut_first lets a caller that shards a batch keep the batch-wide assignment)
  * followed by lweKeySwitch. With pbar = the phase of in[b] mod-switched to

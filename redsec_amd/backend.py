@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "rs_phase_dev", "rs_audit_keys_dev", "rs_audit_compressed_keys_dev",
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
+    "rs_bootstrap_sparse_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -140,6 +141,7 @@ def load_library(path=None):
     L.rs_reserve.argtypes = [vp, C.c_size_t]
     L.rs_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp]
     L.rs_bootstrap.argtypes = [vp, _i32p, _i32p, C.c_int32, C.c_size_t]
+    L.rs_bootstrap_sparse_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_size_t, vp, C.c_size_t, vp]
     L.rs_gate_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp]
     L.rs_gate.argtypes = [vp, C.c_int, _i32p, _i32p, _i32p, C.c_size_t]
     L.rs_gate_mu_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int32, C.c_size_t, vp]
@@ -633,6 +635,21 @@ class Backend:
         B = x.shape[0]
         out = self.empty(B, self.W) if out is None else out
         _check(self.L, self.L.rs_bootstrap_dev(self.h, self._ck_dev(out, self.W), self._ck_dev(x, self.W), int(mu), B, self._stream()))
+        return out
+
+    def bootstrap_sparse(self, rows, mu, live, out=None):
+        """bootstrap of a batch whose rows outside `live` are KNOWN trivial samples (rs_bootstrap_sparse_dev; INTEGRATION.md section
+        20). rows [B][W]; live: int32 CUDA tensor of the rows that are really bootstrapped (entries outside [0, B) are ignored). An
+        unlisted row is read at its last word only and gets the trivial sample the dense call yields for it. out may be rows."""
+        import torch
+        B = rows.shape[0]
+        out = self.empty(B, self.W) if out is None else out
+        assert out.numel() == B * self.W, "out must hold [B][n+1] words"
+        n_live = int(live.numel())
+        assert live.dtype == torch.int32 and (n_live == 0 or (live.is_cuda and live.is_contiguous() and live.device.index == self.device)), \
+            "live must be a contiguous int32 CUDA tensor on the context's device"
+        _check(self.L, self.L.rs_bootstrap_sparse_dev(self.h, self._ck_dev(out, self.W), self._ck_dev(rows, self.W), int(mu), B,
+                                                       C.c_void_p(live.data_ptr()) if n_live else None, n_live, self._stream()))
         return out
 
     def bootstrap_lut(self, x, lut, out=None, first=0):

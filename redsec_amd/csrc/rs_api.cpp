@@ -31,6 +31,7 @@
 #include "rs_pack.h"
 #include "rs_packkey.h"
 #include "rs_rlwe.h"
+#include "rs_sparse.h"
 
 namespace {
 
@@ -1244,6 +1245,46 @@ int rs_gate3_dev(rs_ctx* c, int op, int32_t* out, const int32_t* a0, const int32
   a.in_rows = (long)B;
   a.B = (long)B; a.W = c->p.n + 1;
   return run_gate_rows(c, (hipStream_t)stream, out, a, 1 << 29);
+}
+
+// ---- sparse bootstraps ----
+// On the stream: the live rows are gathered into the first half of the lane's staging buffer, all B rows of `out` get the trivial
+// result (each row reads its own word n first, and the gather came before: out may be in), the unchanged run_bootstrap path takes
+// the staged rows into the second half of the staging buffer (the gated exact recomputation of FFT mode re-reads the staged rows),
+// and that half is scattered over the live rows. The gather and the fill lie in front of the timed intervals, the scatter behind.
+int rs_bootstrap_sparse_dev(rs_ctx* c, int32_t* out, const int32_t* in, int32_t mu, size_t B, const int32_t* live, size_t n_live,
+                            void* stream) {
+  int rc = rows_ready(c);
+  if (rc) return rc;
+  const size_t W = (size_t)c->p.n + 1;
+  const char* why = "";
+  if (rs::sparse_check(out, in, live, B, n_live, W, &why) != 0) return fail(RS_ERR_INVALID, "sparse bootstrap refused: %s", why);
+  if (B == 0) return RS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Lane* ln = nullptr;
+  rc = lane_of(c, st, &ln);
+  if (rc) return rc;
+  rs::SparseArgs a{};
+  a.in = in; a.out = out; a.live = live; a.B = (long)B; a.n_live = (long)n_live; a.W = (int)W; a.mu = mu; a.logn = c->logn;
+  if (n_live == 0) {
+    // no rotation and no keyswitch: the stream's last launch is "none" (rs_last_launch and rs_last_kernel_ms answer RS_ERR_STATE)
+    RS_HIP(rs::launch_sparse_fill(a, c->num_cus, st));
+    ln->last = rs::LaunchInfo{};
+    ln->ev_valid = false;
+    return RS_OK;
+  }
+  rc = ensure_rows(ln, 2 * n_live, W);
+  if (rc) return rc;
+  a.rows = ln->d_rows;
+  int32_t* boot = ln->d_rows + n_live * W;
+  a.boot = boot;
+  RS_HIP(rs::launch_sparse_gather(a, c->num_cus, st));
+  RS_HIP(rs::launch_sparse_fill(a, c->num_cus, st));
+  const Combo x{ln->d_rows, nullptr, 1, 0, 0, nullptr};
+  rc = run_bootstrap(c, st, boot, &x, 1, 0, mu, Lut{}, n_live);
+  if (rc) return rc;
+  RS_HIP(rs::launch_sparse_scatter(a, c->num_cus, st));
+  return RS_OK;
 }
 
 // ---- compiled circuits ----

@@ -23,6 +23,7 @@
 #include "rs_ntt.h"
 #include "rs_circuit.h"
 #include "rs_rows.h"
+#include "rs_sparse.h"
 
 namespace {
 
@@ -1659,6 +1660,44 @@ int rs_emu_circuit_fold(int32_t* u, long B, long mux_rows, int words) {
   rs::CircuitFoldArgs a{u, B, mux_rows, words};
   for (long m = 0; m < mux_rows; ++m)
     for (int lane = 0; lane < 64; ++lane) rs::circuit_fold_lane(a, m, lane);
+  return 0;
+}
+
+// ---- sparse bootstraps (rs_bootstrap_sparse_dev) through the functions of rs_sparse.h, as the kernels of rs_sparse.hip place them:
+// a wave of 64 lanes per row ----
+// the b word of the bootstrapped trivial sample (0, ..., 0, b) on the ring N = 2^logn
+int32_t rs_emu_sparse_trivial(int32_t b, int32_t mu, int logn) { return rs::sparse_trivial_word(b, mu, logn); }
+// the host validation of rs_bootstrap_sparse_dev: 0, or -1 for what it refuses (the pointers are only compared with null)
+int rs_emu_sparse_check(const void* out, const void* in, const void* live, size_t B, size_t n_live, size_t W) {
+  return rs::sparse_check(out, in, live, B, n_live, W, nullptr);
+}
+// sparse_gather_kernel: rows[n_live][W] = in[live[i]], the zero sample for an entry outside [0, B)
+int rs_emu_sparse_gather(const int32_t* in, const int32_t* live, long n_live, long B, int W, int32_t* rows) {
+  if (rs::sparse_check(in, in, live, (size_t)B, (size_t)n_live, (size_t)W, nullptr) != 0 || B < 0 || n_live < 0 || W < 1 || !rows) return -1;
+  rs::SparseArgs a{};
+  a.in = in; a.live = live; a.rows = rows; a.B = B; a.n_live = n_live; a.W = W;
+  for (long i = 0; i < n_live; ++i)
+    for (int lane = 0; lane < 64; ++lane) rs::sparse_gather_lane(a, i, lane);
+  return 0;
+}
+// sparse_fill_kernel: out[B][W] = the trivial results of in's b words; out may be in (word n of a row is read before its lanes store)
+int rs_emu_sparse_fill(const int32_t* in, int32_t* out, long B, int W, int32_t mu, int logn) {
+  if (!in || !out || B < 0 || W < 1 || logn < rs::kGenMinLogN || logn > rs::kGenMaxLogN) return -1;
+  rs::SparseArgs a{};
+  a.in = in; a.out = out; a.B = B; a.W = W; a.mu = mu; a.logn = logn;
+  for (long r = 0; r < B; ++r) {
+    const int32_t b = a.in[r * a.W + a.W - 1];
+    for (int lane = 0; lane < 64; ++lane) rs::sparse_fill_lane(a, r, lane, b);
+  }
+  return 0;
+}
+// sparse_scatter_kernel: out[live[i]] = boot[i]; an entry outside [0, B) writes nothing
+int rs_emu_sparse_scatter(int32_t* out, const int32_t* boot, const int32_t* live, long n_live, long B, int W) {
+  if (rs::sparse_check(out, out, live, (size_t)B, (size_t)n_live, (size_t)W, nullptr) != 0 || B < 0 || n_live < 0 || W < 1 || !boot) return -1;
+  rs::SparseArgs a{};
+  a.out = out; a.boot = boot; a.live = live; a.B = B; a.n_live = n_live; a.W = W;
+  for (long i = 0; i < n_live; ++i)
+    for (int lane = 0; lane < 64; ++lane) rs::sparse_scatter_lane(a, i, lane);
   return 0;
 }
 

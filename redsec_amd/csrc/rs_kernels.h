@@ -241,6 +241,12 @@ struct CircuitLevelArgs;
 struct CircuitFoldArgs;
 hipError_t launch_circuit_rows(const CircuitLevelArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_circuit_fold(const CircuitFoldArgs& a, int num_cus, hipStream_t st);
+// sparse bootstraps (rs_bootstrap_sparse_dev): the rows of SparseArgs (rs_sparse.h) gathered into a.rows, the trivial results
+// written to all of a.out, and a.boot scattered over the live rows of a.out
+struct SparseArgs;
+hipError_t launch_sparse_gather(const SparseArgs& a, int num_cus, hipStream_t st);
+hipError_t launch_sparse_fill(const SparseArgs& a, int num_cus, hipStream_t st);
+hipError_t launch_sparse_scatter(const SparseArgs& a, int num_cus, hipStream_t st);
 hipError_t launch_polymul(int cfg, int mode, const int32_t* a_small, const int32_t* b_torus, int32_t* out, double* scratch,
                           const double* tw, Field f, double scale, long count, unsigned long long* dev_flag, hipStream_t st);
 hipError_t launch_lincomb(int32_t* out, const int32_t* x, int32_t cx, const int32_t* y, int32_t cy, int32_t bconst, int W, long B,

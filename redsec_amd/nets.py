@@ -79,10 +79,30 @@ class MnistSignNet:
         return (b.astype(np.int64) << 20).astype(np.uint64).astype(np.uint32).view(np.int32)
 
 
-class EncryptedMnist:
-    """Device-resident evaluation on a redsec_amd.Backend whose keys are loaded."""
+def dead_outputs(zero):
+    """bool [Cout] (zero uint8 [fh][fw][Cin][Cout]) or [M] (zero uint8 [K][M]): true where EVERY tap of the output channel or neuron
+    has its zero byte set. Such an output's linear stage adds nothing to the bias: it is the trivial sample (0, bias) whatever the
+    input, and its sign bootstrap is known in advance to skip every CMUX."""
+    z = np.asarray(zero)
+    return (z.reshape(-1, z.shape[-1]) != 0).all(axis=0)
 
-    def __init__(self, backend, net):
+
+def live_rows(dead, positions=1):
+    """int32 rows of a [positions][C] stage (row = position * C + channel) whose channel is not dead, ascending; None when no
+    channel is dead (the stage then keeps the dense call)."""
+    dead = np.asarray(dead, bool)
+    if not dead.any():
+        return None
+    return np.flatnonzero(np.tile(~dead, positions)).astype(np.int32)
+
+
+class EncryptedMnist:
+    """Device-resident evaluation on a redsec_amd.Backend whose keys are loaded. skip_dead=True: an FC sign stage with dead
+    neurons (dead_outputs: every weight zero) goes through Backend.bootstrap_sparse with the live list built here, once; the words
+    are those of skip_dead=False (the default, which keeps the dense launches exactly). run(shard=True) and run_many keep the dense
+    calls either way."""
+
+    def __init__(self, backend, net, skip_dead=False):
         import torch
         self.be = backend
         self.net = net
@@ -93,6 +113,11 @@ class EncryptedMnist:
         s, z, b = net.final
         self.final = (t(s), t(z), t(MnistSignNet.bias_to_torus(b)))
         self.pool = dict(H=28, Wd=28, C=1, win_h=2, win_w=2, stride_h=2, stride_w=2, off_h=0, off_w=0, Ho=14, Wo=14)
+        self.live = [None] * len(net.fc)          # per FC sign stage: the live rows on the device, or None = dense
+        if skip_dead:
+            for li, (_, zero, _) in enumerate(net.fc):
+                rows = live_rows(dead_outputs(zero))
+                self.live[li] = None if rows is None else t(rows)
 
     def run(self, image_ct, taps=None, shard=False):
         """image_ct: int32 CUDA tensor [784][W] (encrypt_image.cpp order: row-major pixels).
@@ -117,7 +142,8 @@ class EncryptedMnist:
             taps["pre0"], taps["bits0"] = pre0, bits
         for li, (sign, zero, bias) in enumerate(self.fc):
             pre = be.linear_fc(bits, sign, zero, zero_tap_b=0, bias_b=bias)   # BinFunc: zero taps add nothing
-            bits = boot(pre)
+            live = None if shard else self.live[li]
+            bits = boot(pre) if live is None else be.bootstrap_sparse(pre, MU_SIGN, live)   # a dead neuron's row is (0, bias)
             if taps is not None:
                 taps["pre%d" % (li + 1)], taps["bits%d" % (li + 1)] = pre, bits
         sign, zero, bias = self.final
@@ -283,13 +309,22 @@ class EncryptedCifar:
     int32[Cout])]; fcs [(sign, zero uint8[K][M], bias int32[M])], the last one being the logits layer
     (layouts of lib/BinFunc.cpp:388). shard=True: gate-parallel over the ranks of an initialised
     torch.distributed job as in EncryptedMnist.run (693,248 bootstraps per binarynet image, the
-    largest all_gather 131,072 x 351 words)."""
+    largest all_gather 131,072 x 351 words).
+
+    skip_dead=True (with maxpool="fused"): a stage with dead output channels or neurons (dead_outputs: every weight zero, 356 of
+    binarynet's 512 conv6 channels) goes through Backend.bootstrap_sparse with a live list built here, once: every conv and FC sign
+    stage, and the fused max-pool stage behind a pooled conv -- a dead channel's four taps are trivial samples, so their sum + 3/16
+    is one too. Row (h, w, c) is live iff channel c is. Stages without a dead output keep calling bootstrap, and the words and the
+    `taps` records are those of skip_dead=False, the default, which keeps the dense launches exactly. Not covered: maxpool="chain"
+    (refused together with skip_dead), run(shard=True) (keeps the dense calls), the ReLU (LUT) nets and the C++ layer mirror."""
 
     MU8 = 1 << 29   # modSwitchToTorus32(1, 8): the encoding bootsOR assumes
 
-    def __init__(self, backend, net, maxpool="fused"):
+    def __init__(self, backend, net, maxpool="fused", skip_dead=False):
         import torch
         assert maxpool in ("fused", "chain")
+        if skip_dead and maxpool != "fused":
+            raise ValueError('skip_dead covers maxpool="fused" only')
         self.be = backend
         self.maxpool = maxpool
         dev = "cuda:%d" % backend.device
@@ -301,6 +336,23 @@ class EncryptedCifar:
         self.fcs = [(t(s), t(z), t(tor(b))) for s, z, b in net.fcs]
         self._pool_index = {}
         self._t = t
+        self.live = {}                 # stage name -> the live rows on the device; a stage that is not here is dense
+        if skip_dead:
+            H = 32
+            for li, (_, zero, _) in enumerate(net.convs):
+                dead = dead_outputs(zero)
+                stages = [("conv%d" % (li + 1), H * H)]
+                if li % 2 == 1:
+                    H //= 2
+                    stages.append(("maxpool%d" % (li + 1), H * H))
+                for name, positions in stages:
+                    rows = live_rows(dead, positions)
+                    if rows is not None:
+                        self.live[name] = t(rows)
+            for i, (_, zero, _) in enumerate(net.fcs[:-1]):
+                rows = live_rows(dead_outputs(zero))
+                if rows is not None:
+                    self.live["fc%d" % (i + 1)] = t(rows)
 
     def _pool(self, H, Wd, C):
         """[tap][out] input rows of a 2x2 stride-2 window over [H][Wd][C] (MaxPooling::prep index math)."""
@@ -324,6 +376,12 @@ class EncryptedCifar:
         else:
             run_stage = lambda fn, *xs: fn(*xs)
 
+        def boot(name, mu=MU_SIGN):
+            live = None if shard else self.live.get(name)
+            if live is None:
+                return lambda r: be.bootstrap(r, mu)
+            return lambda r: be.bootstrap_sparse(r, mu, live)
+
         def stage(fn, *xs, name=None, kind="sign", mu=MU_SIGN):
             out = run_stage(fn, *xs)
             if taps is not None:
@@ -343,11 +401,11 @@ class EncryptedCifar:
             pooled = li % 2 == 1
             fused = pooled and self.maxpool == "fused"
             mu = MU_SIGN if not pooled else ((1 << 28) if fused else self.MU8)
-            bits = stage(lambda r: be.bootstrap(r, mu), pre, name="conv%d" % (li + 1), mu=mu)
+            bits = stage(boot("conv%d" % (li + 1), mu), pre, name="conv%d" % (li + 1), mu=mu)
             if fused:
                 win = dict(H=H, Wd=Wd, C=C, win_h=2, win_w=2, stride_h=2, stride_w=2, off_h=0, off_w=0, Ho=H // 2, Wo=Wd // 2)
                 pre = be.sumpool(bits.view(H, Wd, C, W), win, bias_b=self.pool_bias).view(-1, W)
-                bits = stage(lambda r: be.bootstrap(r, MU_SIGN), pre, name="maxpool%d" % (li + 1))
+                bits = stage(boot("maxpool%d" % (li + 1)), pre, name="maxpool%d" % (li + 1))
                 H //= 2; Wd //= 2
             elif pooled:
                 idx = self._pool(H, Wd, C)
@@ -363,7 +421,7 @@ class EncryptedCifar:
             pre = be.linear_fc(v, sign, zero, zero_tap_b=0, bias_b=bias)
             if i == len(self.fcs) - 1:
                 return pre
-            v = stage(lambda r: be.bootstrap(r, MU_SIGN), pre, name="fc%d" % (i + 1))
+            v = stage(boot("fc%d" % (i + 1)), pre, name="fc%d" % (i + 1))
 
 
 class _Rows:
