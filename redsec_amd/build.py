@@ -18,8 +18,6 @@ INCLUDE = os.path.join(ROOT, "include")
 HIP_LIB = os.path.join(HERE, "libredsec_hip.so")
 EMU_LIB = os.path.join(HERE, "librs_emulate.so")
 
-HIP_SOURCES = ["rs_bootstrap.hip", "rs_bootstrap_split.hip", "rs_bootstrap_listed.hip", "rs_general.hip", "rs_kernels.hip", "rs_keyswitch_wide.hip", "rs_seeded.hip", "rs_pubkey.hip", "rs_rlwe.hip", "rs_pack.hip", "rs_packkey.hip", "rs_audit.hip", "rs_rows.hip", "rs_circuit.hip", "rs_sparse.hip", "rs_api.cpp"]
-HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", os.path.join(INCLUDE, "redsec_hip.h")]
 # THE recipe of the product library: what every object is compiled with, then (object name, source under csrc/, extra flags).
 # build_tree() below and, through it, tools/build_variant.sh and the ISA tools (--print-flags) read it from here.
 HIP_COMMON_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fPIC"]
@@ -59,8 +57,14 @@ HIP_OBJECTS = [
     ("rs_circuit", "rs_circuit.hip", []),
     # the gather, the trivial fill and the scatter of the sparse bootstraps (sparse_*_kernel), likewise
     ("rs_sparse", "rs_sparse.hip", []),
+    # the C ABI, host code only, in three units that share rs_api_internal.h: context and the bootstrapped path; the evaluation
+    # key (load, generate, expand); key material and client-side calls
     ("rs_api", "rs_api.cpp", []),
+    ("rs_api_keys", "rs_api_keys.cpp", []),
+    ("rs_api_client", "rs_api_client.cpp", []),
 ]
+HIP_SOURCES = [src for _, src, _ in HIP_OBJECTS]
+HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
 EMU_SOURCES = ["rs_emulate.cpp"]
 EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
 

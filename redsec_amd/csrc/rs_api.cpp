@@ -1,41 +1,27 @@
-// rs_api.cpp -- C ABI of libredsec_hip.so (declared in include/redsec_hip.h).
+// rs_api.cpp -- C ABI of libredsec_hip.so (declared in include/redsec_hip.h): the context, the bootstrapped path and housekeeping.
+// rs_api_keys.cpp holds the evaluation key (load, generate, expand), rs_api_client.cpp the key material and client-side calls;
+// rs_api_internal.h is what the three share.
 //
-// Host-side control only: context, key upload + transform, workspace, launches. No arithmetic on
-// ciphertexts happens on the CPU here, and there is no fallback path: without a HIP device every
-// compute entry point returns RS_ERR_NO_DEVICE.
-#include "redsec_hip.h"
-
-#include <hip/hip_runtime.h>
+// Host-side control only: context, workspace, launches. No arithmetic on ciphertexts happens on the CPU here, and there is no
+// fallback path: without a HIP device every compute entry point returns RS_ERR_NO_DEVICE.
+#include "rs_api_internal.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <climits>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <new>
-#include <set>
 #include <string>
-#include <vector>
 
-#include "rs_circuit.h"
 #include "rs_diag.h"
-#include "rs_host.h"
 #include "rs_general.h"
-#include "rs_kernels.h"
-#include "rs_keygen.h"
-#include "rs_pack.h"
-#include "rs_packkey.h"
-#include "rs_rlwe.h"
 #include "rs_sparse.h"
 
-namespace {
+namespace rs {
 
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -47,96 +33,16 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define RS_HIP(call)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess) return fail(RS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
+int use_device(rs_ctx* c) {
+  if (!c) return fail(RS_ERR_INVALID, "null context");
+  RS_HIP(hipSetDevice(c->device));
+  return RS_OK;
+}
 
-}  // namespace
+}  // namespace rs
 
-// Everything a launch writes besides its outputs lives in a LANE = the per-stream slice of a context:
-// the extracted-sample workspace between blind rotation and keyswitch, the persistent-wave work counter,
-// the certificate slots, the convolution scratch and the timing events. Calls on DIFFERENT streams of one
-// context therefore never share mutable state (calls on one stream are ordered by the stream itself).
-constexpr unsigned kCertSlots = 1024;   // ring of per-call certificate slots; slot kCertSlots = running max, +1 = recomputed calls
-struct Lane {
-  hipStream_t stream = nullptr;
-  int32_t* d_u0 = nullptr;
-  int32_t* d_u1 = nullptr;
-  size_t ws_batch = 0;
-  size_t sample_words = rs::kN + 1;       // words of one extracted sample (N + 1)
-  unsigned int* d_counter = nullptr;      // work counter of the persistent blind-rotate launches
-  unsigned long long* d_cert = nullptr;   // [kCertSlots + 2]
-  unsigned slot_next = 0;
-  uint32_t* d_conv_scratch = nullptr;     // expanded weights of the tiled convolution (grown on demand)
-  size_t conv_scratch_words = 0;
-  uint32_t* d_ks_scratch = nullptr;       // partial sums of the sliced (small-batch) keyswitch (grown on demand; <= ~50 MB)
-  size_t ks_scratch_words = 0;
-  int* d_progress = nullptr;              // XCD cohort table of the split lock-step kernel: [8][kCohortSlots] step counts
-  int32_t* d_rows = nullptr;              // materialised combinations of the indexed gate batches: [rows_batch][n + 1] (grown on demand)
-  size_t rows_batch = 0;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  bool ev_valid = false;
-  rs::LaunchInfo last;
-  rs::KsPlan last_ks; bool ks_ran = false;   // form of the last keyswitch on this stream (rs_last_keyswitch)
-  // enforced split-mode certificate: the lane's running maximum is copied here (pinned host memory) behind every general-kernel
-  // call, and looked at by the next call, rs_certify and rs_sync
-  unsigned long long* h_split_max = nullptr;
-};
-
-// A compiled circuit (rs_circuit_create): the validated cell table on the device and the level cuts on the host. It belongs to
-// its context, which keeps the set of live handles: a handle that is not in the set is refused, never followed.
-struct rs_circuit {
-  rs::Cell* d_cells = nullptr;
-  std::vector<uint32_t> level_end, level_mux;   // per level: one past its last cell, and how many of its cells (the last ones) are MUX
-  size_t n_cells = 0, n_inputs = 0;
-  size_t widest = 0;                            // max over the levels of cells + MUX cells: staged rows per lane
-};
-
-struct rs_ctx {
-  rs_params p{};
-  int device = 0;
-  int cfg = 0;  // 0 default128-shaped gadget, 1 redsec_v2-shaped gadget
-  rs::Tables tables;
-  int mode = 1;  // RS_MODE_FFT by default; RS_MODE_EXACT_NTT = 0
-  double cert_limit = RS_CERTIFICATE_LIMIT;
-  rs::LaunchOpts opts;
-  int ks_force = rs::kKsAuto;      // RS_KS_FORM=wide|tiled (diagnostic, read once in rs_create): rs_host.h keyswitch_form
-  double* d_tw = nullptr;          // exact-NTT tables (kTwTotal doubles)
-  double* d_tw_fft = nullptr;      // FFT tables (kFftTwDoubles doubles)
-  double* d_bk_ntt = nullptr;      // key in the NTT domain
-  double* d_bk_fft = nullptr;      // key in the FFT domain
-  // general ring path (rs_general.h): every parameter set has it; sets outside the specialised N = 1024 kernels
-  // (`general`) have nothing else
-  bool general = false;
-  int wgs_cfg = -1;                // gadget id of the lock-step split-key kernel, or -1 (general kernels only)
-  int logn = 10;
-  double split_bound = 0.0;        // a-priori error bound of the split-key product (rs_general.h; the mode is offered below 1/2)
-  double split_cert_limit = 0.25;    // enforced on the general kernels' rounding distances (REDSEC_SPLIT_CERT_LIMIT lowers it: tests)
-  std::atomic<bool> inexact{false};  // a split-mode call rounded a value 1/4 or more away from an integer: sticky, RS_ERR_INEXACT
-  double* d_tw_gen = nullptr;      // gen_make_twiddles(logn)
-  double* d_bk_gen = nullptr;      // split key in the FFT domain
-  int32_t* d_ksk = nullptr;
-  size_t bk_bytes = 0, ksk_bytes = 0;
-  bool keys = false;
-  int num_cus = 256;
-  bool timing = false;
-  std::mutex lanes_mu;                              // guards the map (a lane itself belongs to its stream's caller)
-  std::map<hipStream_t, std::unique_ptr<Lane>> lanes;
-  std::mutex host_mu;                               // serialises the synchronous host-pointer calls (shared staging buffers)
-  int32_t* d_io[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t io_batch = 0;
-  // rs_allgather_rows: private copy stream, "my slice is computed" / "my copies are done" events, peers already enabled
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_slice = nullptr, ev_copied = nullptr, ev_staged = nullptr;
-  bool copied_recorded = false;
-  std::vector<int> peers_enabled, peers_denied;
-  int32_t* h_stage = nullptr;                       // pinned staging buffer of this context's slice (host-staged exchange only)
-  size_t h_stage_bytes = 0;
-  std::mutex circuits_mu;
-  std::set<rs_circuit*> circuits;                   // live handles of rs_circuit_create
-};
+using rs::fail;
+using rs::use_device;
 
 namespace {
 
@@ -158,12 +64,6 @@ bool gate_coef(rs_gate_op op, GateCoef* g) {
     case RS_ORYN:  *g = {e8, 1, -1}; return true;
   }
   return false;
-}
-
-int use_device(rs_ctx* c) {
-  if (!c) return fail(RS_ERR_INVALID, "null context");
-  RS_HIP(hipSetDevice(c->device));
-  return RS_OK;
 }
 
 void free_lane(Lane* ln) {
@@ -425,47 +325,11 @@ void destroy_ctx(rs_ctx* c) {
 
 bool env_on(const char* name) { const char* v = getenv(name); return v && *v && strcmp(v, "0") != 0; }
 
-// ---- helpers of the secret-key calls on device data (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) ----
-// a 0/1 key appended to `bits`, 32 per word from a fresh word on; the index of the first word outside {0, 1}, or -1
-int pack_key_bits(const int32_t* key, int count, std::vector<uint32_t>& bits) {
-  const size_t base = bits.size();
-  bits.resize(base + (size_t)(count + 31) / 32, 0u);
-  for (int i = 0; i < count; ++i) {
-    if (key[i] != 0 && key[i] != 1) return i;
-    bits[base + ((size_t)i >> 5)] |= (uint32_t)key[i] << (i & 31);
-  }
-  return -1;
-}
-
-// run(d_words, d_extra) with a private device buffer that holds `words` followed by `extra` zeroed bytes. The secret leaves the
-// device (and `words`) before this returns, on the error paths too, as in keygen_impl.
-template <class Run>
-int with_secret_copy(std::vector<uint32_t>& words, size_t extra, Run run) {
-  const size_t key_bytes = (words.size() * sizeof(uint32_t) + 15) & ~(size_t)15, bytes = key_bytes + extra;
-  char* d = nullptr;
-  auto body = [&]() -> int {
-    RS_HIP(hipMalloc(&d, bytes));
-    RS_HIP(hipMemset(d, 0, bytes));
-    RS_HIP(hipMemcpy(d, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return run(reinterpret_cast<const uint32_t*>(d), d + key_bytes);
-  };
-  const int rc = body();
-  std::fill(words.begin(), words.end(), 0u);
-  if (!d) return rc;
-  (void)hipDeviceSynchronize();
-  const hipError_t ez = hipMemset(d, 0, bytes);
-  const hipError_t es = hipDeviceSynchronize();
-  (void)hipFree(d);
-  if (rc != RS_OK) return rc;
-  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
-  return RS_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-const char* rs_last_error(void) { return g_err.c_str(); }
+const char* rs_last_error(void) { return rs::g_err.c_str(); }
 const char* rs_version(void) { return "redsec_hip 0.4 (gfx950; fp64 fft with on-device exact recomputation + exact fp64-carried ntt + split-key fft, N up to 8192)"; }
 
 int rs_params_default128(rs_params* p) {
@@ -601,531 +465,6 @@ int rs_destroy(rs_ctx* c) {
   return rc;
 }
 
-// where load_keys_impl takes the key words from
-enum class KeySource { kHost, kDevice, kSynthetic, kCompressedHost, kCompressedDevice };
-
-// drops every key buffer of the context (a failed load leaves no half-built transform key behind)
-static void free_keys(rs_ctx* c) {
-  c->keys = false;
-  if (c->d_bk_ntt) { (void)hipFree(c->d_bk_ntt); c->d_bk_ntt = nullptr; }
-  if (c->d_bk_fft) { (void)hipFree(c->d_bk_fft); c->d_bk_fft = nullptr; }
-  if (c->d_bk_gen) { (void)hipFree(c->d_bk_gen); c->d_bk_gen = nullptr; }
-  if (c->d_ksk) { (void)hipFree(c->d_ksk); c->d_ksk = nullptr; }
-  c->bk_bytes = c->ksk_bytes = 0;
-}
-
-// the expansion arguments of this context's parameter set (outputs and bodies filled in by the caller)
-static rs::ExpandArgs expand_args(const rs_ctx* c, const uint8_t* mask_seed) {
-  rs::ExpandArgs e{};
-  rs::kg_seed_words(mask_seed, e.seed);
-  e.n = c->p.n; e.N = c->p.N; e.l = c->p.bk_l; e.t = c->p.ks_t; e.basebit = c->p.ks_basebit;
-  return e;
-}
-
-// bk / ksk: host arrays, device arrays, unused for the synthetic key of `seed` generated on the device (rs_load_synthetic_keys),
-// or the bodies of a compressed key (host or device) whose masks are regenerated from mask_seed
-static int load_keys_impl(rs_ctx* c, KeySource src, const int32_t* bk, const int32_t* ksk, uint64_t seed,
-                          const uint8_t* mask_seed = nullptr) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (src != KeySource::kSynthetic && (!bk || !ksk)) return fail(RS_ERR_INVALID, "null key pointer");
-  const bool compressed = src == KeySource::kCompressedHost || src == KeySource::kCompressedDevice;
-  if (compressed && !mask_seed) return fail(RS_ERR_INVALID, "null mask seed");
-  const rs_params& p = c->p;
-  const size_t n_polys = (size_t)p.n * (size_t)(2 * p.bk_l) * 2;
-  const size_t bk_words = n_polys * (size_t)p.N;
-  const size_t ksk_samples = (size_t)p.N * p.ks_t * ((size_t)1 << p.ks_basebit);
-  const size_t ksk_words = ksk_samples * (size_t)(p.n + 1);
-  free_keys(c);
-  int32_t* d_bk = nullptr;     // staging copy of the key words (freed on every path)
-  int32_t* d_body = nullptr;   // staging copy of host bodies of a compressed key (freed on every path)
-  auto body = [&]() -> int {
-    RS_HIP(hipMalloc(&d_bk, bk_words * sizeof(int32_t)));
-    if (src == KeySource::kSynthetic) RS_HIP(rs::launch_synthetic_words(d_bk, seed, bk_words, nullptr));
-    else if (compressed) {
-      const int32_t* bk_body = bk;
-      if (src == KeySource::kCompressedHost) {
-        RS_HIP(hipMalloc(&d_body, bk_words / 2 * sizeof(int32_t)));
-        RS_HIP(hipMemcpy(d_body, bk, bk_words / 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-        bk_body = d_body;
-      }
-      rs::ExpandArgs e = expand_args(c, mask_seed);
-      e.bk = d_bk; e.bk_body = bk_body;
-      RS_HIP(rs::launch_expand_bk(c->logn, e, c->num_cus, nullptr));
-      RS_HIP(hipDeviceSynchronize());
-      if (d_body) { RS_HIP(hipFree(d_body)); d_body = nullptr; }
-    } else RS_HIP(hipMemcpy(d_bk, bk, bk_words * sizeof(int32_t), src == KeySource::kHost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
-    if (!c->general) {
-      // both transform domains are kept resident (62 + 62 MB default-128, 115 + 115 MB REDsec): the FFT mode's
-      // gated exact recomputation needs the NTT-domain key, and the mode can be switched per call
-      RS_HIP(hipMalloc(&c->d_bk_ntt, bk_words * sizeof(double)));
-      RS_HIP(hipMalloc(&c->d_bk_fft, bk_words * sizeof(double)));
-      RS_HIP(rs::launch_bk_transform(c->cfg, 0, d_bk, c->d_bk_ntt, c->d_tw, c->tables.f, c->tables.ninv, (long)n_polys, nullptr));
-      RS_HIP(rs::launch_bk_transform(c->cfg, 1, d_bk, c->d_bk_fft, c->d_tw_fft, c->tables.f, 0.0, (long)n_polys, nullptr));
-      c->bk_bytes = bk_words * sizeof(double);
-    }
-    if (c->d_tw_gen) {
-      // the split key: two transformed halves per polynomial (twice the bytes of one domain)
-      RS_HIP(hipMalloc(&c->d_bk_gen, 2 * bk_words * sizeof(double)));
-      RS_HIP(rs::launch_gen_bk_transform(c->logn, d_bk, c->d_bk_gen, c->d_tw_gen, (long)n_polys, c->num_cus, nullptr));
-      if (c->general) c->bk_bytes = 2 * bk_words * sizeof(double);
-    }
-    RS_HIP(hipDeviceSynchronize());
-    RS_HIP(hipFree(d_bk));
-    d_bk = nullptr;
-    RS_HIP(hipMalloc(&c->d_ksk, ksk_words * sizeof(int32_t)));
-    if (src == KeySource::kSynthetic) { RS_HIP(rs::launch_synthetic_words(c->d_ksk, seed ^ 0x6b73ull, ksk_words, nullptr)); RS_HIP(hipDeviceSynchronize()); }
-    else if (src == KeySource::kHost) RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyHostToDevice));
-    else if (src == KeySource::kDevice) { RS_HIP(hipMemcpy(c->d_ksk, ksk, ksk_words * sizeof(int32_t), hipMemcpyDeviceToDevice)); RS_HIP(hipDeviceSynchronize()); }
-    else {
-      const int32_t* ksk_body = ksk;
-      if (src == KeySource::kCompressedHost) {
-        RS_HIP(hipMalloc(&d_body, ksk_samples * sizeof(int32_t)));
-        RS_HIP(hipMemcpy(d_body, ksk, ksk_samples * sizeof(int32_t), hipMemcpyHostToDevice));
-        ksk_body = d_body;
-      }
-      rs::ExpandArgs e = expand_args(c, mask_seed);
-      e.ksk = c->d_ksk; e.ksk_body = ksk_body;
-      RS_HIP(rs::launch_expand_ksk(e, c->num_cus, nullptr));
-      RS_HIP(hipDeviceSynchronize());
-      if (d_body) { RS_HIP(hipFree(d_body)); d_body = nullptr; }
-    }
-    c->ksk_bytes = ksk_words * sizeof(int32_t);
-    return RS_OK;
-  };
-  rc = body();
-  if (rc != RS_OK) {
-    (void)hipDeviceSynchronize();
-    if (d_bk) (void)hipFree(d_bk);
-    if (d_body) (void)hipFree(d_body);
-    free_keys(c);
-    return rc;
-  }
-  c->keys = true;
-  return RS_OK;
-}
-
-int rs_load_keys(rs_ctx* c, const int32_t* bk, const int32_t* ksk) {
-  if (!bk || !ksk) return fail(RS_ERR_INVALID, "null key pointer");
-  return load_keys_impl(c, KeySource::kHost, bk, ksk, 0);
-}
-int rs_load_keys_dev(rs_ctx* c, const int32_t* bk, const int32_t* ksk) {
-  if (!bk || !ksk) return fail(RS_ERR_INVALID, "null key pointer");
-  return load_keys_impl(c, KeySource::kDevice, bk, ksk, 0);
-}
-int rs_load_synthetic_keys(rs_ctx* c, uint64_t seed) { return load_keys_impl(c, KeySource::kSynthetic, nullptr, nullptr, seed); }
-// a failed compressed load leaves no key, invalid arguments included
-static int load_compressed(rs_ctx* c, KeySource src, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!mask_seed || !bk_body || !ksk_body) { free_keys(c); return fail(RS_ERR_INVALID, "null pointer"); }
-  return load_keys_impl(c, src, bk_body, ksk_body, 0, mask_seed);
-}
-int rs_load_compressed_keys(rs_ctx* c, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
-  return load_compressed(c, KeySource::kCompressedHost, mask_seed, bk_body, ksk_body);
-}
-int rs_load_compressed_keys_dev(rs_ctx* c, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
-  return load_compressed(c, KeySource::kCompressedDevice, mask_seed, bk_body, ksk_body);
-}
-
-// rs_keygen_dev (noise_seed null) and rs_keygen_compressed_dev (the bodies only, masks of `seed`, noise of noise_seed)
-static int keygen_impl(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
-                       const uint8_t* noise_seed, double bk_stdev, double ks_stdev) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  const bool compressed = noise_seed != nullptr;
-  if (!bk || !ksk || !lwe_key || !tlwe_key || !seed) return fail(RS_ERR_INVALID, "null pointer");
-  if (((uintptr_t)bk & 15u) != 0) return fail(RS_ERR_INVALID, "bk must be 16-byte aligned");
-  if (compressed && memcmp(seed, noise_seed, 32) == 0)
-    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
-  if (!(std::isfinite(bk_stdev) && bk_stdev >= 0.0) || !(std::isfinite(ks_stdev) && ks_stdev >= 0.0))
-    return fail(RS_ERR_INVALID, "noise deviations must be finite and non-negative (bk %g, ks %g)", bk_stdev, ks_stdev);
-  if (!c->d_tw_gen) return fail(RS_ERR_INVALID, "split-key product not offered for this set: a-priori bound %.3g", c->split_bound);
-  const rs_params& p = c->p;
-  for (int i = 0; i < p.n; ++i)
-    if (lwe_key[i] != 0 && lwe_key[i] != 1) return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", i, lwe_key[i]);
-  for (int i = 0; i < p.N; ++i)
-    if (tlwe_key[i] != 0 && tlwe_key[i] != 1) return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", i, tlwe_key[i]);
-  // private device copy of the secret key [n + N] plus the rounding-distance flag; zeroed and freed before returning
-  const size_t key_bytes = ((size_t)(p.n + p.N) * sizeof(int32_t) + 15) & ~(size_t)15;
-  const size_t bytes = key_bytes + sizeof(unsigned long long);
-  char* d_sec = nullptr;
-  RS_HIP(hipMalloc(&d_sec, bytes));
-  rs::KeygenArgs a{};
-  a.bk = bk; a.ksk = ksk;
-  a.lwe_key = reinterpret_cast<const int32_t*>(d_sec);
-  a.tlwe_key = a.lwe_key + p.n;
-  rs::kg_seed_words(seed, a.seed);
-  if (compressed) rs::kg_seed_words(noise_seed, a.noise_seed);
-  a.compressed = compressed ? 1 : 0;
-  a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
-  a.bk_sigma = bk_stdev; a.ks_sigma = ks_stdev;
-  a.dev_flag = reinterpret_cast<unsigned long long*>(d_sec + key_bytes);
-  unsigned long long flag = 0;
-  auto body = [&]() -> int {
-    RS_HIP(hipMemcpy(d_sec, lwe_key, (size_t)p.n * sizeof(int32_t), hipMemcpyHostToDevice));
-    RS_HIP(hipMemcpy(d_sec + (size_t)p.n * sizeof(int32_t), tlwe_key, (size_t)p.N * sizeof(int32_t), hipMemcpyHostToDevice));
-    RS_HIP(hipMemset(a.dev_flag, 0, sizeof(unsigned long long)));
-    RS_HIP(rs::launch_keygen_bk(c->logn, a, c->d_tw_gen, c->num_cus, nullptr));
-    RS_HIP(rs::launch_keygen_ksk(a, c->num_cus, nullptr));
-    RS_HIP(hipDeviceSynchronize());
-    RS_HIP(hipMemcpy(&flag, a.dev_flag, sizeof flag, hipMemcpyDeviceToHost));
-    return RS_OK;
-  };
-  rc = body();
-  // the secret leaves the device before the call returns, on the error paths too
-  (void)hipDeviceSynchronize();
-  const hipError_t ez = hipMemset(d_sec, 0, bytes);
-  const hipError_t es = hipDeviceSynchronize();
-  (void)hipFree(d_sec);
-  if (rc != RS_OK) return rc;
-  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
-  double dist = 0.0;
-  memcpy(&dist, &flag, sizeof dist);
-  if (!(dist < rs::kSplitBoundEnforce))
-    return fail(RS_ERR_INEXACT, "key generation: a rounding distance of %.3g was observed in the a*S products (limit 1/4)", dist);
-  return RS_OK;
-}
-
-int rs_keygen_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* seed,
-                  double bk_stdev, double ks_stdev) {
-  return keygen_impl(c, bk, ksk, lwe_key, tlwe_key, seed, nullptr, bk_stdev, ks_stdev);
-}
-int rs_keygen_compressed_dev(rs_ctx* c, int32_t* bk_body, int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
-                             const uint8_t* mask_seed, const uint8_t* noise_seed, double bk_stdev, double ks_stdev) {
-  if (!noise_seed) return fail(RS_ERR_INVALID, "null pointer");
-  return keygen_impl(c, bk_body, ksk_body, lwe_key, tlwe_key, mask_seed, noise_seed, bk_stdev, ks_stdev);
-}
-
-int rs_expand_keys_dev(rs_ctx* c, int32_t* bk, int32_t* ksk, const uint8_t* mask_seed, const int32_t* bk_body, const int32_t* ksk_body) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!bk || !ksk || !mask_seed || !bk_body || !ksk_body) return fail(RS_ERR_INVALID, "null pointer");
-  if (((uintptr_t)bk & 15u) != 0) return fail(RS_ERR_INVALID, "bk must be 16-byte aligned");
-  rs::ExpandArgs e = expand_args(c, mask_seed);
-  e.bk = bk; e.ksk = ksk; e.bk_body = bk_body; e.ksk_body = ksk_body;
-  RS_HIP(rs::launch_expand_bk(c->logn, e, c->num_cus, nullptr));
-  RS_HIP(rs::launch_expand_ksk(e, c->num_cus, nullptr));
-  RS_HIP(hipDeviceSynchronize());
-  return RS_OK;
-}
-
-// seeded LWE ciphertexts (include/redsec_hip.h): the checks both directions share
-static int seeded_args(const rs_ctx* c, rs::SeededArgs* a, const uint8_t* mask_seed, uint64_t first, size_t B) {
-  if (B > 0 && B - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + B = %llu + %zu passes 2^64", (unsigned long long)first, B);
-  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
-  rs::kg_seed_words(mask_seed, a->seed);
-  a->first = first; a->B = (long)B;
-  a->n = c->p.n; a->tile = rs::kg_ct_tile(c->p.n);
-  return RS_OK;
-}
-
-int rs_encrypt_seeded_dev(rs_ctx* c, int32_t* body, int32_t* ct, const int32_t* mu, size_t B, const int32_t* lwe_key,
-                          const uint8_t* mask_seed, const uint8_t* noise_seed, uint64_t first, double stdev) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!body || !mu || !lwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
-  if (memcmp(mask_seed, noise_seed, 32) == 0)
-    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
-  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
-  const int n = c->p.n;
-  for (int i = 0; i < n; ++i)
-    if (lwe_key[i] != 0 && lwe_key[i] != 1) return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", i, lwe_key[i]);
-  rs::SeededArgs a{};
-  rc = seeded_args(c, &a, mask_seed, first, B);
-  if (rc) return rc;
-  if (B == 0) return RS_OK;
-  // private device copy of the key, one bit per word, zero past n; zeroed and freed before returning
-  std::vector<uint32_t> bits((size_t)(n + 31) / 32, 0u);
-  for (int i = 0; i < n; ++i) bits[(size_t)i >> 5] |= (uint32_t)lwe_key[i] << (i & 31);
-  const size_t bytes = bits.size() * sizeof(uint32_t);
-  uint32_t* d_key = nullptr;
-  RS_HIP(hipMalloc(&d_key, bytes));
-  a.ct = ct; a.body = body; a.mu = mu; a.key_bits = d_key;
-  rs::kg_seed_words(noise_seed, a.noise_seed);
-  a.sigma = stdev;
-  auto run = [&]() -> int {
-    RS_HIP(hipMemcpy(d_key, bits.data(), bytes, hipMemcpyHostToDevice));
-    RS_HIP(rs::launch_encrypt_seeded(a, c->num_cus, nullptr));
-    RS_HIP(hipDeviceSynchronize());
-    return RS_OK;
-  };
-  rc = run();
-  std::fill(bits.begin(), bits.end(), 0u);
-  // the secret leaves the device before the call returns, on the error paths too
-  (void)hipDeviceSynchronize();
-  const hipError_t ez = hipMemset(d_key, 0, bytes);
-  const hipError_t es = hipDeviceSynchronize();
-  (void)hipFree(d_key);
-  if (rc != RS_OK) return rc;
-  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
-  return RS_OK;
-}
-
-int rs_expand_ciphertexts_dev(rs_ctx* c, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body, size_t B,
-                              void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!ct || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
-  rs::SeededArgs a{};
-  rc = seeded_args(c, &a, mask_seed, first, B);
-  if (rc) return rc;
-  if (B == 0) return RS_OK;
-  a.ct = ct; a.body = const_cast<int32_t*>(body);
-  RS_HIP(rs::launch_expand_ciphertexts(a, c->num_cus, (hipStream_t)stream));
-  return RS_OK;
-}
-
-// public-key encryption (include/redsec_hip.h; kernel of rs_pubkey.hip): needs no key, the rand seed travels as a kernel argument
-int rs_pk_encrypt_dev(rs_ctx* c, int32_t* ct, const int32_t* pk, size_t m, const int32_t* mu, const int32_t* base, size_t B,
-                      const uint8_t* rand_seed, uint64_t first, void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!ct || !pk || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
-  if (m < 1 || m > (size_t)INT32_MAX) return fail(RS_ERR_INVALID, "m = %zu is outside 1 .. 2^31 - 1", m);
-  if (B > 0 && B - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + B = %llu + %zu passes 2^64", (unsigned long long)first, B);
-  const size_t row_bytes = ((size_t)c->p.n + 1) * sizeof(int32_t);
-  if (B > (size_t)LONG_MAX / row_bytes || m > (size_t)LONG_MAX / row_bytes || (B + rs::kPkTile - 1) / rs::kPkTile > (size_t)INT32_MAX)
-    return fail(RS_ERR_INVALID, "B = %zu or m = %zu is too large for rows of %zu bytes", B, m, row_bytes);
-  if (B == 0) return RS_OK;
-  rs::PkArgs a{};
-  a.ct = ct; a.pk = pk; a.mu = mu; a.base = base;
-  rs::kg_seed_words(rand_seed, a.seed);
-  a.first = first; a.B = (long)B; a.m = (long)m; a.n = c->p.n;
-  const hipError_t e = rs::launch_pk_encrypt(a, (hipStream_t)stream);
-  for (uint32_t& w : a.seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the seed words does not outlive the call
-  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pk_encrypt failed: %s", hipGetErrorString(e));
-  return RS_OK;
-}
-
-// compact RLWE public keys (include/redsec_hip.h; kernels of rs_rlwe.hip): neither call needs a key, the ring is the context's
-int rs_rlwe_pk_encrypt_dev(rs_ctx* c, int32_t* rlwe, const int32_t* pk, const int32_t* mu, size_t count, const uint8_t* rand_seed,
-                           uint64_t first, double stdev, void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!rlwe || !pk || !mu || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
-  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
-  const size_t N = (size_t)c->p.N;
-  if (N < (size_t)rs::kRlMinN || N > (size_t)rs::kRlMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
-  const size_t R = count / N + (count % N ? 1 : 0), tiles = N / rs::kRlTile;
-  if (R > 0 && R - 1 > UINT64_MAX - first) return fail(RS_ERR_INVALID, "first + R = %llu + %zu passes 2^64", (unsigned long long)first, R);
-  if (count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N || R > (size_t)INT32_MAX / (2 * tiles))
-    return fail(RS_ERR_INVALID, "count = %zu is too large for ciphertexts of 2 x %zu words", count, N);
-  if (count == 0) return RS_OK;
-  rs::RlweEncArgs a{};
-  a.rlwe = rlwe; a.pk = pk; a.mu = mu;
-  rs::kg_seed_words(rand_seed, a.seed);
-  a.first = first; a.count = (long)count; a.N = (int)N; a.sigma = stdev;
-  const hipError_t e = rs::launch_rlwe_pk_encrypt(a, (hipStream_t)stream);
-  for (uint32_t& w : a.seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the seed words does not outlive the call
-  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_rlwe_pk_encrypt failed: %s", hipGetErrorString(e));
-  return RS_OK;
-}
-
-int rs_rlwe_extract_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t count, void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!u || !rlwe) return fail(RS_ERR_INVALID, "null pointer");
-  const size_t row_bytes = ((size_t)c->p.N + 1) * sizeof(int32_t);
-  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)INT32_MAX)
-    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
-  if (count == 0) return RS_OK;
-  const rs::RlweExtractArgs x{u, rlwe, (long)count, c->p.N};
-  RS_HIP(rs::launch_rlwe_extract(x, (hipStream_t)stream));
-  return RS_OK;
-}
-
-// packed results (include/redsec_hip.h; kernels of rs_pack.hip, integer arithmetic only): needs no key, the ring and n are the context's
-int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const int32_t* pack_key, int32_t basebit, int32_t t,
-                void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!rlwe || !ct || !pack_key) return fail(RS_ERR_INVALID, "null pointer");
-  if (basebit < 1 || basebit > 8) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
-  if (t < 1) return fail(RS_ERR_INVALID, "t = %d is below 1", (int)t);
-  if ((int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
-  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
-  if (N < (size_t)rs::kPaMinN || N > (size_t)rs::kPaMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
-  const size_t row_bytes = (n + 1) * sizeof(int32_t), R = count / N + (count % N ? 1 : 0);
-  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N)
-    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
-  if (count == 0) return RS_OK;
-  const size_t per_r = 2 * (N / rs::kPaTile) * (size_t)rs::pa_slot_blocks((long)count, (int)N) * (size_t)rs::pa_chunks((int)n);
-  if (R > (size_t)INT32_MAX / per_r)                                        // workgroups of one launch (rs::pa_groups)
-    return fail(RS_ERR_INVALID, "count = %zu is too large for one launch", count);
-  const rs::PackArgs a{rlwe, ct, pack_key, (long)count, (int)n, (int)N, (int)basebit, (int)t};
-  RS_HIP(rs::launch_pack(a, (hipStream_t)stream));
-  return RS_OK;
-}
-
-// the packing key on the device (include/redsec_hip.h; kernels of rs_packkey.hip): the checks the three calls share. rows = n t.
-static int pack_key_shape(const rs_ctx* c, int32_t basebit, int32_t t, bool digits, size_t* rows) {
-  if (digits && (basebit < 1 || basebit > 8)) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
-  if (t < 1) return fail(RS_ERR_INVALID, "t = %d is below 1", (int)t);
-  if (digits && (int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
-  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
-  if (N < (size_t)rs::kPgMinN || N > (size_t)rs::kPgMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
-  // rows x tiles workgroups of the generator, rows N / 16 threads of the expansion and 2 rows N words of the key, all below 2^31 x 256
-  if (n < 1 || (size_t)t > (size_t)INT32_MAX / (N / 16) / n)
-    return fail(RS_ERR_INVALID, "n t = %zu x %d is too large for rows of %zu words", n, (int)t, N);
-  *rows = n * (size_t)t;
-  return RS_OK;
-}
-
-int rs_pack_keygen_dev(rs_ctx* c, int32_t* body, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* mask_seed,
-                       const uint8_t* noise_seed, int32_t basebit, int32_t t, double stdev) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!body || !lwe_key || !tlwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
-  if (memcmp(mask_seed, noise_seed, 32) == 0)
-    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
-  if (!(std::isfinite(stdev) && stdev >= 0.0)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
-  size_t rows = 0;
-  rc = pack_key_shape(c, basebit, t, true, &rows);
-  if (rc) return rc;
-  const rs_params& p = c->p;
-  std::vector<uint32_t> bits;
-  int bad = pack_key_bits(lwe_key, p.n, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
-  const size_t lwe_words = bits.size();
-  bad = pack_key_bits(tlwe_key, p.N, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
-  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
-    rs::PackKeygenArgs a{};
-    a.body = body; a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
-    rs::kg_seed_words(mask_seed, a.seed);
-    rs::kg_seed_words(noise_seed, a.noise_seed);
-    a.n = p.n; a.N = p.N; a.basebit = basebit; a.t = t; a.sigma = stdev;
-    const hipError_t e = rs::launch_pack_keygen(a, nullptr);
-    for (uint32_t& w : a.noise_seed) *const_cast<volatile uint32_t*>(&w) = 0u;   // the host copy of the private seed words does not outlive the call
-    if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pack_keygen failed: %s", hipGetErrorString(e));
-    RS_HIP(hipDeviceSynchronize());
-    return RS_OK;
-  });
-}
-
-int rs_pack_expand_dev(rs_ctx* c, int32_t* pack_key, const uint8_t* mask_seed, const int32_t* body, int32_t t, void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!pack_key || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
-  size_t rows = 0;
-  rc = pack_key_shape(c, 0, t, false, &rows);
-  if (rc) return rc;
-  rs::PackExpandArgs a{};
-  a.key = pack_key; a.body = body;
-  rs::kg_seed_words(mask_seed, a.seed);
-  a.rows = (long)rows; a.N = c->p.N;
-  RS_HIP(rs::launch_pack_expand(a, (hipStream_t)stream));
-  return RS_OK;
-}
-
-// ---- device decryption and the noise audit of evaluation keys (CLIENT side; kernels of rs_audit.hip, integer arithmetic only) ----
-
-int rs_phase_dev(rs_ctx* c, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!phase || !ct || !key) return fail(RS_ERR_INVALID, "null pointer");
-  if (dim != c->p.n && dim != c->p.k * c->p.N) return fail(RS_ERR_INVALID, "dim = %d is neither n = %d nor k N = %d", dim, c->p.n, c->p.k * c->p.N);
-  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
-  std::vector<uint32_t> bits;
-  const int bad = pack_key_bits(key, dim, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "key[%d] = %d is not 0 or 1", bad, key[bad]); }
-  if (B == 0) { std::fill(bits.begin(), bits.end(), 0u); return RS_OK; }
-  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
-    RS_HIP(hipDeviceSynchronize());   // everything queued on the device, side streams included, has written ct
-    rs::PhaseArgs a{phase, ct, d_bits, (long)B, dim};
-    RS_HIP(rs::launch_lwe_phase(a, c->num_cus, nullptr));
-    RS_HIP(hipDeviceSynchronize());
-    return RS_OK;
-  });
-}
-
-// rs_audit_keys_dev (mask_seed null: bk / ksk are the full key) and rs_audit_compressed_keys_dev (the bodies)
-static int audit_impl(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed, bool compressed,
-                      const int32_t* bk, const int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit,
-                      uint32_t ksk_limit) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!report || !lwe_key || !tlwe_key || (compressed && !mask_seed)) return fail(RS_ERR_INVALID, "null pointer");
-  if (!bk && !ksk) return fail(RS_ERR_INVALID, "both halves of the key are null: nothing to audit");
-  const rs_params& p = c->p;
-  std::vector<uint32_t> bits;
-  int bad = pack_key_bits(lwe_key, p.n, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
-  const size_t lwe_words = bits.size();
-  bad = pack_key_bits(tlwe_key, p.N, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
-  rs::AuditReportDev dev{};
-  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
-    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
-    rs::AuditArgs a{};
-    a.bk = bk; a.ksk = ksk; a.bk_noise = bk_noise; a.ksk_noise = ksk_noise;
-    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
-    if (compressed) rs::kg_seed_words(mask_seed, a.seed);
-    a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
-    a.bk_limit = bk_limit; a.ksk_limit = ksk_limit;
-    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
-    if (bk) RS_HIP(rs::launch_audit_bk(a, compressed, c->num_cus, nullptr));
-    if (ksk) RS_HIP(rs::launch_audit_ksk(a, compressed, c->num_cus, nullptr));
-    RS_HIP(hipDeviceSynchronize());
-    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
-    return RS_OK;
-  });
-  if (rc != RS_OK) return rc;
-  report->bk_max_abs = dev.bk_max_abs; report->ksk_max_abs = dev.ksk_max_abs;
-  report->bk_over = dev.bk_over; report->ksk_over = dev.ksk_over; report->ksk_zero_bad = dev.ksk_zero_bad;
-  report->bk_words = bk ? (uint64_t)p.n * (uint64_t)(2 * p.bk_l) * (uint64_t)p.N : 0u;
-  report->ksk_words = ksk ? (uint64_t)p.N * (uint64_t)p.ks_t * (((uint64_t)1 << p.ks_basebit) - 1u) : 0u;
-  return RS_OK;
-}
-
-int rs_audit_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const int32_t* bk, const int32_t* ksk,
-                      const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit, uint32_t ksk_limit) {
-  return audit_impl(c, report, bk_noise, ksk_noise, nullptr, false, bk, ksk, lwe_key, tlwe_key, bk_limit, ksk_limit);
-}
-int rs_audit_compressed_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed,
-                                 const int32_t* bk_body, const int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
-                                 uint32_t bk_limit, uint32_t ksk_limit) {
-  return audit_impl(c, report, bk_noise, ksk_noise, mask_seed, true, bk_body, ksk_body, lwe_key, tlwe_key, bk_limit, ksk_limit);
-}
-
-// the same audit of a packing key (mask_seed null: key is the full key [n][t][2][N]; else the bodies, the masks regenerated)
-int rs_audit_pack_key_dev(rs_ctx* c, rs_pack_key_audit* report, int32_t* noise, const int32_t* key, const uint8_t* mask_seed,
-                          const int32_t* lwe_key, const int32_t* tlwe_key, int32_t basebit, int32_t t, uint32_t limit) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!report || !key || !lwe_key || !tlwe_key) return fail(RS_ERR_INVALID, "null pointer");
-  size_t rows = 0;
-  rc = pack_key_shape(c, basebit, t, true, &rows);
-  if (rc) return rc;
-  const rs_params& p = c->p;
-  std::vector<uint32_t> bits;
-  int bad = pack_key_bits(lwe_key, p.n, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]); }
-  const size_t lwe_words = bits.size();
-  bad = pack_key_bits(tlwe_key, p.N, bits);
-  if (bad >= 0) { std::fill(bits.begin(), bits.end(), 0u); return fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]); }
-  rs::AuditReportDev dev{};
-  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
-    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
-    rs::AuditPackArgs a{};
-    a.key = key; a.noise = noise;
-    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
-    if (mask_seed) rs::kg_seed_words(mask_seed, a.seed);
-    a.n = p.n; a.N = p.N; a.t = t; a.basebit = basebit; a.limit = limit;
-    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
-    RS_HIP(rs::launch_audit_pack(a, mask_seed != nullptr, c->num_cus, nullptr));
-    RS_HIP(hipDeviceSynchronize());
-    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
-    return RS_OK;
-  });
-  if (rc != RS_OK) return rc;
-  report->max_abs = dev.bk_max_abs;
-  report->over = dev.bk_over;
-  report->words = (uint64_t)rows * (uint64_t)p.N;
-  return RS_OK;
-}
-
 int rs_reserve(rs_ctx* c, size_t max_batch) { return rs_reserve_stream(c, max_batch, nullptr); }
 
 int rs_reserve_stream(rs_ctx* c, size_t max_batch, void* stream) {
@@ -1177,12 +516,14 @@ int rs_gate_dev(rs_ctx* c, rs_gate_op op, int32_t* out, const int32_t* a, const 
 namespace {
 
 // without a context nothing can run; say why when the reason is that no device exists (rs_create cannot have succeeded)
+int refuse_without_device(const rs_ctx* c) {
+  int count = 0;
+  if (!c && (hipGetDeviceCount(&count) != hipSuccess || count <= 0)) { (void)hipGetLastError(); return fail(RS_ERR_NO_DEVICE, "no HIP device visible"); }
+  return RS_OK;
+}
 int rows_ready(rs_ctx* c) {
-  if (!c) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { (void)hipGetLastError(); return fail(RS_ERR_NO_DEVICE, "no HIP device visible"); }
-  }
-  return ready(c);
+  const int rc = refuse_without_device(c);
+  return rc ? rc : ready(c);
 }
 
 // The one path of the indexed gate batches: the combinations are materialised in the lane's staging buffer (gate_rows_kernel, in
@@ -1295,11 +636,8 @@ namespace {
 
 // the context of a circuit call that needs no key: as rows_ready, without the key check
 int circuit_ctx(rs_ctx* c) {
-  if (!c) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { (void)hipGetLastError(); return fail(RS_ERR_NO_DEVICE, "no HIP device visible"); }
-  }
-  return use_device(c);
+  const int rc = refuse_without_device(c);
+  return rc ? rc : use_device(c);
 }
 
 bool circuit_alive(rs_ctx* c, const rs_circuit* q) {

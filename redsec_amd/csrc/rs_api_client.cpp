@@ -1,0 +1,400 @@
+// rs_api_client.cpp -- key material and client-side calls of the C ABI (include/redsec_hip.h) that need no lane, no launch plan
+// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack and the packing key, device
+// decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
+// (rs::with_secret_copy; rs_keygen_dev of rs_api_keys.cpp goes through it too) and of the refusals these calls share.
+#include "rs_api_internal.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+
+#include "rs_keygen.h"
+#include "rs_pack.h"
+#include "rs_packkey.h"
+#include "rs_rlwe.h"
+
+using rs::fail;
+using rs::use_device;
+
+namespace {
+
+// a 0/1 key appended to `out`, `per_word` to a word from a fresh word on; the index of the first word outside {0, 1}, or -1
+int pack_key_bits(const int32_t* key, int count, int per_word, std::vector<uint32_t>& out) {
+  const size_t base = out.size();
+  out.resize(base + ((size_t)count + per_word - 1) / per_word, 0u);
+  for (int i = 0; i < count; ++i) {
+    if (key[i] != 0 && key[i] != 1) return i;
+    out[base + (size_t)(i / per_word)] |= (uint32_t)key[i] << (i % per_word);
+  }
+  return -1;
+}
+
+// `rc` behind the host copy of a secret that is not needed any more
+int wiped(std::vector<uint32_t>& words, int rc) {
+  std::fill(words.begin(), words.end(), 0u);
+  return rc;
+}
+
+// the host copy of seed words does not outlive the call
+void wipe_seed(uint32_t (&seed)[8]) {
+  for (uint32_t& w : seed) *const_cast<volatile uint32_t*>(&w) = 0u;
+}
+
+int refuse_deviation(double stdev) {
+  if (!rs::deviation_ok(stdev)) return fail(RS_ERR_INVALID, "noise deviation must be finite and non-negative (%g)", stdev);
+  return RS_OK;
+}
+
+// `count` consecutive indices from `first` on stay below 2^64 (`what`: B ciphertexts, R ring ciphertexts)
+int refuse_overflow(uint64_t first, size_t count, char what) {
+  if (count > 0 && count - 1 > UINT64_MAX - first)
+    return fail(RS_ERR_INVALID, "first + %c = %llu + %zu passes 2^64", what, (unsigned long long)first, count);
+  return RS_OK;
+}
+
+// the digits of a packing key: t of them (`digits`: of basebit bits each, inside one 32-bit word)
+int refuse_digits(int32_t basebit, int32_t t, bool digits) {
+  if (digits && (basebit < 1 || basebit > 8)) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
+  if (t < 1) return fail(RS_ERR_INVALID, "t = %d is below 1", (int)t);
+  if (digits && (int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
+  return RS_OK;
+}
+
+}  // namespace
+
+namespace rs {
+
+int refuse_equal_seeds(const uint8_t* mask_seed, const uint8_t* noise_seed) {
+  if (memcmp(mask_seed, noise_seed, 32) == 0)
+    return fail(RS_ERR_INVALID, "mask seed and noise seed are equal: the public mask seed would reveal the noise");
+  return RS_OK;
+}
+
+int pack_key_pair(const rs_params& p, const int32_t* lwe_key, const int32_t* tlwe_key, int per_word, std::vector<uint32_t>& out,
+                  size_t* lwe_words) {
+  int bad = pack_key_bits(lwe_key, p.n, per_word, out);
+  if (bad >= 0) return wiped(out, fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]));
+  *lwe_words = out.size();
+  bad = pack_key_bits(tlwe_key, p.N, per_word, out);
+  if (bad >= 0) return wiped(out, fail(RS_ERR_INVALID, "tlwe_key[%d] = %d is not 0 or 1", bad, tlwe_key[bad]));
+  return RS_OK;
+}
+
+int with_secret_copy(std::vector<uint32_t>& words, size_t extra, const std::function<int(const uint32_t*, char*)>& run) {
+  const size_t key_bytes = (words.size() * sizeof(uint32_t) + 15) & ~(size_t)15, bytes = key_bytes + extra;
+  char* d = nullptr;
+  auto body = [&]() -> int {
+    RS_HIP(hipMalloc(&d, bytes));
+    RS_HIP(hipMemset(d, 0, bytes));
+    RS_HIP(hipMemcpy(d, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return run(reinterpret_cast<const uint32_t*>(d), d + key_bytes);
+  };
+  const int rc = body();
+  std::fill(words.begin(), words.end(), 0u);
+  if (!d) return rc;
+  (void)hipDeviceSynchronize();
+  const hipError_t ez = hipMemset(d, 0, bytes);
+  const hipError_t es = hipDeviceSynchronize();
+  (void)hipFree(d);
+  if (rc != RS_OK) return rc;
+  if (ez != hipSuccess || es != hipSuccess) return fail(RS_ERR_HIP, "clearing the device copy of the secret key failed");
+  return RS_OK;
+}
+
+}  // namespace rs
+
+using rs::pack_key_pair;
+using rs::with_secret_copy;
+
+// seeded LWE ciphertexts (include/redsec_hip.h): the checks both directions share
+static int seeded_args(const rs_ctx* c, rs::SeededArgs* a, const uint8_t* mask_seed, uint64_t first, size_t B) {
+  const int rc = refuse_overflow(first, B, 'B');
+  if (rc) return rc;
+  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
+  rs::kg_seed_words(mask_seed, a->seed);
+  a->first = first; a->B = (long)B;
+  a->n = c->p.n; a->tile = rs::kg_ct_tile(c->p.n);
+  return RS_OK;
+}
+
+extern "C" {
+
+int rs_encrypt_seeded_dev(rs_ctx* c, int32_t* body, int32_t* ct, const int32_t* mu, size_t B, const int32_t* lwe_key,
+                          const uint8_t* mask_seed, const uint8_t* noise_seed, uint64_t first, double stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!body || !mu || !lwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if ((rc = rs::refuse_equal_seeds(mask_seed, noise_seed)) != RS_OK) return rc;
+  if ((rc = refuse_deviation(stdev)) != RS_OK) return rc;
+  // the key, one bit per word, zero past n
+  std::vector<uint32_t> bits;
+  const int bad = pack_key_bits(lwe_key, c->p.n, 32, bits);
+  if (bad >= 0) return wiped(bits, fail(RS_ERR_INVALID, "lwe_key[%d] = %d is not 0 or 1", bad, lwe_key[bad]));
+  rs::SeededArgs a{};
+  rc = seeded_args(c, &a, mask_seed, first, B);
+  if (rc || B == 0) return wiped(bits, rc);
+  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
+    a.ct = ct; a.body = body; a.mu = mu; a.key_bits = d_bits;
+    rs::kg_seed_words(noise_seed, a.noise_seed);
+    a.sigma = stdev;
+    RS_HIP(rs::launch_encrypt_seeded(a, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  });
+}
+
+int rs_expand_ciphertexts_dev(rs_ctx* c, int32_t* ct, const uint8_t* mask_seed, uint64_t first, const int32_t* body, size_t B,
+                              void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!ct || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
+  rs::SeededArgs a{};
+  rc = seeded_args(c, &a, mask_seed, first, B);
+  if (rc) return rc;
+  if (B == 0) return RS_OK;
+  a.ct = ct; a.body = const_cast<int32_t*>(body);
+  RS_HIP(rs::launch_expand_ciphertexts(a, c->num_cus, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// public-key encryption (include/redsec_hip.h; kernel of rs_pubkey.hip): needs no key, the rand seed travels as a kernel argument
+int rs_pk_encrypt_dev(rs_ctx* c, int32_t* ct, const int32_t* pk, size_t m, const int32_t* mu, const int32_t* base, size_t B,
+                      const uint8_t* rand_seed, uint64_t first, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!ct || !pk || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if (m < 1 || m > (size_t)INT32_MAX) return fail(RS_ERR_INVALID, "m = %zu is outside 1 .. 2^31 - 1", m);
+  if ((rc = refuse_overflow(first, B, 'B')) != RS_OK) return rc;
+  const size_t row_bytes = ((size_t)c->p.n + 1) * sizeof(int32_t);
+  if (B > (size_t)LONG_MAX / row_bytes || m > (size_t)LONG_MAX / row_bytes || (B + rs::kPkTile - 1) / rs::kPkTile > (size_t)INT32_MAX)
+    return fail(RS_ERR_INVALID, "B = %zu or m = %zu is too large for rows of %zu bytes", B, m, row_bytes);
+  if (B == 0) return RS_OK;
+  rs::PkArgs a{};
+  a.ct = ct; a.pk = pk; a.mu = mu; a.base = base;
+  rs::kg_seed_words(rand_seed, a.seed);
+  a.first = first; a.B = (long)B; a.m = (long)m; a.n = c->p.n;
+  const hipError_t e = rs::launch_pk_encrypt(a, (hipStream_t)stream);
+  wipe_seed(a.seed);
+  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pk_encrypt failed: %s", hipGetErrorString(e));
+  return RS_OK;
+}
+
+// compact RLWE public keys (include/redsec_hip.h; kernels of rs_rlwe.hip): neither call needs a key, the ring is the context's
+int rs_rlwe_pk_encrypt_dev(rs_ctx* c, int32_t* rlwe, const int32_t* pk, const int32_t* mu, size_t count, const uint8_t* rand_seed,
+                           uint64_t first, double stdev, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!rlwe || !pk || !mu || !rand_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if ((rc = refuse_deviation(stdev)) != RS_OK) return rc;
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kRlMinN || N > (size_t)rs::kRlMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  const size_t R = count / N + (count % N ? 1 : 0), tiles = N / rs::kRlTile;
+  if ((rc = refuse_overflow(first, R, 'R')) != RS_OK) return rc;
+  if (count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N || R > (size_t)INT32_MAX / (2 * tiles))
+    return fail(RS_ERR_INVALID, "count = %zu is too large for ciphertexts of 2 x %zu words", count, N);
+  if (count == 0) return RS_OK;
+  rs::RlweEncArgs a{};
+  a.rlwe = rlwe; a.pk = pk; a.mu = mu;
+  rs::kg_seed_words(rand_seed, a.seed);
+  a.first = first; a.count = (long)count; a.N = (int)N; a.sigma = stdev;
+  const hipError_t e = rs::launch_rlwe_pk_encrypt(a, (hipStream_t)stream);
+  wipe_seed(a.seed);
+  if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_rlwe_pk_encrypt failed: %s", hipGetErrorString(e));
+  return RS_OK;
+}
+
+int rs_rlwe_extract_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t count, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!u || !rlwe) return fail(RS_ERR_INVALID, "null pointer");
+  const size_t row_bytes = ((size_t)c->p.N + 1) * sizeof(int32_t);
+  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)INT32_MAX)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
+  if (count == 0) return RS_OK;
+  const rs::RlweExtractArgs x{u, rlwe, (long)count, c->p.N};
+  RS_HIP(rs::launch_rlwe_extract(x, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// packed results (include/redsec_hip.h; kernels of rs_pack.hip, integer arithmetic only): needs no key, the ring and n are the context's
+int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const int32_t* pack_key, int32_t basebit, int32_t t,
+                void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!rlwe || !ct || !pack_key) return fail(RS_ERR_INVALID, "null pointer");
+  if ((rc = refuse_digits(basebit, t, true)) != RS_OK) return rc;
+  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
+  if (N < (size_t)rs::kPaMinN || N > (size_t)rs::kPaMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  const size_t row_bytes = (n + 1) * sizeof(int32_t), R = count / N + (count % N ? 1 : 0);
+  if (count > (size_t)LONG_MAX / row_bytes || count > (size_t)LONG_MAX / (2 * sizeof(int32_t)) - N)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for rows of %zu bytes", count, row_bytes);
+  if (count == 0) return RS_OK;
+  const size_t per_r = 2 * (N / rs::kPaTile) * (size_t)rs::pa_slot_blocks((long)count, (int)N) * (size_t)rs::pa_chunks((int)n);
+  if (R > (size_t)INT32_MAX / per_r)                                        // workgroups of one launch (rs::pa_groups)
+    return fail(RS_ERR_INVALID, "count = %zu is too large for one launch", count);
+  const rs::PackArgs a{rlwe, ct, pack_key, (long)count, (int)n, (int)N, (int)basebit, (int)t};
+  RS_HIP(rs::launch_pack(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// the packing key on the device (include/redsec_hip.h; kernels of rs_packkey.hip): the checks the three calls share. rows = n t.
+static int pack_key_shape(const rs_ctx* c, int32_t basebit, int32_t t, bool digits, size_t* rows) {
+  const int rc = refuse_digits(basebit, t, digits);
+  if (rc) return rc;
+  const size_t N = (size_t)c->p.N, n = (size_t)c->p.n;
+  if (N < (size_t)rs::kPgMinN || N > (size_t)rs::kPgMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  // rows x tiles workgroups of the generator, rows N / 16 threads of the expansion and 2 rows N words of the key, all below 2^31 x 256
+  if (n < 1 || (size_t)t > (size_t)INT32_MAX / (N / 16) / n)
+    return fail(RS_ERR_INVALID, "n t = %zu x %d is too large for rows of %zu words", n, (int)t, N);
+  *rows = n * (size_t)t;
+  return RS_OK;
+}
+
+int rs_pack_keygen_dev(rs_ctx* c, int32_t* body, const int32_t* lwe_key, const int32_t* tlwe_key, const uint8_t* mask_seed,
+                       const uint8_t* noise_seed, int32_t basebit, int32_t t, double stdev) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!body || !lwe_key || !tlwe_key || !mask_seed || !noise_seed) return fail(RS_ERR_INVALID, "null pointer");
+  if ((rc = rs::refuse_equal_seeds(mask_seed, noise_seed)) != RS_OK) return rc;
+  if ((rc = refuse_deviation(stdev)) != RS_OK) return rc;
+  size_t rows = 0;
+  rc = pack_key_shape(c, basebit, t, true, &rows);
+  if (rc) return rc;
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  size_t lwe_words = 0;
+  rc = pack_key_pair(p, lwe_key, tlwe_key, 32, bits, &lwe_words);
+  if (rc) return rc;
+  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
+    rs::PackKeygenArgs a{};
+    a.body = body; a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    rs::kg_seed_words(mask_seed, a.seed);
+    rs::kg_seed_words(noise_seed, a.noise_seed);
+    a.n = p.n; a.N = p.N; a.basebit = basebit; a.t = t; a.sigma = stdev;
+    const hipError_t e = rs::launch_pack_keygen(a, nullptr);
+    wipe_seed(a.noise_seed);
+    if (e != hipSuccess) return fail(RS_ERR_HIP, "launch_pack_keygen failed: %s", hipGetErrorString(e));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  });
+}
+
+int rs_pack_expand_dev(rs_ctx* c, int32_t* pack_key, const uint8_t* mask_seed, const int32_t* body, int32_t t, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!pack_key || !mask_seed || !body) return fail(RS_ERR_INVALID, "null pointer");
+  size_t rows = 0;
+  rc = pack_key_shape(c, 0, t, false, &rows);
+  if (rc) return rc;
+  rs::PackExpandArgs a{};
+  a.key = pack_key; a.body = body;
+  rs::kg_seed_words(mask_seed, a.seed);
+  a.rows = (long)rows; a.N = c->p.N;
+  RS_HIP(rs::launch_pack_expand(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// ---- device decryption and the noise audit of evaluation keys (CLIENT side; kernels of rs_audit.hip, integer arithmetic only) ----
+
+int rs_phase_dev(rs_ctx* c, int32_t* phase, const int32_t* ct, size_t B, const int32_t* key, int32_t dim) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!phase || !ct || !key) return fail(RS_ERR_INVALID, "null pointer");
+  if (dim != c->p.n && dim != c->p.k * c->p.N) return fail(RS_ERR_INVALID, "dim = %d is neither n = %d nor k N = %d", dim, c->p.n, c->p.k * c->p.N);
+  if (B > (size_t)LONG_MAX) return fail(RS_ERR_INVALID, "B = %zu is too large", B);
+  std::vector<uint32_t> bits;
+  const int bad = pack_key_bits(key, dim, 32, bits);
+  if (bad >= 0) return wiped(bits, fail(RS_ERR_INVALID, "key[%d] = %d is not 0 or 1", bad, key[bad]));
+  if (B == 0) return wiped(bits, RS_OK);
+  return with_secret_copy(bits, 0, [&](const uint32_t* d_bits, char*) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device, side streams included, has written ct
+    rs::PhaseArgs a{phase, ct, d_bits, (long)B, dim};
+    RS_HIP(rs::launch_lwe_phase(a, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    return RS_OK;
+  });
+}
+
+// rs_audit_keys_dev (mask_seed null: bk / ksk are the full key) and rs_audit_compressed_keys_dev (the bodies)
+static int audit_impl(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed, bool compressed,
+                      const int32_t* bk, const int32_t* ksk, const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit,
+                      uint32_t ksk_limit) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!report || !lwe_key || !tlwe_key || (compressed && !mask_seed)) return fail(RS_ERR_INVALID, "null pointer");
+  if (!bk && !ksk) return fail(RS_ERR_INVALID, "both halves of the key are null: nothing to audit");
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  size_t lwe_words = 0;
+  rc = pack_key_pair(p, lwe_key, tlwe_key, 32, bits, &lwe_words);
+  if (rc) return rc;
+  rs::AuditReportDev dev{};
+  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
+    rs::AuditArgs a{};
+    a.bk = bk; a.ksk = ksk; a.bk_noise = bk_noise; a.ksk_noise = ksk_noise;
+    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    if (compressed) rs::kg_seed_words(mask_seed, a.seed);
+    a.n = p.n; a.N = p.N; a.l = p.bk_l; a.bgbit = p.bk_Bgbit; a.t = p.ks_t; a.basebit = p.ks_basebit;
+    a.bk_limit = bk_limit; a.ksk_limit = ksk_limit;
+    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
+    if (bk) RS_HIP(rs::launch_audit_bk(a, compressed, c->num_cus, nullptr));
+    if (ksk) RS_HIP(rs::launch_audit_ksk(a, compressed, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
+    return RS_OK;
+  });
+  if (rc != RS_OK) return rc;
+  report->bk_max_abs = dev.bk_max_abs; report->ksk_max_abs = dev.ksk_max_abs;
+  report->bk_over = dev.bk_over; report->ksk_over = dev.ksk_over; report->ksk_zero_bad = dev.ksk_zero_bad;
+  report->bk_words = bk ? (uint64_t)p.n * (uint64_t)(2 * p.bk_l) * (uint64_t)p.N : 0u;
+  report->ksk_words = ksk ? (uint64_t)p.N * (uint64_t)p.ks_t * (((uint64_t)1 << p.ks_basebit) - 1u) : 0u;
+  return RS_OK;
+}
+
+int rs_audit_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const int32_t* bk, const int32_t* ksk,
+                      const int32_t* lwe_key, const int32_t* tlwe_key, uint32_t bk_limit, uint32_t ksk_limit) {
+  return audit_impl(c, report, bk_noise, ksk_noise, nullptr, false, bk, ksk, lwe_key, tlwe_key, bk_limit, ksk_limit);
+}
+int rs_audit_compressed_keys_dev(rs_ctx* c, rs_key_audit* report, int32_t* bk_noise, int32_t* ksk_noise, const uint8_t* mask_seed,
+                                 const int32_t* bk_body, const int32_t* ksk_body, const int32_t* lwe_key, const int32_t* tlwe_key,
+                                 uint32_t bk_limit, uint32_t ksk_limit) {
+  return audit_impl(c, report, bk_noise, ksk_noise, mask_seed, true, bk_body, ksk_body, lwe_key, tlwe_key, bk_limit, ksk_limit);
+}
+
+// the same audit of a packing key (mask_seed null: key is the full key [n][t][2][N]; else the bodies, the masks regenerated)
+int rs_audit_pack_key_dev(rs_ctx* c, rs_pack_key_audit* report, int32_t* noise, const int32_t* key, const uint8_t* mask_seed,
+                          const int32_t* lwe_key, const int32_t* tlwe_key, int32_t basebit, int32_t t, uint32_t limit) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!report || !key || !lwe_key || !tlwe_key) return fail(RS_ERR_INVALID, "null pointer");
+  size_t rows = 0;
+  rc = pack_key_shape(c, basebit, t, true, &rows);
+  if (rc) return rc;
+  const rs_params& p = c->p;
+  std::vector<uint32_t> bits;
+  size_t lwe_words = 0;
+  rc = pack_key_pair(p, lwe_key, tlwe_key, 32, bits, &lwe_words);
+  if (rc) return rc;
+  rs::AuditReportDev dev{};
+  rc = with_secret_copy(bits, sizeof(rs::AuditReportDev), [&](const uint32_t* d_bits, char* d_report) -> int {
+    RS_HIP(hipDeviceSynchronize());   // everything queued on the device has written the key
+    rs::AuditPackArgs a{};
+    a.key = key; a.noise = noise;
+    a.lwe_bits = d_bits; a.tlwe_bits = d_bits + lwe_words;
+    if (mask_seed) rs::kg_seed_words(mask_seed, a.seed);
+    a.n = p.n; a.N = p.N; a.t = t; a.basebit = basebit; a.limit = limit;
+    a.report = reinterpret_cast<rs::AuditReportDev*>(d_report);
+    RS_HIP(rs::launch_audit_pack(a, mask_seed != nullptr, c->num_cus, nullptr));
+    RS_HIP(hipDeviceSynchronize());
+    RS_HIP(hipMemcpy(&dev, d_report, sizeof dev, hipMemcpyDeviceToHost));
+    return RS_OK;
+  });
+  if (rc != RS_OK) return rc;
+  report->max_abs = dev.bk_max_abs;
+  report->over = dev.bk_over;
+  report->words = (uint64_t)rows * (uint64_t)p.N;
+  return RS_OK;
+}
+
+}  // extern "C"

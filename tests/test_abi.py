@@ -159,6 +159,8 @@ def test_kernel_sources_carry_no_experiment_switches():
     ("rs_bootstrap_listed.hip", ["-DRS_DIAG=256"]),                # stamps of the listed coop8 kernel: the array lives in its unit
     ("rs_general.hip", ["-DRS_DIAG=144"]),                         # no-key and half-key probes of the general rings
     ("rs_api.cpp", ["-DRS_DIAG=48"]),                              # the probes' switch that turns the exactness gates off
+    ("rs_api_keys.cpp", ["-DRS_DIAG=48"]),                         # ... and the other two units of the C ABI: neither reads rs::diag
+    ("rs_api_client.cpp", ["-DRS_DIAG=48"]),                       #     today, and the diagnostic build still has to hold all three
 ])
 def test_diagnostic_builds_compile(src, flags):
     """Everything diagnostic sits behind -DRS_DIAG=<bits> (csrc/rs_diag.h) and no product build defines it: nothing but this test would
