@@ -248,6 +248,34 @@ int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t cou
 int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
                 const int32_t* pack_key, int32_t basebit, int32_t t, void* stream);
 
+/* Re-keying: a public LWE-to-LWE keyswitch under a caller-supplied key, from any source dimension to
+ * any destination dimension. Results encrypted under a key s leave the server decryptable under another key s': delegation to a
+ * third party, key rotation, or crossing from one parameter set to another (n = 350 to n = 630 and back). rs_keyswitch_dev reads
+ * only the context's loaded key in TFHE's table layout; this call reads the key it is given, in the digit-times-row form of
+ * rs_pack_dev. Word-wise mod 2^32, the digit convention of lweKeySwitch / rs_keyswitch_dev / rs_pack_dev:
+ *   K[i][j]  = row i t + j of rekey_key = (a_ij, b_ij),  b_ij = <a_ij, s'> + e_ij + s_i 2^(32-(j+1) basebit)     i < n_src, j < t
+ *   abar     = a + off,  off = 2^(31 - t basebit)  (0 when t basebit = 32)
+ *   d_ij(r)  = (abar_i of sample r >> (32-(j+1) basebit)) & (2^basebit - 1)
+ *   out[r]   = (0, b_r) - sum_{i,j} d_ij(r) K[i][j]
+ * Under s', out[r] has the phase of ct[r] under s plus the re-keying error, of variance
+ *   sigma^2 = n_src t (2^basebit - 1)(2^(basebit+1) - 1)/6 sigma_row^2  +  (n_src/2) 2^(-2 t basebit)/12
+ * (sigma_row the deviation of one key row's phase; the first term is the key noise under the digits, the second the digits'
+ * rounding). The key needs no call of its own: it is n_src t seeded encryptions of the words s_i 2^(32-(j+1) basebit) under the
+ * recipient's LWE key (rs_encrypt_seeded_dev, expanded by rs_expand_ciphertexts_dev on a context with n = n_dst), or, without the
+ * recipient's secret, ceil(n_src t / N) ciphertexts of those words under the recipient's compact RLWE public key
+ * (rs_rlwe_pk_encrypt_dev) turned into rows by rs_rlwe_extract_dev: then n_dst = N and the destination is the recipient's ring
+ * key read as an LWE key, under which rs_phase_dev(dim = N) decrypts. The rows of one such ciphertext share its selector and
+ * noise polynomials, so their noise has a common part that the unsigned digits would add up; redsec_amd encrypts every odd row
+ * negated and negates it back after the extraction (keygen.py rekey_alternate), and the formula above then holds for this form.
+ * ct DEVICE int32[B][n_src+1]; rekey_key DEVICE int32[n_src][t][n_dst+1]; out DEVICE int32[B][n_dst+1], overlaps neither input.
+ * Both dimensions are arguments, not the context's: a server context of any set re-keys to any recipient. Integer arithmetic
+ * only, exact: the words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on `stream`; no
+ * allocation. B = 0 is a no-op that returns RS_OK. A second call into the same buffer gives the same words.
+ * RS_ERR_INVALID: a null out, ct or rekey_key; n_src or n_dst outside 1 .. 65536; basebit outside 1 .. 8; t < 1; t basebit > 32; a
+ * B whose row arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_pack_dev does. */
+int rs_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* ct, size_t B, int32_t n_src,
+                 const int32_t* rekey_key, int32_t n_dst, int32_t basebit, int32_t t, void* stream);
+
 /* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
  * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three
  * need no loaded key and work on every context, N = 1024 .. 8192: 32-bit integer adds, no product, no transform, no mode dependence.

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "rs_gate3_dev", "rs_gate_rows_dev",
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
     "rs_bootstrap_sparse_dev",
+    "rs_rekey_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -132,6 +133,7 @@ def load_library(path=None):
     L.rs_rlwe_pk_encrypt_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_char_p, C.c_uint64, C.c_double, vp]
     L.rs_rlwe_extract_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.rs_pack_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
+    L.rs_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
     L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
     L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
@@ -500,6 +502,49 @@ class Backend:
             raise ValueError("the packing key is of %s with n = %d, the context of %s with n = %d"
                              % (key.name, key.n, keygen.set_name(self.p), self.p.n))
         return self.expand_packing_key(key.mask_seed, torch.from_numpy(key.body).to("cuda:%d" % self.device), key.t)
+
+    # ---- re-keying ----
+    def rekey(self, ct, key, basebit=None, t=None, out=None):
+        """LWE samples ct (int32 CUDA tensor [B][n_src+1]) keyswitched to a recipient's key under a caller-supplied key (rs_rekey_dev,
+        on torch's current stream) -> int32 CUDA tensor [B][n_dst+1]. key: a client.RekeyKey (uploaded and expanded on this context's
+        device, which must be of the destination's n, or ring for the RLWE form: keep the tensor of upload_rekey_key for repeated
+        calls) or an int32 CUDA tensor [n_src][t][n_dst+1] with explicit basebit and t. Both dimensions come from the key, not from the
+        context: a tensor key works on a context of any set. Needs no loaded key."""
+        from . import keygen
+        if hasattr(key, "form"):
+            basebit, t, key = key.basebit, key.t, self.upload_rekey_key(key)
+        if basebit is None or t is None:
+            raise ValueError("a re-keying key given as a tensor needs explicit basebit and t")
+        basebit, t = keygen._check_digits(basebit, t)
+        if key.dim() != 3 or key.shape[1] != t or key.shape[2] < 2:
+            raise ValueError("a re-keying key tensor must hold [n_src][t][n_dst+1] words with t = %d, not %s" % (t, tuple(key.shape)))
+        n_src, n_dst = key.shape[0], key.shape[2] - 1
+        assert ct.numel() % (n_src + 1) == 0, "ct must hold [B][n_src+1] words"
+        B = ct.numel() // (n_src + 1)
+        out = self.empty(B, n_dst + 1) if out is None else out
+        assert out.numel() == B * (n_dst + 1), "out must hold [B][n_dst+1] words"
+        _check(self.L, self.L.rs_rekey_dev(self.h, self._ck_dev(out), self._ck_dev(ct), B, n_src, self._ck_dev(key), n_dst, basebit, t,
+                                           self._stream()))
+        return out
+
+    def upload_rekey_key(self, key):
+        """The expanded client.RekeyKey on this context's device -> int32 CUDA tensor [n_src][t][n_dst+1] (pass it to rekey with
+        key.basebit and key.t). Form "seeded": the bodies are uploaded and the masks regenerated beside them
+        (rs_expand_ciphertexts_dev), on a context whose n is the key's n_dst; form "rlwe": the ciphertexts are uploaded, their
+        rows extracted (rs_rlwe_extract_dev) and the odd ones negated back, on a context whose ring is the key's n_dst. ValueError names the mismatch otherwise."""
+        import torch
+        dev = "cuda:%d" % self.device
+        if key.form == "seeded":
+            if self.p.n != key.n_dst:
+                raise ValueError("the re-keying key's destination has n = %d (%s), the context n = %d" % (key.n_dst, key.dst_name, self.p.n))
+            rows = self.expand_ciphertexts(key.mask_seed, torch.from_numpy(key.body).to(dev), 0)
+        else:
+            if self.p.N != key.n_dst:
+                raise ValueError("the re-keying key's destination is the ring key of N = %d (%s), the context's ring N = %d"
+                                 % (key.n_dst, key.dst_name, self.p.N))
+            rows = self.rlwe_extract(torch.from_numpy(key.rlwe).to(dev), key.rows)
+            rows[1::2].neg_()                                   # keygen.rekey_alternate: the odd rows travel negated
+        return rows.reshape(key.n_src, key.t, key.n_dst + 1)
 
     # ---- the packing key on the device (INTEGRATION.md section 19) ----
     def _secrets(self, lwe_key, tlwe_key):

@@ -263,21 +263,88 @@ class SecretKeySet:
         """decrypt_ints of the first `count` slots of packed ciphertexts."""
         return _round_phase(self.packed_phase(rlwe, count, backend), msize)
 
-    def phase(self, ct, backend=None):
+    def phase(self, ct, backend=None, ring=False):
         """Phases b - sum_k a_k s_k of ct [B][n+1]; with backend= (a redsec_amd.Backend) ct is an int32 CUDA tensor and the phase is
-        taken on the device (rs_phase_dev)."""
+        taken on the device (rs_phase_dev). ring=True: ct holds [B][N+1] samples under the ring key read as an LWE key of dimension
+        N (the output of bootstrap_wo_ks, of rlwe_extract, or of a re-keying under this secret's RLWE public key; rs_phase_dev with
+        dim = N)."""
+        key = self.tlwe_key if ring else self.lwe_key
         if backend is not None:
-            return backend.phase(ct.reshape(-1, self.W), self.lwe_key).cpu().numpy()
-        ct = np.asarray(ct, np.int32).reshape(-1, self.W)
-        dot = (ct[:, :self.n].view(np.uint32).astype(np.uint64) * self.lwe_key.astype(np.uint64)).sum(axis=-1)
-        return _wrap32(ct[:, self.n].view(np.uint32).astype(np.uint64) - dot)
+            return backend.phase(ct.reshape(-1, key.size + 1), key).cpu().numpy()
+        ct = np.asarray(ct, np.int32).reshape(-1, key.size + 1)
+        dot = (ct[:, :key.size].view(np.uint32).astype(np.uint64) * key.astype(np.uint64)).sum(axis=-1)
+        return _wrap32(ct[:, key.size].view(np.uint32).astype(np.uint64) - dot)
 
-    def decrypt_bits(self, ct, backend=None):
-        return (self.phase(ct, backend) > 0).astype(np.int64)
+    def decrypt_bits(self, ct, backend=None, ring=False):
+        return (self.phase(ct, backend, ring) > 0).astype(np.int64)
 
-    def decrypt_ints(self, ct, msize=MSG_SPACE, backend=None):
+    def decrypt_ints(self, ct, msize=MSG_SPACE, backend=None, ring=False):
         """client/decrypt_image.cpp:52-58: round the phase to multiples of 1/msize, signed."""
-        return _round_phase(self.phase(ct, backend), msize)
+        return _round_phase(self.phase(ct, backend, ring), msize)
+
+    # re-keying (include/redsec_hip.h rs_rekey_dev; INTEGRATION.md section 21): keys under which a server turns samples under THIS
+    # secret's LWE key into samples under a recipient's key
+    def _rekey_digits(self, dst_name, basebit, t):
+        from . import keygen
+        d = keygen.rekey_default(dst_name)
+        return keygen._check_digits(d[0] if basebit is None else basebit, d[1] if t is None else t)
+
+    def _rekey_mu(self, basebit, t, backend, run, alternate=False):
+        """run(mu) with mu = keygen.rekey_messages of this secret (alternate: the odd rows negated, keygen.rekey_alternate): a host
+        array, or with a backend an int32 CUDA tensor that is zeroed before this returns (it holds the source secret's bits)."""
+        from . import keygen
+        mu = keygen.rekey_messages(self.lwe_key, basebit, t)
+        if alternate:
+            mu = keygen.rekey_alternate(mu)
+        if backend is None:
+            return run(mu)
+        import torch
+        dev = torch.from_numpy(mu).to("cuda:%d" % backend.device)
+        try:
+            return run(dev)
+        finally:
+            dev.zero_()
+            torch.cuda.synchronize(backend.device)
+
+    def rekey_to(self, other, basebit=None, t=None, mask_seed=None, noise_seed=None, stdev=None, backend=None):
+        """The re-keying key from this secret's LWE key to the LWE key of `other` (a SecretKeySet of any set and n), made by the
+        owner of both secrets -> RekeyKey of form "seeded": n_src t seeded encryptions (rows 0 .. n_src t - 1 of the public mask seed,
+        domains 7 / 8) of keygen.rekey_messages under other's LWE key, 32 + 4 n_src t bytes. basebit, t default to
+        keygen.rekey_default(other.name), stdev to other's ks_stdev (ValueError where that truncates to zero: pass one). Equal seeds
+        are refused. With backend= (a redsec_amd.Backend of other's set and n) the bodies are made on the device
+        (rs_encrypt_seeded_dev): the same words."""
+        from . import keygen
+        basebit, t = self._rekey_digits(other.name, basebit, t)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        keygen._check_seeds(mask_seed, noise_seed)
+        stdev = keygen.rekey_row_stdev(other.name) if stdev is None else float(stdev)
+        if backend is None:
+            body = self._rekey_mu(basebit, t, None, lambda mu: keygen.encrypt_seeded(other.lwe_key, mu, mask_seed, noise_seed, 0, stdev))
+        else:
+            other._check_backend(backend)
+            body = self._rekey_mu(basebit, t, backend, lambda mu: backend.encrypt_seeded(other.lwe_key, mu, mask_seed, noise_seed, 0,
+                                                                                         stdev).cpu().numpy())
+        return RekeyKey(self.name, other.name, self.n, other.n, basebit, t, mask_seed=mask_seed, body=body)
+
+    def rekey_for(self, rlwe_pk, basebit=None, t=None, rand_seed=None, stdev=None, backend=None):
+        """The re-keying key from this secret's LWE key to the RING key behind the recipient's RlwePublicKey, made without any secret of
+        the recipient -> RekeyKey of form "rlwe": ceil(n_src t / N) ciphertexts of keygen.rekey_messages, the odd rows negated
+        (keygen.rekey_alternate: the rows of one ciphertext share its selector and noise polynomials, and alternating signs keep
+        their common part from adding up under the unsigned digits), under rlwe_pk (rows 0 .. of the PRIVATE rand seed, domains
+        12 / 13), 8 N bytes each; n_dst = N, and the recipient decrypts what arrives with phase(., ring=True). basebit, t default to keygen.rekey_default(rlwe_pk.name), stdev to the set's bk_stdev (ValueError where that
+        truncates to zero: pass one). A rand seed equal to the key's public mask seed is refused. With backend= (a redsec_amd.Backend
+        of the recipient's set) the ciphertexts are made on the device (rs_rlwe_pk_encrypt_dev): the same words."""
+        from . import keygen
+        basebit, t = self._rekey_digits(rlwe_pk.name, basebit, t)
+        rand_seed = os.urandom(32) if rand_seed is None else bytes(rand_seed)
+        keygen._check_seeds(rlwe_pk.mask_seed, rand_seed)
+        stdev = keygen.rlwe_default_stdev(rlwe_pk.name) if stdev is None else float(stdev)
+        if backend is None:
+            rlwe = self._rekey_mu(basebit, t, None, lambda mu: keygen.rlwe_pk_encrypt(rlwe_pk.expand(), mu, rand_seed, 0, stdev=stdev), True)
+        else:
+            rlwe = self._rekey_mu(basebit, t, backend, lambda mu: backend.rlwe_pk_encrypt(rlwe_pk, mu, rand_seed, 0, stdev).cpu().numpy(), True)
+        return RekeyKey(self.name, rlwe_pk.name, self.n, rlwe_pk.N, basebit, t, rlwe=rlwe)
 
     def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
@@ -351,12 +418,13 @@ def read_tfhe_keyset(f, secret):
     return out
 
 
-# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key; redsec_amd/host/
+# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key, "RSR1" re-keying key; redsec_amd/host/
 # tfhe_shim.cpp ParamHeader): magic, int32 n, N, k, l, Bgbit, ks_t, ks_basebit, then double lwe alpha min / max, tlwe alpha min / max.
 _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
-RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352}
+RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352,
+            "RSR1": 0x31525352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -575,6 +643,111 @@ def read_packing_key(f):
     if len(rest) != 4 * n * t * shape[0]:
         raise ValueError("truncated packing key file: %d body bytes, expected %d" % (len(rest), 4 * n * t * shape[0]))
     return PackingKey(name, n, basebit, t, seed, np.frombuffer(rest, np.int32).copy())
+
+
+class RekeyKey:
+    """A re-keying key (include/redsec_hip.h rs_rekey_dev) from the LWE key of a secret of set src_name
+    and dimension n_src to a recipient's key of dimension n_dst, with the digit shape (basebit, t). Row i t + j encrypts
+    s_i 2^(32-(j+1) basebit). One of two payloads:
+      form "seeded"  the public 32-byte mask seed and the n_src t body words (int32, numpy) of seeded ciphertexts, rows 0 ..
+                     n_src t - 1 of domains 7 / 8, under the recipient's LWE key of set dst_name and dimension n_dst
+      form "rlwe"    ceil(n_src t / N) RLWE ciphertexts int32 [R][2][N] under the recipient's compact RLWE public key; n_dst = N and
+                     the destination is the recipient's ring key read as an LWE key. Slot r carries row r, negated when r is odd
+                     (keygen.rekey_alternate) and negated back on expansion
+    nbytes: what travels (seed + bodies, or the ciphertexts)."""
+
+    def __init__(self, src_name, dst_name, n_src, n_dst, basebit, t, mask_seed=None, body=None, rlwe=None):
+        self.src_name, self.dst_name, self.n_src, self.n_dst = src_name, dst_name, int(n_src), int(n_dst)
+        self.basebit, self.t = int(basebit), int(t)
+        assert src_name in PARAM_SETS and dst_name in PARAM_SETS, "unknown parameter set"
+        assert 1 <= self.basebit <= 8 and self.t >= 1 and self.t * self.basebit <= 32, "basebit in 1 .. 8, t >= 1, t basebit <= 32"
+        assert self.n_src >= 1 and self.n_dst >= 1, "dimensions must be positive"
+        assert (rlwe is None) != (body is None), "one payload: seeded bodies or RLWE ciphertexts"
+        self.rows = self.n_src * self.t
+        if rlwe is None:
+            self.form, self.mask_seed, self.rlwe = "seeded", bytes(mask_seed), None
+            assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+            self.body = np.ascontiguousarray(body, np.int32).reshape(-1)
+            assert self.body.size == self.rows, "body must have n_src t = %d words" % self.rows
+        else:
+            N = PARAM_SETS[dst_name][1]
+            assert self.n_dst == N, "a key under an RLWE public key has n_dst = N = %d" % N
+            self.form, self.mask_seed, self.body = "rlwe", None, None
+            self.rlwe = np.ascontiguousarray(rlwe, np.int32).reshape(-1)
+            assert self.rlwe.size == -(-self.rows // N) * 2 * N, "rlwe must hold [ceil(n_src t / N)][2][N] words"
+            self.rlwe = self.rlwe.reshape(-1, 2, N)
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.rows if self.form == "seeded" else 4 * self.rlwe.size
+
+    def expand(self):
+        """K[i][j] = row i t + j: the domain-7 masks of the seed beside the bodies, or the rows extracted from the RLWE ciphertexts
+        -> int32 [n_src][t][n_dst+1], what rs_rekey_dev takes (numpy path; Backend.upload_rekey_key does the same on the device)."""
+        from . import keygen
+        if self.form == "seeded":
+            rows = keygen.expand_ciphertexts(self.mask_seed, self.body, self.n_dst, 0)
+        else:
+            rows = keygen.rekey_alternate(keygen.rlwe_extract(self.rlwe, self.rows))
+        return rows.reshape(self.n_src, self.t, self.n_dst + 1)
+
+
+def _rs_header(magic, name, n, max_stdev=0.012467):
+    (_, N, k, l, Bgbit, t, basebit, ks_stdev, bk_stdev) = PARAM_SETS[name]
+    h = np.zeros((), _RS_HEADER)
+    h["magic"], h["n"], h["N"], h["k"], h["l"], h["Bgbit"], h["ks_t"], h["ks_basebit"] = RS_MAGIC[magic], n, N, k, l, Bgbit, t, basebit
+    h["lwe_alpha_min"], h["lwe_alpha_max"], h["tlwe_alpha_min"], h["tlwe_alpha_max"] = ks_stdev, max_stdev, bk_stdev, max_stdev
+    return h.tobytes()
+
+
+def write_rekey_key(f, key):
+    """A re-keying key file (binary file object): the RS header with magic RSR1 for the destination (its n the key's n_dst), the
+    same header for the source (its n the key's n_src), int32 basebit, int32 t, int32 form (0 seeded, 1 rlwe), then the 32-byte
+    mask seed and the n_src t int32 body words, or the ceil(n_src t / N) 2 N int32 words of the RLWE ciphertexts. key: RekeyKey."""
+    f.write(_rs_header("RSR1", key.dst_name, key.n_dst))
+    f.write(_rs_header("RSR1", key.src_name, key.n_src))
+    f.write(np.array([key.basebit, key.t, 0 if key.form == "seeded" else 1], "<i4").tobytes())
+    if key.form == "seeded":
+        f.write(key.mask_seed)
+        f.write(key.body.tobytes())
+    else:
+        f.write(key.rlwe.tobytes())
+
+
+def read_rekey_key(f):
+    """-> RekeyKey of a re-keying key file. Raises ValueError for a truncated file, another magic, a parameter shape no set has, a
+    dimension below 1, digits outside basebit 1 .. 8, t >= 1, t basebit <= 32, an unknown form, an RLWE form whose n_dst is not the
+    destination's N, or a payload that is not exactly the words the header promises."""
+    names, dims = [], []
+    for what in ("destination", "source"):
+        raw = f.read(_RS_HEADER.itemsize)
+        if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSR1"]:
+            raise ValueError("not a re-keying key (RSR1) file: %s header" % what)
+        if len(raw) < _RS_HEADER.itemsize:
+            raise ValueError("truncated re-keying key file: short %s header" % what)
+        h = np.frombuffer(raw, _RS_HEADER)[0]
+        shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+        name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+        if name is None:
+            raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s (%s)" % (shape, what))
+        names.append(name)
+        dims.append(int(h["n"]))
+    digits, rest = f.read(12), f.read()
+    if len(digits) < 12:
+        raise ValueError("truncated re-keying key file: %d bytes after the headers" % len(digits))
+    basebit, t, form = (int(v) for v in np.frombuffer(digits, "<i4"))
+    (dst, src), (n_dst, n_src) = names, dims
+    if n_src < 1 or n_dst < 1 or not (1 <= basebit <= 8 and t >= 1 and t * basebit <= 32) or form not in (0, 1):
+        raise ValueError("re-keying key file with n_src = %d, n_dst = %d, basebit = %d, t = %d, form = %d" % (n_src, n_dst, basebit, t, form))
+    N = PARAM_SETS[dst][1]
+    if form == 1 and n_dst != N:
+        raise ValueError("re-keying key file of the RLWE form with n_dst = %d, not N = %d" % (n_dst, N))
+    want = 32 + 4 * n_src * t if form == 0 else 4 * -(-(n_src * t) // N) * 2 * N
+    if len(rest) != want:
+        raise ValueError("truncated re-keying key file: %d payload bytes, expected %d" % (len(rest), want))
+    if form == 0:
+        return RekeyKey(src, dst, n_src, n_dst, basebit, t, mask_seed=rest[:32], body=np.frombuffer(rest[32:], np.int32).copy())
+    return RekeyKey(src, dst, n_src, n_dst, basebit, t, rlwe=np.frombuffer(rest, np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

@@ -1,5 +1,5 @@
 // rs_api_client.cpp -- key material and client-side calls of the C ABI (include/redsec_hip.h) that need no lane, no launch plan
-// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack and the packing key, device
+// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying and the packing key, device
 // decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
 // (rs::with_secret_copy; rs_keygen_dev of rs_api_keys.cpp goes through it too) and of the refusals these calls share.
 #include "rs_api_internal.h"
@@ -11,6 +11,7 @@
 #include "rs_keygen.h"
 #include "rs_pack.h"
 #include "rs_packkey.h"
+#include "rs_rekey.h"
 #include "rs_rlwe.h"
 
 using rs::fail;
@@ -234,6 +235,28 @@ int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const
     return fail(RS_ERR_INVALID, "count = %zu is too large for one launch", count);
   const rs::PackArgs a{rlwe, ct, pack_key, (long)count, (int)n, (int)N, (int)basebit, (int)t};
   RS_HIP(rs::launch_pack(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// re-keying (include/redsec_hip.h; kernels of rs_rekey.hip, integer arithmetic only): needs no key, both dimensions are arguments
+int rs_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* ct, size_t B, int32_t n_src, const int32_t* rekey_key, int32_t n_dst,
+                 int32_t basebit, int32_t t, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !ct || !rekey_key) return fail(RS_ERR_INVALID, "null pointer");
+  if (n_src < rs::kRkMinDim || n_src > rs::kRkMaxDim) return fail(RS_ERR_INVALID, "n_src = %d is outside 1 .. %d", (int)n_src, rs::kRkMaxDim);
+  if (n_dst < rs::kRkMinDim || n_dst > rs::kRkMaxDim) return fail(RS_ERR_INVALID, "n_dst = %d is outside 1 .. %d", (int)n_dst, rs::kRkMaxDim);
+  if ((rc = refuse_digits(basebit, t, true)) != RS_OK) return rc;
+  const size_t row_bytes = ((size_t)std::max(n_src, n_dst) + 1) * sizeof(int32_t);
+  if (B > (size_t)LONG_MAX / row_bytes) return fail(RS_ERR_INVALID, "B = %zu is too large for rows of %zu bytes", B, row_bytes);
+  if (B == 0) return RS_OK;
+  // workgroups of the two launches: one per kRkInitThreads output words, and rs::rk_groups
+  const size_t init_groups = (B * ((size_t)n_dst + 1) + rs::kRkInitThreads - 1) / rs::kRkInitThreads;
+  const size_t per_tile = (size_t)rs::rk_word_tiles(n_dst) * (size_t)rs::rk_splits((long)B, n_src, n_dst);
+  if (init_groups > (size_t)INT32_MAX || (size_t)rs::rk_ct_tiles((long)B) > (size_t)INT32_MAX / per_tile)
+    return fail(RS_ERR_INVALID, "B = %zu is too large for one launch", B);
+  const rs::RekeyArgs a{out, ct, rekey_key, (long)B, (int)n_src, (int)n_dst, (int)basebit, (int)t};
+  RS_HIP(rs::launch_rekey(a, (hipStream_t)stream));
   return RS_OK;
 }
 

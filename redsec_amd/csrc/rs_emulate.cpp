@@ -17,6 +17,7 @@
 #include "rs_keygen.h"
 #include "rs_pack.h"
 #include "rs_packkey.h"
+#include "rs_rekey.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
@@ -1408,6 +1409,98 @@ void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pac
       }
     uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0;
     for (int x = 0; x < rs::kPaTile; ++x) o[x] += 0u - acc[x];
+  }
+}
+
+// ---- re-keying (rs_rekey_dev) through the functions of rs_rekey.h ----
+uint32_t rs_emu_rekey_offset(int basebit, int t) { return rs::rk_offset(basebit, t); }
+uint32_t rs_emu_rekey_digit(uint32_t abar, int basebit, int j) { return rs::rk_digit(abar, basebit, j); }
+int rs_emu_rekey_tile() { return rs::kRkTile; }
+int rs_emu_rekey_wave_cts() { return rs::kRkWaveCts; }
+int rs_emu_rekey_words() { return rs::kRkWords; }
+int rs_emu_rekey_seg() { return rs::kRkSeg; }
+int rs_emu_rekey_fill() { return rs::kRkFill; }
+int rs_emu_rekey_chunks(int n_src) { return rs::rk_chunks(n_src); }
+int rs_emu_rekey_span(long B, int n_src, int n_dst) { return rs::rk_span(B, n_src, n_dst); }
+int rs_emu_rekey_splits(long B, int n_src, int n_dst) { return rs::rk_splits(B, n_src, n_dst); }
+long rs_emu_rekey_groups(long B, int n_src, int n_dst) { return rs::rk_groups(B, n_src, n_dst); }
+// rekey_init_kernel, then rekey_kernel workgroup by workgroup as the kernel places them: the grid over (word tile, index split,
+// ciphertext tile), per chunk the transposed mask words of every wave, per source index the staged t x kRkWords key words, per wave
+// and lane 32 accumulators fed by scalar digits in groups of kRkGroup, the negated partial sums added into the rows below B.
+// span_override > 0 walks the same loops with that many chunks per workgroup instead of rk_span's (the CPU tests reach the
+// splits of a large launch with a small one that way); 0 is the kernel's own plan.
+void rs_emu_rekey(const int32_t* ct_, long B, int n_src, const int32_t* rekey_key, int n_dst, int basebit, int t, int span_override,
+                  int32_t* out_) {
+  if (B <= 0) return;
+  const long W = (long)n_dst + 1;
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_);
+  for (long idx = 0; idx < B * W; ++idx) {
+    const long r = idx / W;
+    const int w = (int)(idx - r * W);
+    out[idx] = w == n_dst ? (uint32_t)ct_[(size_t)r * ((size_t)n_src + 1) + n_src] : 0u;
+  }
+  const int chunks = rs::rk_chunks(n_src), wtiles = rs::rk_word_tiles(n_dst);
+  const int span = span_override > 0 ? span_override : rs::rk_span(B, n_src, n_dst);
+  const int splits = (chunks + span - 1) / span;
+  const long groups = rs::rk_ct_tiles(B) * wtiles * splits;
+  const uint32_t off = rs::rk_offset(basebit, t), mask = (1u << basebit) - 1u;
+  const uint32_t* key = reinterpret_cast<const uint32_t*>(rekey_key);
+  std::vector<uint32_t> s_a((size_t)rs::kRkWaves * rs::kRkSeg * rs::kRkWaveCts), s_key((size_t)t * rs::kRkWords);
+  std::vector<uint32_t> acc((size_t)rs::kRkThreads * rs::kRkWaveCts);
+  for (long blk = 0; blk < groups; ++blk) {
+    long g = blk;
+    const int wt = (int)(g % wtiles); g /= wtiles;
+    const int split = (int)(g % splits);
+    const long ctile = g / splits;
+    const int c_first = split * span, c_last = c_first + span < chunks ? c_first + span : chunks;
+    std::fill(acc.begin(), acc.end(), 0u);
+    int rows[rs::kRkWaves];
+    const uint32_t* cts[rs::kRkWaves];
+    for (int wave = 0; wave < rs::kRkWaves; ++wave) {
+      const long r0 = ctile * rs::kRkTile + (long)wave * rs::kRkWaveCts, left = B - r0;
+      rows[wave] = left >= rs::kRkWaveCts ? rs::kRkWaveCts : left > 0 ? (int)left : 0;
+      cts[wave] = reinterpret_cast<const uint32_t*>(ct_) + (size_t)(rows[wave] > 0 ? r0 : 0) * ((size_t)n_src + 1);
+    }
+    for (int chunk = c_first; chunk < c_last; ++chunk) {
+      const int i0 = chunk * rs::kRkSeg, segn = n_src - i0 < rs::kRkSeg ? n_src - i0 : rs::kRkSeg;
+      for (int wave = 0; wave < rs::kRkWaves; ++wave) {
+        uint32_t* sa = &s_a[(size_t)wave * rs::kRkSeg * rs::kRkWaveCts];
+        for (int idx = 0; idx < segn * rs::kRkWaveCts; ++idx) {
+          const int c = idx / segn, ii = idx - c * segn;
+          sa[rs::rk_mask_index(ii, c)] = c < rows[wave] ? cts[wave][(size_t)c * ((size_t)n_src + 1) + i0 + ii] + off : 0u;
+        }
+      }
+      for (int ii = 0; ii < segn; ++ii) {
+        for (int j = 0; j < t; ++j)
+          for (int lane = 0; lane < rs::kRkWords; ++lane) {
+            const int w = wt * rs::kRkWords + lane;
+            s_key[(size_t)j * rs::kRkWords + lane] = w <= n_dst ? key[rs::rk_key_offset(n_dst, t, i0 + ii, j) + w] : 0u;
+          }
+        for (int wave = 0; wave < rs::kRkWaves; ++wave) {
+          if (rows[wave] == 0) continue;
+          const uint32_t* abar = &s_a[(size_t)wave * rs::kRkSeg * rs::kRkWaveCts + rs::rk_mask_index(ii, 0)];
+          for (int lane = 0; lane < rs::kRkWords; ++lane) {
+            uint32_t* a32 = &acc[((size_t)wave * rs::kRkWords + lane) * rs::kRkWaveCts];
+            for (int j = 0; j < t; ++j) {
+              const uint32_t kw = s_key[(size_t)j * rs::kRkWords + lane];
+              const int shift = 32 - (j + 1) * basebit;
+              for (int q = 0; q < rs::kRkWaveCts / rs::kRkGroup; ++q) {
+                if (q * rs::kRkGroup >= rows[wave]) continue;
+                for (int c = q * rs::kRkGroup; c < (q + 1) * rs::kRkGroup; ++c) a32[c] += kw * ((abar[c] >> shift) & mask);
+              }
+            }
+          }
+        }
+      }
+    }
+    for (int wave = 0; wave < rs::kRkWaves; ++wave)
+      for (int lane = 0; lane < rs::kRkWords; ++lane) {
+        const int w = wt * rs::kRkWords + lane;
+        if (w > n_dst) continue;
+        const long r0 = ctile * rs::kRkTile + (long)wave * rs::kRkWaveCts;
+        for (int c = 0; c < rows[wave]; ++c)
+          out[(size_t)(r0 + c) * W + w] += 0u - acc[((size_t)wave * rs::kRkWords + lane) * rs::kRkWaveCts + c];
+      }
   }
 }
 

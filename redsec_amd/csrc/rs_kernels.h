@@ -179,6 +179,15 @@ struct PackArgs {
   int n, N, basebit, t;
 };
 hipError_t launch_pack(const PackArgs& a, hipStream_t st);
+// re-keying (rs_rekey_dev; placement and index arithmetic of rs_rekey.h): both dimensions are the caller's, not the context's
+struct RekeyArgs {
+  int32_t* out;                                       // [B][n_dst+1]
+  const int32_t* ct;                                  // [B][n_src+1]
+  const int32_t* key;                                 // [n_src][t][n_dst+1]: the re-keying key
+  long B;
+  int n_src, n_dst, basebit, t;
+};
+hipError_t launch_rekey(const RekeyArgs& a, hipStream_t st);
 // the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev; streams and placement of rs_packkey.h): row i t + j is
 // (a, a*S + e + s_i g_j X^0), a the domain-14 words of the mask seed, e the domain-15 Gaussians of the noise seed
 struct PackKeygenArgs {

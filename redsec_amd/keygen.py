@@ -80,6 +80,13 @@ section 19): the bodies above generated by the device word for word, the full ke
 bodies, and the noise words e_ij = b_ij - a_ij*S - s_i 2^(32-(j+1) basebit) X^0 of a key under its secret. pack_key_noise restates
 the audit (through _times_binary, a third arithmetic beside the device's two loops); pack_noise_limit gives the default limit.
 
+Re-keying (rs_rekey_dev; include/redsec_hip.h): a public keyswitch from an LWE key s of dimension n_src
+to an LWE key s' of dimension n_dst under a caller-supplied key [n_src][t][n_dst+1] whose row i t + j encrypts s_i 2^(32-(j+1)
+basebit) under s'. The key uses no stream of its own: its rows are seeded ciphertexts of rows 0 .. n_src t - 1 (domains 7 / 8) under
+the recipient's LWE key, or the rows extracted from RLWE public-key ciphertexts (domains 12 / 13) under the recipient's ring key.
+  out[r] = (0, b_r) - sum_{i,j} d_ij(r) K[i][j], d_ij(r) = ((a_i + off of sample r) >> (32-(j+1) basebit)) & (2^basebit - 1).
+  rekey_messages / rekey / rekey_sigma / rekey_default restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -758,6 +765,83 @@ def pack_sigma(n, N, basebit, t, count, stdev):
     cr = min(int(count), int(N))
     base = 1 << basebit
     return float(np.sqrt(n * t * cr * (base - 1) * (2 * base - 1) / 6.0 * float(stdev) ** 2 + (n / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
+
+
+# ---- re-keying (rs_rekey_dev restated) ----
+
+def rekey_default(dst_name):
+    """(basebit, t) of a re-keying key whose destination is a secret of set dst_name: (2, 8) to default-128, whose rows carry the
+    set's ks_stdev 2^-15 and whose results are +-1/8 bits (8 rekey_sigma stays below 1/16 from n_src = 630); (4, 5) to
+    redsec_small_v2 and redsec_small, (4, 6) to redsec_medium and redsec_large, whose 1/4096-scale values need 8 rekey_sigma below
+    the half step 1/8192 from a source of the set's own n (20 bits of digits leave the rounding sqrt(n_src / 24) 2^-20 alone at
+    1.5e-5 from n_src = 6144). INTEGRATION.md section 21 has the table."""
+    _shape(dst_name)
+    return (2, 8) if dst_name == "default128" else (4, 6) if dst_name in ("redsec_medium", "redsec_large") else (4, 5)
+
+
+def rekey_row_stdev(dst_name):
+    """The default deviation of a seeded row of a re-keying key under a secret of dst_name: the set's ks_stdev, the deviation of
+    the rows of its own keyswitching key. ValueError where that truncates to zero in a 32-bit torus (redsec_medium, redsec_large)."""
+    stdev = _shape(dst_name)["ks_stdev"]
+    if stdev < MIN_STDEV:
+        raise ValueError("the ks_stdev of %s (%.3g) truncates to zero in a 32-bit torus and noise-free rows publish the secret: "
+                         "pass an explicit stdev >= 2^-31" % (dst_name, stdev))
+    return stdev
+
+
+def rekey_messages(lwe_key, basebit, t):
+    """The torus words a re-keying key encrypts: s_i 2^(32-(j+1) basebit) at row i t + j -> int32 [n_src t]."""
+    basebit, t = _check_digits(basebit, t)
+    s = np.asarray(lwe_key).ravel().astype(np.uint32)
+    g = (np.uint32(1) << (32 - (np.arange(t) + 1) * basebit).astype(np.uint32)).astype(np.uint32)
+    return (s[:, None] * g[None, :]).ravel().view(np.int32)
+
+
+def rekey_alternate(rows):
+    """The odd rows negated mod 2^32 (its own inverse): rows int32 [R] (messages) or [R][W] (samples) -> the same shape. A key made
+    under an RLWE public key carries row r in slot r of a ciphertext whose N slots share one selector u and the key's and the
+    ciphertext's noise polynomials; a binary u has mean 1/2, so the noise of neighbouring slots has a common part, fixed by the key,
+    which the unsigned digits (mean (2^basebit - 1) / 2) would add up over all n_src t rows into an offset of many rekey_sigma
+    (measured: up to 40 at n_src = 350, (4, 5)). Encrypting every other row negated and negating it back after the extraction
+    makes the common part cancel in pairs; what is left fits rekey_sigma."""
+    out = np.array(rows, np.int32, copy=True)
+    with np.errstate(over="ignore"):
+        out[1::2] = (np.uint32(0) - out[1::2].view(np.uint32)).view(np.int32)
+    return out
+
+
+def rekey(ct, key, basebit, t):
+    """rs_rekey_dev restated: ct int32 [B][n_src+1], key int32 [n_src][t][n_dst+1] -> int32 [B][n_dst+1], out[r] = (0, b_r) -
+    sum_{i,j} d_ij(r) K[i][j]. The sum over the n_src t rows is ONE float64 matrix product per 16-bit half of the key words (every
+    entry below 2^8 2^16 n_src t < 2^53: exact), recombined in 64-bit integers: nothing like the device's tiled 32-bit multiply-adds."""
+    basebit, t = _check_digits(basebit, t)
+    key = np.ascontiguousarray(key, np.int32)
+    assert key.ndim == 3 and key.shape[1] == t, "key must hold [n_src][t][n_dst+1] words"
+    n_src, W = key.shape[0], key.shape[2]
+    assert W >= 2 and n_src * t < 1 << 28, "key rows need n_dst >= 1 and n_src t below 2^28"
+    ct = np.ascontiguousarray(ct, np.int32).reshape(-1, n_src + 1)
+    B = ct.shape[0]
+    out = np.zeros((B, W), np.uint64)
+    ku = key.view(np.uint32).reshape(n_src * t, W)
+    lo, hi = (ku & np.uint32(0xFFFF)).astype(np.float64), (ku >> np.uint32(16)).astype(np.float64)
+    for r0 in range(0, B, 4096):
+        D = pack_digits(ct[r0:r0 + 4096, :n_src], basebit, t).reshape(-1, n_src * t).astype(np.float64)      # [r][i t + j]
+        out[r0:r0 + 4096] = (D @ lo).astype(np.uint64) + ((D @ hi).astype(np.uint64) << np.uint64(16))
+    with np.errstate(over="ignore"):
+        out = np.uint64(0) - out
+        out[:, W - 1] += ct[:, n_src].view(np.uint32)
+    return (out & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)
+
+
+def rekey_sigma(n_src, basebit, t, sigma_row):
+    """Deviation of the re-keying error of one sample, as a real in [-1/2, 1/2): the noise of the n_src t key rows under the
+    digits (a uniform digit has mean square (2^basebit - 1)(2^(basebit+1) - 1) / 6) and the rounding of the digits over the n_src / 2
+    set key bits. sigma_row is the deviation of one key row's phase: the stdev of a seeded row, stdev sqrt(N + 1) for a row made
+    under an RLWE public key.
+      sigma^2 = n_src t (2^basebit - 1)(2^(basebit+1) - 1)/6 sigma_row^2  +  (n_src/2) 2^(-2 t basebit)/12"""
+    basebit, t = _check_digits(basebit, t)
+    base = 1 << basebit
+    return float(np.sqrt(n_src * t * (base - 1) * (2 * base - 1) / 6.0 * float(sigma_row) ** 2 + (n_src / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
