@@ -276,6 +276,33 @@ int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
 int rs_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* ct, size_t B, int32_t n_src,
                  const int32_t* rekey_key, int32_t n_dst, int32_t basebit, int32_t t, void* stream);
 
+/* Ring re-keying: a public RLWE-to-RLWE keyswitch under a caller-supplied key of t + 1 ring samples.
+ * Packed ciphertexts (rs_pack_dev, rs_rlwe_pk_encrypt_dev) under a ring key S leave the server decryptable under another ring key
+ * S' of the same degree: packed replies for a third party, or key rotation of packed ciphertexts that lie in storage, with one
+ * keyswitch error and no detour through LWE samples. Word-wise mod 2^32 with negacyclic products:
+ *   K[j]     = row j of ring_key = (a_j, b_j),  b_j - a_j*S' = e_j + h_j S,  h_j = 2^(31-(j+1) basebit)                j < t
+ *   K[t]     = (a_t, b_t),  b_t - a_t*S' = e_t + c0 (1 + X + ... + X^(N-1)) S,  c0 = (2^basebit - 1) sum_j h_j
+ *   abar_k   = a_k + off,  off = 2^(31 - t basebit)
+ *   d_j(k)   = 2 ((abar_k >> (32-(j+1) basebit)) & (2^basebit - 1)) - (2^basebit - 1)        odd, symmetric about zero
+ *   D_j(X)   = sum_k d_j(k) X^k
+ *   out[r]   = (0, b_r) - K[t] - sum_{j<t} D_j(X) K[j]
+ * Under S', out[r] has the phase of rlwe[r] under S plus the re-keying error, per coefficient of variance
+ *   sigma^2 = (t N (4^basebit - 1)/3 + 1) sigma_row^2  +  (N/2) 2^(-2 t basebit)/12
+ * (sigma_row the deviation of one key row's phase per coefficient; an odd digit has mean square (4^basebit - 1)/3; the second
+ * term is the rounding of abar to t basebit bits). The digits are centred, not the unsigned ones of rs_pack_dev / rs_rekey_dev,
+ * and the constant row K[t] carries what the centring took away: rows made from one RLWE public key share that key's noise, and
+ * a digit polynomial with a mean would add the common part up along the coefficients (16 .. 22 times the formula with unsigned
+ * digits; section 22 has the comparison). The key needs no call of its own: t + 1 seeded ring samples under S', or, without the
+ * recipient's secret, the t + 1 ciphertexts of rs_rlwe_pk_encrypt_dev over the message rows under the recipient's RLWE public key.
+ * rlwe, out DEVICE int32[R][2][N]; ring_key DEVICE int32[t+1][2][N]; out overlaps neither input. N is the context's ring; source
+ * and destination share it (crossing between rings of different degree is out of scope). Integer arithmetic only, exact: the
+ * words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on `stream`; no allocation. R = 0 is
+ * a no-op that returns RS_OK. A second call into the same buffer gives the same words.
+ * RS_ERR_INVALID: a null out, rlwe or ring_key; basebit outside 1 .. 8; t < 1; t basebit > 31 (h_j is an integer); an R whose row
+ * arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_pack_dev does. */
+int rs_ring_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* rlwe, size_t R,
+                      const int32_t* ring_key, int32_t basebit, int32_t t, void* stream);
+
 /* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
  * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three
  * need no loaded key and work on every context, N = 1024 .. 8192: 32-bit integer adds, no product, no transform, no mode dependence.

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "rs_circuit_create", "rs_circuit_destroy", "rs_circuit_run_dev",
     "rs_bootstrap_sparse_dev",
     "rs_rekey_dev",
+    "rs_ring_rekey_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -134,6 +135,7 @@ def load_library(path=None):
     L.rs_rlwe_extract_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.rs_pack_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rs_ring_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
     L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
     L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
@@ -545,6 +547,37 @@ class Backend:
             rows = self.rlwe_extract(torch.from_numpy(key.rlwe).to(dev), key.rows)
             rows[1::2].neg_()                                   # keygen.rekey_alternate: the odd rows travel negated
         return rows.reshape(key.n_src, key.t, key.n_dst + 1)
+
+    # ---- ring re-keying ----
+    def ring_rekey(self, rlwe, key, basebit=None, t=None, out=None):
+        """Packed ciphertexts rlwe (int32 CUDA tensor [R][2][N]) keyswitched to a recipient's ring key under a caller-supplied key
+        (rs_ring_rekey_dev, on torch's current stream) -> int32 CUDA tensor [R][2][N] (or into `out`, which overlaps neither input).
+        key: a client.RingRekeyKey (uploaded on this context's device, whose ring must be the key's: keep the tensor of
+        upload_ring_rekey_key for repeated calls) or an int32 CUDA tensor [t+1][2][N] with explicit basebit and t. Needs no loaded
+        key."""
+        from . import keygen
+        N = self.p.N
+        if hasattr(key, "form"):
+            basebit, t, key = key.basebit, key.t, self.upload_ring_rekey_key(key)
+        if basebit is None or t is None:
+            raise ValueError("a ring re-keying key given as a tensor needs explicit basebit and t")
+        basebit, t = keygen._check_ring_digits(basebit, t)
+        assert key.numel() == (t + 1) * 2 * N, "key must hold [t+1][2][N] words"
+        assert rlwe.numel() % (2 * N) == 0, "rlwe must hold [R][2][N] words"
+        R = rlwe.numel() // (2 * N)
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        _check(self.L, self.L.rs_ring_rekey_dev(self.h, self._ck_dev(out), self._ck_dev(rlwe), R, self._ck_dev(key), basebit, t, self._stream()))
+        return out
+
+    def upload_ring_rekey_key(self, key):
+        """The expanded client.RingRekeyKey on this context's device -> int32 CUDA tensor [t+1][2][N] (pass it to ring_rekey with
+        key.basebit and key.t). The key is t + 1 rows, so the masks of the seeded form are regenerated on the host. ValueError for
+        a key of another ring."""
+        import torch
+        if self.p.N != key.N:
+            raise ValueError("the ring re-keying key is of N = %d (%s), the context's ring N = %d" % (key.N, key.dst_name, self.p.N))
+        return torch.from_numpy(key.expand()).to("cuda:%d" % self.device)
 
     # ---- the packing key on the device (INTEGRATION.md section 19) ----
     def _secrets(self, lwe_key, tlwe_key):

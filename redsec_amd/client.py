@@ -346,6 +346,60 @@ class SecretKeySet:
             rlwe = self._rekey_mu(basebit, t, backend, lambda mu: backend.rlwe_pk_encrypt(rlwe_pk, mu, rand_seed, 0, stdev).cpu().numpy(), True)
         return RekeyKey(self.name, rlwe_pk.name, self.n, rlwe_pk.N, basebit, t, rlwe=rlwe)
 
+    # ring re-keying (include/redsec_hip.h rs_ring_rekey_dev): keys under which a server turns PACKED
+    # ciphertexts under THIS secret's ring key into packed ciphertexts under a recipient's ring key of the same N
+    def _ring_rekey_digits(self, dst_name, form, basebit, t):
+        from . import keygen
+        if PARAM_SETS[dst_name][1] != self.N:
+            raise ValueError("source and destination rings differ: N = %d (%s) and %d (%s); crossing between rings is out of scope"
+                             % (self.N, self.name, PARAM_SETS[dst_name][1], dst_name))
+        d = keygen.ring_rekey_default(dst_name, form)
+        return keygen._check_ring_digits(d[0] if basebit is None else basebit, d[1] if t is None else t)
+
+    def ring_rekey_to(self, other, basebit=None, t=None, mask_seed=None, noise_seed=None, stdev=None):
+        """The ring re-keying key from this secret's ring key to the ring key of `other` (a SecretKeySet of the same N), made by the
+        owner of both secrets -> RingRekeyKey of form "seeded": t + 1 seeded ring samples (rows 0 .. t of the public mask seed,
+        domains 16 / 17) of keygen.ring_rekey_messages under other's ring key, 32 + 4 N (t + 1) bytes. basebit, t default to
+        keygen.ring_rekey_default(other.name, "seeded"), stdev to other's bk_stdev (ValueError where that truncates to zero: pass
+        one). Equal seeds are refused. The t + 1 products run on the host: there is no device generator."""
+        from . import keygen
+        basebit, t = self._ring_rekey_digits(other.name, "seeded", basebit, t)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        keygen._check_seeds(mask_seed, noise_seed)
+        stdev = keygen.rlwe_default_stdev(other.name) if stdev is None else float(stdev)
+        body = keygen.ring_rekey_key(self.tlwe_key, other.tlwe_key, mask_seed, noise_seed, basebit, t, stdev)
+        return RingRekeyKey(self.name, other.name, basebit, t, mask_seed=mask_seed, body=body)
+
+    def ring_rekey_for(self, rlwe_pk, basebit=None, t=None, rand_seed=None, stdev=None, backend=None):
+        """The ring re-keying key from this secret's ring key to the ring key behind the recipient's RlwePublicKey, made without any
+        secret of the recipient -> RingRekeyKey of form "rlwe": the t + 1 ciphertexts of keygen.ring_rekey_messages under rlwe_pk
+        (rows 0 .. t of the PRIVATE rand seed, domains 12 / 13), 8 N bytes each, already the layout rs_ring_rekey_dev takes.
+        basebit, t default to keygen.ring_rekey_default(rlwe_pk.name, "rlwe"), stdev to the set's bk_stdev (ValueError where that
+        truncates to zero: pass one). A rand seed equal to the key's public mask seed is refused. With backend= (a
+        redsec_amd.Backend of the recipient's set) the ciphertexts are made on the device (rs_rlwe_pk_encrypt_dev): the same words.
+        The message rows hold this secret's ring key; they are zeroed on the host and on the device before this returns."""
+        from . import keygen
+        basebit, t = self._ring_rekey_digits(rlwe_pk.name, "rlwe", basebit, t)
+        rand_seed = os.urandom(32) if rand_seed is None else bytes(rand_seed)
+        keygen._check_seeds(rlwe_pk.mask_seed, rand_seed)
+        stdev = keygen.rlwe_default_stdev(rlwe_pk.name) if stdev is None else float(stdev)
+        mu = keygen.ring_rekey_messages(self.tlwe_key, basebit, t)
+        try:
+            if backend is None:
+                rlwe = keygen.rlwe_pk_encrypt(rlwe_pk.expand(), mu.ravel(), rand_seed, 0, stdev=stdev)
+            else:
+                import torch
+                dev = torch.from_numpy(mu.ravel()).to("cuda:%d" % backend.device)
+                try:
+                    rlwe = backend.rlwe_pk_encrypt(rlwe_pk, dev, rand_seed, 0, stdev).cpu().numpy()
+                finally:
+                    dev.zero_()
+                    torch.cuda.synchronize(backend.device)
+        finally:
+            mu[...] = 0
+        return RingRekeyKey(self.name, rlwe_pk.name, basebit, t, rlwe=rlwe)
+
     def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
         return int(np.argmax(self.decrypt_ints(logits_ct, backend=backend)))
@@ -418,13 +472,13 @@ def read_tfhe_keyset(f, secret):
     return out
 
 
-# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key, "RSR1" re-keying key; redsec_amd/host/
+# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key, "RSR1" re-keying key, "RSX1" ring re-keying key; redsec_amd/host/
 # tfhe_shim.cpp ParamHeader): magic, int32 n, N, k, l, Bgbit, ks_t, ks_basebit, then double lwe alpha min / max, tlwe alpha min / max.
 _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
 RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352,
-            "RSR1": 0x31525352}
+            "RSR1": 0x31525352, "RSX1": 0x31585352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -748,6 +802,96 @@ def read_rekey_key(f):
     if form == 0:
         return RekeyKey(src, dst, n_src, n_dst, basebit, t, mask_seed=rest[:32], body=np.frombuffer(rest[32:], np.int32).copy())
     return RekeyKey(src, dst, n_src, n_dst, basebit, t, rlwe=np.frombuffer(rest, np.int32).copy())
+
+
+class RingRekeyKey:
+    """A ring re-keying key (include/redsec_hip.h rs_ring_rekey_dev) from the ring key of a secret of set
+    src_name to a recipient's ring key of set dst_name (the same N), with the digit shape (basebit, t), t basebit <= 31. Row j < t
+    encrypts 2^(31-(j+1) basebit) S, row t the constant row. One of two payloads:
+      form "seeded"  the public 32-byte mask seed and the bodies int32 [t+1][N] of ring samples, rows 0 .. t of domains 16 / 17,
+                     under the recipient's ring key
+      form "rlwe"    the t + 1 ciphertexts int32 [t+1][2][N] of the message rows under the recipient's compact RLWE public key:
+                     already the layout the call takes
+    nbytes: what travels (seed + bodies, or the ciphertexts)."""
+
+    def __init__(self, src_name, dst_name, basebit, t, mask_seed=None, body=None, rlwe=None):
+        self.src_name, self.dst_name, self.basebit, self.t = src_name, dst_name, int(basebit), int(t)
+        assert src_name in PARAM_SETS and dst_name in PARAM_SETS, "unknown parameter set"
+        self.N = PARAM_SETS[dst_name][1]
+        assert PARAM_SETS[src_name][1] == self.N, "source and destination share the ring degree N"
+        assert 1 <= self.basebit <= 8 and self.t >= 1 and self.t * self.basebit <= 31, "basebit in 1 .. 8, t >= 1, t basebit <= 31"
+        assert (rlwe is None) != (body is None), "one payload: seeded bodies or RLWE ciphertexts"
+        self.rows = self.t + 1
+        if rlwe is None:
+            self.form, self.mask_seed, self.rlwe = "seeded", bytes(mask_seed), None
+            assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+            self.body = np.ascontiguousarray(body, np.int32).reshape(-1)
+            assert self.body.size == self.rows * self.N, "body must have (t + 1) N = %d words" % (self.rows * self.N)
+            self.body = self.body.reshape(self.rows, self.N)
+        else:
+            self.form, self.mask_seed, self.body = "rlwe", None, None
+            self.rlwe = np.ascontiguousarray(rlwe, np.int32).reshape(-1)
+            assert self.rlwe.size == self.rows * 2 * self.N, "rlwe must hold [t+1][2][N] words"
+            self.rlwe = self.rlwe.reshape(self.rows, 2, self.N)
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.body.size if self.form == "seeded" else 4 * self.rlwe.size
+
+    def expand(self):
+        """K[j] = row j: the domain-16 masks of the seed beside the bodies, or the ciphertexts as they are -> int32 [t+1][2][N], what
+        rs_ring_rekey_dev takes."""
+        from . import keygen
+        return keygen.ring_rekey_expand(self.mask_seed, self.body) if self.form == "seeded" else self.rlwe.copy()
+
+
+def write_ring_rekey_key(f, key):
+    """A ring re-keying key file (binary file object): the RS header with magic RSX1 for the destination, the same header for the
+    source, int32 basebit, int32 t, int32 form (0 seeded, 1 rlwe), then the 32-byte mask seed and the (t + 1) N int32 body words, or
+    the (t + 1) 2 N int32 words of the RLWE ciphertexts. key: RingRekeyKey."""
+    f.write(_rs_header("RSX1", key.dst_name, PARAM_SETS[key.dst_name][0]))
+    f.write(_rs_header("RSX1", key.src_name, PARAM_SETS[key.src_name][0]))
+    f.write(np.array([key.basebit, key.t, 0 if key.form == "seeded" else 1], "<i4").tobytes())
+    if key.form == "seeded":
+        f.write(key.mask_seed)
+        f.write(key.body.tobytes())
+    else:
+        f.write(key.rlwe.tobytes())
+
+
+def read_ring_rekey_key(f):
+    """-> RingRekeyKey of a ring re-keying key file. Raises ValueError for a truncated file, another magic, a parameter shape no set
+    has, rings of different degree, digits outside basebit 1 .. 8, t >= 1, t basebit <= 31, an unknown form, or a payload that is not
+    exactly the words the header promises."""
+    names = []
+    for what in ("destination", "source"):
+        raw = f.read(_RS_HEADER.itemsize)
+        if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSX1"]:
+            raise ValueError("not a ring re-keying key (RSX1) file: %s header" % what)
+        if len(raw) < _RS_HEADER.itemsize:
+            raise ValueError("truncated ring re-keying key file: short %s header" % what)
+        h = np.frombuffer(raw, _RS_HEADER)[0]
+        shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+        name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+        if name is None:
+            raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s (%s)" % (shape, what))
+        names.append(name)
+    digits, rest = f.read(12), f.read()
+    if len(digits) < 12:
+        raise ValueError("truncated ring re-keying key file: %d bytes after the headers" % len(digits))
+    basebit, t, form = (int(v) for v in np.frombuffer(digits, "<i4"))
+    dst, src = names
+    N = PARAM_SETS[dst][1]
+    if PARAM_SETS[src][1] != N:
+        raise ValueError("ring re-keying key file between rings of N = %d and N = %d" % (PARAM_SETS[src][1], N))
+    if not (1 <= basebit <= 8 and t >= 1 and t * basebit <= 31) or form not in (0, 1):
+        raise ValueError("ring re-keying key file with basebit = %d, t = %d, form = %d" % (basebit, t, form))
+    want = 32 + 4 * (t + 1) * N if form == 0 else 4 * (t + 1) * 2 * N
+    if len(rest) != want:
+        raise ValueError("truncated ring re-keying key file: %d payload bytes, expected %d" % (len(rest), want))
+    if form == 0:
+        return RingRekeyKey(src, dst, basebit, t, mask_seed=rest[:32], body=np.frombuffer(rest[32:], np.int32).copy())
+    return RingRekeyKey(src, dst, basebit, t, rlwe=np.frombuffer(rest, np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

@@ -1,5 +1,5 @@
 // rs_api_client.cpp -- key material and client-side calls of the C ABI (include/redsec_hip.h) that need no lane, no launch plan
-// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying and the packing key, device
+// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying (LWE and ring) and the packing key, device
 // decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
 // (rs::with_secret_copy; rs_keygen_dev of rs_api_keys.cpp goes through it too) and of the refusals these calls share.
 #include "rs_api_internal.h"
@@ -12,6 +12,7 @@
 #include "rs_pack.h"
 #include "rs_packkey.h"
 #include "rs_rekey.h"
+#include "rs_ring_rekey.h"
 #include "rs_rlwe.h"
 
 using rs::fail;
@@ -257,6 +258,27 @@ int rs_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* ct, size_t B, int32_t n
     return fail(RS_ERR_INVALID, "B = %zu is too large for one launch", B);
   const rs::RekeyArgs a{out, ct, rekey_key, (long)B, (int)n_src, (int)n_dst, (int)basebit, (int)t};
   RS_HIP(rs::launch_rekey(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// ring re-keying (include/redsec_hip.h; kernels of rs_ring_rekey.hip, integer arithmetic only): needs no key, the ring is the context's
+int rs_ring_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* rlwe, size_t R, const int32_t* ring_key, int32_t basebit, int32_t t,
+                      void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !rlwe || !ring_key) return fail(RS_ERR_INVALID, "null pointer");
+  if ((rc = refuse_digits(basebit, t, true)) != RS_OK) return rc;
+  if ((int64_t)t * basebit > rs::kRrMaxBits)
+    return fail(RS_ERR_INVALID, "t basebit = %d x %d passes %d bits", (int)t, (int)basebit, rs::kRrMaxBits);
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kRrMinN || N > (size_t)rs::kRrMaxN || (N & (N - 1))) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  if (R > (size_t)LONG_MAX / (2 * N * sizeof(int32_t))) return fail(RS_ERR_INVALID, "R = %zu is too large for ciphertexts of %zu bytes", R, 2 * N * sizeof(int32_t));
+  if (R == 0) return RS_OK;
+  // workgroups of the two launches: one per kRrInitThreads output words, and rs::rr_groups
+  const size_t init_per_r = 2 * N / rs::kRrInitThreads, per_r = (size_t)rs::rr_groups_per_ct((int)N, (int)t);
+  if (R > (size_t)INT32_MAX / init_per_r || R > (size_t)INT32_MAX / per_r) return fail(RS_ERR_INVALID, "R = %zu is too large for one launch", R);
+  const rs::RingRekeyArgs a{out, rlwe, ring_key, (long)R, (int)N, (int)basebit, (int)t};
+  RS_HIP(rs::launch_ring_rekey(a, (hipStream_t)stream));
   return RS_OK;
 }
 

@@ -18,6 +18,7 @@
 #include "rs_pack.h"
 #include "rs_packkey.h"
 #include "rs_rekey.h"
+#include "rs_ring_rekey.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
@@ -1504,6 +1505,60 @@ void rs_emu_rekey(const int32_t* ct_, long B, int n_src, const int32_t* rekey_ke
   }
 }
 
+// ---- ring re-keying (rs_ring_rekey_dev) through the functions of rs_ring_rekey.h ----
+uint32_t rs_emu_ring_rekey_offset(int basebit, int t) { return rs::rr_offset(basebit, t); }
+uint32_t rs_emu_ring_rekey_digit(uint32_t abar, int basebit, int j) { return rs::rr_digit(abar, basebit, j); }
+int rs_emu_ring_rekey_tile() { return rs::kRrTile; }
+int rs_emu_ring_rekey_slots() { return rs::kRrSlots; }
+long rs_emu_ring_rekey_groups(long R, int N, int t) { return rs::rr_groups(R, N, t); }
+int rs_emu_ring_rekey_window_base(int N, int k0, int c0) { return rs::rr_window_base(N, k0, c0); }
+// ring_rekey_init_kernel, then ring_rekey_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over
+// (tile, polynomial, source block, digit, ciphertext), the staged window of the key row and the block's words a_k + offset, a 4-word
+// chunk per thread and four scalar odd digits, the negated partial sums added into the output
+void rs_emu_ring_rekey(const int32_t* rlwe, long R, int N, const int32_t* ring_key, int basebit, int t, int32_t* out_) {
+  if (R <= 0) return;
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_);
+  const uint32_t* in = reinterpret_cast<const uint32_t*>(rlwe);
+  const uint32_t* key = reinterpret_cast<const uint32_t*>(ring_key);
+  for (long idx = 0; idx < R * 2 * (long)N; ++idx) {
+    const int w = (int)(idx & (2 * (long)N - 1));
+    out[idx] = (w >= N ? in[idx] : 0u) - key[rs::rr_key_offset(N, t, 0) + (size_t)w];
+  }
+  const int tiles = rs::rr_tiles(N), blocks = rs::rr_blocks(N);
+  const uint32_t off = rs::rr_offset(basebit, t), mask = (1u << basebit) - 1u;
+  std::vector<uint32_t> win((size_t)rs::kRrSlots + rs::kRrTile), sa((size_t)rs::kRrSlots);
+  for (long blk = 0; blk < rs::rr_groups(R, N, t); ++blk) {
+    long g = blk;
+    const int tile = (int)(g % tiles); g /= tiles;
+    const int poly = (int)(g & 1); g >>= 1;
+    const int sb = (int)(g % blocks); g /= blocks;
+    const int j = (int)(g % t);
+    const long r = g / t;
+    const int c0 = sb * rs::kRrSlots, k0 = tile * rs::kRrTile, wb = rs::rr_window_base(N, k0, c0);
+    const int shift = 32 - (j + 1) * basebit;
+    const uint32_t* src = in + (size_t)r * 2 * N + c0;
+    const uint32_t* p = key + rs::rr_key_offset(N, j, poly);
+    for (int x = 0; x < rs::kRrSlots + rs::kRrTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
+    for (int cc = 0; cc < rs::kRrSlots; ++cc) sa[cc] = src[cc] + off;
+    for (int th = 0; th < rs::kRrThreads; ++th) {
+      uint32_t acc[rs::kRrKpt] = {0u, 0u, 0u, 0u};
+      int c4 = th + rs::kRrSlots / 4;
+      const uint32_t* hi = &win[4 * (size_t)c4];
+      for (int q4 = 0; q4 < rs::kRrSlots / 4; ++q4) {
+        const uint32_t* av = &sa[4 * (size_t)q4];
+        const uint32_t* lo = &win[4 * (size_t)(--c4)];
+        const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        for (int b = 0; b < 4; ++b) {
+          const uint32_t d = 2u * ((av[b] >> shift) & mask) - mask;
+          for (int q = 0; q < rs::kRrKpt; ++q) acc[q] += w[4 + q - b] * d;
+        }
+        hi = lo;
+      }
+      uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0 + rs::kRrKpt * th;
+      for (int q = 0; q < rs::kRrKpt; ++q) o[q] += 0u - acc[q];
+    }
+  }
+}
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of
 // rs_audit.h, as the kernels of rs_audit.hip place them: a wave of 64 lanes per LWE sample, a workgroup of kAuThreads per bk row ----
 static std::vector<uint32_t> emu_pack_bits(const int32_t* key, int count) {

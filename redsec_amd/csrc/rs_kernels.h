@@ -188,6 +188,15 @@ struct RekeyArgs {
   int n_src, n_dst, basebit, t;
 };
 hipError_t launch_rekey(const RekeyArgs& a, hipStream_t st);
+// ring re-keying (rs_ring_rekey_dev; placement and index arithmetic of rs_ring_rekey.h)
+struct RingRekeyArgs {
+  int32_t* out;                                       // [R][2][N]
+  const int32_t* rlwe;                                // [R][2][N]
+  const int32_t* key;                                 // [t+1][2][N]: the ring re-keying key, row t the constant row
+  long R;
+  int N, basebit, t;
+};
+hipError_t launch_ring_rekey(const RingRekeyArgs& a, hipStream_t st);
 // the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev; streams and placement of rs_packkey.h): row i t + j is
 // (a, a*S + e + s_i g_j X^0), a the domain-14 words of the mask seed, e the domain-15 Gaussians of the noise seed
 struct PackKeygenArgs {

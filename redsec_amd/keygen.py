@@ -87,6 +87,19 @@ the recipient's LWE key, or the rows extracted from RLWE public-key ciphertexts 
   out[r] = (0, b_r) - sum_{i,j} d_ij(r) K[i][j], d_ij(r) = ((a_i + off of sample r) >> (32-(j+1) basebit)) & (2^basebit - 1).
   rekey_messages / rekey / rekey_sigma / rekey_default restate it.
 
+Ring re-keying (rs_ring_rekey_dev; include/redsec_hip.h): a public keyswitch from a
+ring key S to a ring key S' of the same N under a caller-supplied key [t+1][2][N]: row j < t encrypts h_j S, h_j = 2^(31-(j+1)
+basebit), row t the constant row c0 (1 + X + ... + X^(N-1)) S, c0 = (2^basebit - 1) sum_j h_j, under S'. The seeded form:
+
+  domain 16  ring re-keying mask    row j   mask seed (public)             a_j[k] = word k, k < N
+  domain 17  ring re-keying noise   row j   owner's noise seed (private)   e_j[k] = Gaussian k (words 4k .. 4k+3)
+  out[r] = (0, b_r) - K[t] - sum_j D_j(X) K[j], D_j(X) = sum_k (2 (((a_k + off) >> (32-(j+1) basebit)) & (2^basebit - 1)) -
+  (2^basebit - 1)) X^k, off = 2^(31 - t basebit): odd digits, symmetric about zero.
+
+  Domains 16 and 17 are disjoint from domains 1-15. Equal mask and noise seeds are refused. The other form is t + 1 ciphertexts of
+  rlwe_pk_encrypt (domains 12 / 13) over the same message rows. ring_rekey_messages / ring_rekey_key / ring_rekey_expand /
+  ring_rekey / ring_rekey_sigma / ring_rekey_default restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -109,6 +122,7 @@ DOMAIN_CT_MASK, DOMAIN_CT_NOISE = 7, 8
 DOMAIN_PK_SELECT = 9
 DOMAIN_RLWE_MASK, DOMAIN_RLWE_NOISE, DOMAIN_RLWE_SELECT, DOMAIN_RLWE_ENC_NOISE = 10, 11, 12, 13
 DOMAIN_PACK_MASK, DOMAIN_PACK_NOISE = 14, 15
+DOMAIN_RING_REKEY_MASK, DOMAIN_RING_REKEY_NOISE = 16, 17
 _SIGMA = b"expand 32-byte k"
 
 
@@ -842,6 +856,142 @@ def rekey_sigma(n_src, basebit, t, sigma_row):
     basebit, t = _check_digits(basebit, t)
     base = 1 << basebit
     return float(np.sqrt(n_src * t * (base - 1) * (2 * base - 1) / 6.0 * float(sigma_row) ** 2 + (n_src / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
+
+
+# ---- ring re-keying (rs_ring_rekey_dev restated) ----
+
+RING_REKEY_MAX_BITS = 31   # t basebit <= 31: h_j = 2^(31 - (j+1) basebit) is an integer
+
+
+def _check_ring_digits(basebit, t):
+    basebit, t = _check_digits(basebit, t)
+    if t * basebit > RING_REKEY_MAX_BITS:
+        raise ValueError("basebit = %d, t = %d: a ring re-keying key needs t basebit <= 31" % (basebit, t))
+    return basebit, t
+
+
+def ring_rekey_default(name, form="seeded"):
+    """(basebit, t) of a ring re-keying key to a secret of set `name`, per key form ("seeded" rows of the ring's alpha, or "rlwe" rows
+    made from an RLWE public key, alpha sqrt(N + 1)), chosen so that 8 ring_rekey_sigma stays inside the use of the re-keyed phase:
+    1/8 for default-128's +-1/8 bits, the half step 1/8192 for the networks' 1/4096-scale values. (2, 8) for default-128 in both
+    forms; seeded: (4, 5) at N = 1024 and (4, 6) at N = 4096 and 8192 (20 bits leave the rounding sqrt(N / 24) 2^-20 alone at
+    1.8e-5 on the large ring); rlwe: (2, 12) for redsec_small_v2 and redsec_small and (1, 24) for redsec_medium, whose wider row
+    noise needs the small digits. No shape reaches 8 sigma for redsec_large in the rlwe form. INTEGRATION.md section 22 has the
+    table."""
+    N = _shape(name)["N"]
+    if form not in ("seeded", "rlwe"):
+        raise ValueError("form must be 'seeded' or 'rlwe', not %r" % (form,))
+    if name == "default128":
+        return (2, 8)
+    if form == "seeded":
+        return (4, 5) if N <= 1024 else (4, 6)
+    return (2, 12) if N <= 1024 else (1, 24)
+
+
+def ring_rekey_messages(tlwe_key, basebit, t):
+    """The torus polynomials a ring re-keying key encrypts -> int32 [t+1][N]: row j < t is h_j S, h_j = 2^(31-(j+1) basebit); row t
+    is c0 (1 + X + ... + X^(N-1)) S (negacyclic), c0 = (2^basebit - 1) sum_j h_j, what the centring of the digits took away. The
+    rows hold the source secret: zero them after use."""
+    basebit, t = _check_ring_digits(basebit, t)
+    S = np.asarray(tlwe_key).ravel().astype(np.int64)
+    N = S.size
+    h = [1 << (31 - (j + 1) * basebit) for j in range(t)]
+    out = np.empty((t + 1, N), np.int64)
+    for j in range(t):
+        out[j] = S * h[j]
+    # coefficient k of (1 + X + ... + X^(N-1)) S: the bits at or below k minus the bits above k
+    below = np.cumsum(S)
+    out[t] = (2 * below - below[-1]) * (((1 << basebit) - 1) * sum(h))
+    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def ring_rekey_digits(a, basebit, t):
+    """The odd digits d_j(k) = 2 ((abar_k >> (32-(j+1) basebit)) & (2^basebit - 1)) - (2^basebit - 1), abar = a + 2^(31 - t basebit),
+    of mask polynomials a int32 [..., N] -> int64 [..., t, N]."""
+    basebit, t = _check_ring_digits(basebit, t)
+    abar = (np.asarray(a, np.int32).view(np.uint32).astype(np.int64) + (1 << (31 - t * basebit))) & 0xFFFFFFFF
+    B1 = (1 << basebit) - 1
+    return np.stack([2 * ((abar >> (32 - (j + 1) * basebit)) & B1) - B1 for j in range(t)], axis=-2)
+
+
+def _negacyclic(d, p):
+    """d(X) p(X) mod X^N + 1 for int64 d (|d| < 2^9) and words p (below 2^32) as int64: every sum stays below 2^54 -> int64 [N]."""
+    N = d.size
+    c = np.convolve(d, p)
+    out = c[:N].copy()
+    out[:N - 1] -= c[N:]
+    return out
+
+
+def ring_rekey(rlwe, key, basebit, t, unsigned=False):
+    """rs_ring_rekey_dev restated: rlwe int32 [R][2][N], key int32 [t+1][2][N] -> int32 [R][2][N], out[r] = (0, b_r) - K[t] -
+    sum_j D_j(X) K[j]. Each product is one int64 linear convolution folded negacyclically (numpy.convolve): nothing like the
+    device's tiled 32-bit multiply-adds. unsigned=True is NOT the device's convention: the unsigned digits of rs_pack_dev /
+    rs_rekey_dev over rows that encrypt 2^(32-(j+1) basebit) S, and no constant row (K[t] is ignored); kept to show what a digit
+    polynomial with a mean does to a key made from an RLWE public key."""
+    basebit, t = _check_ring_digits(basebit, t)
+    key = np.ascontiguousarray(key, np.int32)
+    assert key.ndim == 3 and key.shape[0] == t + 1 and key.shape[1] == 2, "key must hold [t+1][2][N] words"
+    N = key.shape[2]
+    rlwe = np.ascontiguousarray(rlwe, np.int32).reshape(-1, 2, N)
+    ku = key.view(np.uint32).astype(np.int64)
+    D = ring_rekey_digits(rlwe[:, 0], basebit, t)
+    if unsigned:
+        D = (D + ((1 << basebit) - 1)) >> 1
+    out = np.zeros(rlwe.shape, np.int64)
+    out[:, 1] = rlwe[:, 1].view(np.uint32)
+    if not unsigned:
+        out -= ku[t]
+    for r in range(rlwe.shape[0]):
+        for j in range(t):
+            for poly in range(2):
+                out[r, poly] = (out[r, poly] - _negacyclic(D[r, j], ku[j, poly])) & 0xFFFFFFFF
+    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def ring_rekey_mask(mask_seed, N, rows):
+    """The mask polynomials a_j of ring re-keying rows: words 0 .. N-1 of stream (16, row) of the mask seed -> int32 [R][N]."""
+    rows = np.asarray(rows, np.int64).ravel()
+    return chacha20_words(mask_seed, DOMAIN_RING_REKEY_MASK, rows.astype(np.uint64), int(N)).reshape(len(rows), int(N)).view(np.int32)
+
+
+def ring_rekey_key(src_tlwe_key, dst_tlwe_key, mask_seed, noise_seed, basebit, t, stdev):
+    """The bodies b_j = a_j*S' + e_j + m_j of the seeded ring re-keying key from the ring secret S = src_tlwe_key to S' =
+    dst_tlwe_key -> int32 [t+1][N]: a_j = ring_rekey_mask(mask_seed, N, j), e_j the N Gaussians of stream (17, j) of the private
+    noise seed, m = ring_rekey_messages(S, basebit, t). The t + 1 products by the binary S' run here (_times_binary): the key is
+    t + 1 rows, there is no device generator. Equal seeds are refused."""
+    _check_seeds(mask_seed, noise_seed)
+    basebit, t = _check_ring_digits(basebit, t)
+    S, S2 = np.asarray(src_tlwe_key).ravel(), np.asarray(dst_tlwe_key).ravel()
+    N = S.size
+    if S2.size != N:
+        raise ValueError("source and destination rings differ: N = %d and %d (crossing between rings is out of scope)" % (N, S2.size))
+    rows = np.arange(t + 1)
+    B = _times_binary(np.ascontiguousarray(ring_rekey_mask(mask_seed, N, rows)).view(np.uint32), S2)
+    mu = ring_rekey_messages(S, basebit, t)
+    with np.errstate(over="ignore"):
+        if stdev:
+            B += noise32(chacha20_words(noise_seed, DOMAIN_RING_REKEY_NOISE, rows.astype(np.uint64), 4 * N), stdev).reshape(t + 1, N).view(np.uint32)
+        B += mu.view(np.uint32)
+    mu[...] = 0
+    return B.view(np.int32)
+
+
+def ring_rekey_expand(mask_seed, body):
+    """[t+1][2][N], what rs_ring_rekey_dev takes, from the public mask seed and the bodies int32 [t+1][N]."""
+    body = np.ascontiguousarray(body, np.int32)
+    assert body.ndim == 2, "body must hold [t+1][N] words"
+    return np.ascontiguousarray(np.stack([ring_rekey_mask(mask_seed, body.shape[1], np.arange(body.shape[0])), body], axis=1))
+
+
+def ring_rekey_sigma(N, basebit, t, sigma_row):
+    """Deviation of the ring re-keying error of one coefficient, as a real in [-1/2, 1/2): the noise of the t key rows under the N
+    odd digits of each (a uniform odd digit has mean square (4^basebit - 1)/3), the constant row once, and the rounding of abar
+    to t basebit bits over the N / 2 set key bits. sigma_row is the deviation of one key row's phase per coefficient: the stdev of
+    a seeded row, stdev sqrt(N + 1) for a row made under an RLWE public key.
+      sigma^2 = (t N (4^basebit - 1)/3 + 1) sigma_row^2  +  (N/2) 2^(-2 t basebit)/12"""
+    basebit, t = _check_ring_digits(basebit, t)
+    return float(np.sqrt((t * N * (4.0 ** basebit - 1) / 3.0 + 1.0) * float(sigma_row) ** 2 + (N / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
