@@ -303,6 +303,43 @@ int rs_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* ct, size_t B, int32_t
 int rs_ring_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* rlwe, size_t R,
                       const int32_t* ring_key, int32_t basebit, int32_t t, void* stream);
 
+/* Encrypted selection: the levelled mode on packed ciphertexts. rs_ring_cmux_dev is the CMUX built on
+ * the external product RLWE x RGSW: out[r] takes the phase of d1[r] where the selector encrypts 1 and of d0[r] where it encrypts 0,
+ * and the server learns nothing of the bit. rs_ring_lookup_dev is the CMUX tree: out = table[index] for an index whose bits arrive
+ * as `depth` selectors and which the server never sees. Ciphertexts are int32[2][N] = (a, b) with phase b - a*S, as rs_pack_dev and
+ * rs_rlwe_pk_encrypt_dev make them and rs_ring_rekey_dev takes them; a plaintext row p is the trivial ciphertext (0, p).
+ * sel DEVICE int32[2l][2][N]: one RGSW sample of a bit m under the context ring's key S. Rows j < l are ring samples of zero with
+ * m h_j added to a, rows l + j have m h_j added to b, h_j = 2^(32-(j+1) basebit): the samples a bootstrapping key consists of, made
+ * by the client (client.SecretKeySet.ring_selector). Word-wise mod 2^32 with negacyclic products and the signed digits of TFHE's
+ * tGswTorus32PolynomialDecompH:
+ *   B = 2^basebit,  off = sum_j (B/2) h_j + 2^(31 - l basebit)
+ *   x = d1[r] - d0[r]                      (x = -d0[r] when d1 == NULL: an all-zero d1)
+ *   u_j(w)   = ((w + off) >> (32 - (j+1) basebit)) & (B - 1),   dig_j(w) = u_j(w) - B/2
+ *   Da_j(X)  = sum_k dig_j(x.a_k) X^k,   Db_j(X) = sum_k dig_j(x.b_k) X^k
+ *   out[r]   = d0[r] + sum_{j<l} Da_j(X) sel[j] + sum_{j<l} Db_j(X) sel[l+j]
+ * phase(out) = phase(d0) + m (phase(d1) - phase(d0)) + noise, per coefficient and CMUX of variance
+ *   sigma^2 = 2 l N (B^2 + 2)/12 sigma_row^2  +  (1 + N/2) 2^(-2 l basebit)/12
+ * (sigma_row the deviation of one selector row's phase per coefficient; a signed digit has mean square (B^2 + 2)/12; the second
+ * term is the rounding of x to l basebit bits, present where m = 1). A lookup adds `depth` of them.
+ * d0[r] and d1[r] are read at row r stride (int32[2][N] each; stride >= 1, 2 for the even and odd entries of a table); out DEVICE
+ * int32[R][2][N], contiguous, overlaps no input. The first kernel sets out = d0, so a second call into the same buffer gives the
+ * same words. N is the context's ring. Integer arithmetic only, exact: the words do not depend on how the work is tiled. Needs no
+ * loaded key. Asynchronous and ordered on `stream`; no allocation. R = 0 is a no-op that returns RS_OK.
+ * RS_ERR_INVALID: a null out, d0 or sel; basebit outside 1 .. 8; l < 1; l basebit > 31; stride = 0; an R and stride whose row
+ * arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_ring_rekey_dev does. */
+int rs_ring_cmux_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride,
+                     const int32_t* sel, int32_t basebit, int32_t l, void* stream);
+/* out DEVICE int32[2][N] = table[index] for table DEVICE int32[entries][2][N], 1 <= entries <= 2^depth, 1 <= depth <= 30, and sel
+ * DEVICE int32[depth][2l][2][N]: sample k selects on bit k of the index, least significant bit first. Entries at or past `entries`
+ * count as the all-zero ciphertext, so an index past `entries` yields an encryption of zero. Level k is one rs_ring_cmux_dev-shaped
+ * launch over the pairs (2r, 2r + 1) of the previous level with stride 2; an unpaired last row runs as a second launch with d1 =
+ * NULL, also where it is the only row of its level. scratch DEVICE int32[ceil(E/2) + ceil(E/4)][2][N], E = entries, used as two
+ * ping-pong halves; it may be NULL when depth = 1. The last level writes out. out and scratch overlap neither each other nor an
+ * input. Otherwise as rs_ring_cmux_dev, and RS_ERR_INVALID also for a null table, depth or entries out of range, and a null
+ * scratch with depth > 1. */
+int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
+                       const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
+
 /* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
  * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three
  * need no loaded key and work on every context, N = 1024 .. 8192: 32-bit integer adds, no product, no transform, no mode dependence.

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "rs_bootstrap_sparse_dev",
     "rs_rekey_dev",
     "rs_ring_rekey_dev",
+    "rs_ring_cmux_dev", "rs_ring_lookup_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -136,6 +137,8 @@ def load_library(path=None):
     L.rs_pack_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rs_ring_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
+    L.rs_ring_cmux_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
+    L.rs_ring_lookup_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
     L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
     L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
@@ -578,6 +581,71 @@ class Backend:
         if self.p.N != key.N:
             raise ValueError("the ring re-keying key is of N = %d (%s), the context's ring N = %d" % (key.N, key.dst_name, self.p.N))
         return torch.from_numpy(key.expand()).to("cuda:%d" % self.device)
+
+    # ---- encrypted selection ----
+    def _ring_selector(self, sel, basebit, l):
+        from . import keygen
+        depth = None
+        if hasattr(sel, "body"):
+            basebit, l, depth, sel = sel.basebit, sel.l, sel.depth, self.upload_ring_selector(sel)
+        if basebit is None or l is None:
+            raise ValueError("a selector given as a tensor needs explicit basebit and l")
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        per = 2 * l * 2 * self.p.N
+        assert sel.numel() and sel.numel() % per == 0, "sel must hold [depth][2l][2][N] words"
+        assert depth is None or sel.numel() == depth * per
+        return sel, basebit, l, sel.numel() // per
+
+    def ring_cmux(self, d1, d0, sel, basebit=None, l=None, stride=1, out=None):
+        """out[r] = d1[r stride] where the selector encrypts 1, d0[r stride] where it encrypts 0 (rs_ring_cmux_dev, on torch's
+        current stream) -> int32 CUDA tensor [R][2][N], R = ceil(rows of d0 / stride) (or into `out`, which overlaps no input).
+        d0, d1: int32 CUDA tensors [rows][2][N] of packed ciphertexts (Backend.pack, rlwe_pk_encrypt) or trivial ones
+        (keygen.ring_trivial); d1 = None is the all-zero ciphertext. sel: a client.RingSelector of depth 1 (uploaded on this
+        context's device: keep the tensor of upload_ring_selector for repeated calls) or an int32 CUDA tensor [2l][2][N] with
+        explicit basebit and l. Needs no loaded key."""
+        N = self.p.N
+        sel, basebit, l, depth = self._ring_selector(sel, basebit, l)
+        assert depth == 1, "ring_cmux takes one selector; ring_lookup takes a tree of them"
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride = %d is below 1" % stride)
+        assert d0.numel() % (2 * N) == 0, "d0 must hold [rows][2][N] words"
+        R = -(-(d0.numel() // (2 * N)) // stride)
+        assert d1 is None or d1.numel() >= ((R - 1) * stride + 1) * 2 * N, "d1 must hold a row for every row read of d0"
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        _check(self.L, self.L.rs_ring_cmux_dev(self.h, self._ck_dev(out), None if d1 is None else self._ck_dev(d1), self._ck_dev(d0),
+                                               R, stride, self._ck_dev(sel), basebit, l, self._stream()))
+        return out
+
+    def ring_lookup(self, table, sel, basebit=None, l=None, out=None):
+        """table[index] for the index encrypted in sel (rs_ring_lookup_dev, on torch's current stream) -> int32 CUDA tensor [2][N]
+        (or into `out`). table: int32 CUDA tensor [entries][2][N], entries <= 2^depth; sel: a client.RingSelector (uploaded on this
+        context's device) or an int32 CUDA tensor [depth][2l][2][N] with explicit basebit and l. An index at or past `entries`
+        gives an encryption of zero. The scratch of the call, ceil(E/2) + ceil(E/4) ciphertexts, is allocated here. Needs no
+        loaded key."""
+        N = self.p.N
+        sel, basebit, l, depth = self._ring_selector(sel, basebit, l)
+        assert table.numel() and table.numel() % (2 * N) == 0, "table must hold [entries][2][N] words"
+        entries = table.numel() // (2 * N)
+        if entries > 1 << depth:
+            raise ValueError("%d entries need more than the %d selectors given" % (entries, depth))
+        out = self.empty(2, N) if out is None else out
+        assert out.numel() == 2 * N, "out must hold [2][N] words"
+        first = (entries + 1) // 2
+        scratch = self.empty(first + (first + 1) // 2, 2, N) if depth > 1 else None
+        _check(self.L, self.L.rs_ring_lookup_dev(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
+                                                 basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
+        return out
+
+    def upload_ring_selector(self, sel):
+        """The expanded client.RingSelector on this context's device -> int32 CUDA tensor [depth][2l][2][N] (pass it to ring_cmux or
+        ring_lookup with sel.basebit and sel.l). The masks of the seeded rows are regenerated on the host. ValueError for a
+        selector of another ring."""
+        import torch
+        if self.p.N != sel.N:
+            raise ValueError("the selector is of N = %d (%s), the context's ring N = %d" % (sel.N, sel.name, self.p.N))
+        return torch.from_numpy(sel.expand()).to("cuda:%d" % self.device)
 
     # ---- the packing key on the device (INTEGRATION.md section 19) ----
     def _secrets(self, lwe_key, tlwe_key):

@@ -400,6 +400,32 @@ class SecretKeySet:
             mu[...] = 0
         return RingRekeyKey(self.name, rlwe_pk.name, basebit, t, rlwe=rlwe)
 
+    # encrypted selection (include/redsec_hip.h rs_ring_cmux_dev / rs_ring_lookup_dev): the bits of an
+    # index as RGSW samples under THIS secret's ring key, under which a server picks one packed ciphertext without learning which
+    def ring_selector(self, index, depth, basebit=None, l=None, mask_seed=None, noise_seed=None, stdev=None):
+        """The selector of table entry `index` for a lookup of `depth` levels (depth = 1: the bit of one CMUX) -> RingSelector: depth
+        seeded RGSW samples of 2l rows each (rows k 2l + j of the public mask seed, domains 18 / 19), sample k of bit k of the index,
+        32 + 4 N 2l depth bytes. basebit, l default to keygen.ring_cmux_default(name, depth), stdev to the set's bk_stdev (ValueError
+        where that truncates to zero: pass one). Equal seeds and an index at or past 2^depth are refused. The 2l depth products run
+        on the host: there is no device generator."""
+        from . import keygen
+        index, depth = int(index), int(depth)
+        if not 1 <= depth <= keygen.RING_LOOKUP_MAX_DEPTH:
+            raise ValueError("depth = %d is outside 1 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+        if not 0 <= index < 1 << depth:
+            raise ValueError("index = %d is outside 0 .. 2^%d - 1" % (index, depth))
+        if basebit is None or l is None:
+            d = keygen.ring_cmux_default(self.name, depth)
+            basebit, l = d[0] if basebit is None else basebit, d[1] if l is None else l
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        keygen._check_seeds(mask_seed, noise_seed)
+        stdev = keygen.rlwe_default_stdev(self.name) if stdev is None else float(stdev)
+        bits = [(index >> k) & 1 for k in range(depth)]
+        body = keygen.ring_selector_rows(bits, self.tlwe_key, mask_seed, noise_seed, basebit, l, stdev)
+        return RingSelector(self.name, self.N, depth, basebit, l, mask_seed, body)
+
     def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
         return int(np.argmax(self.decrypt_ints(logits_ct, backend=backend)))
@@ -472,13 +498,13 @@ def read_tfhe_keyset(f, secret):
     return out
 
 
-# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key, "RSR1" re-keying key, "RSX1" ring re-keying key; redsec_amd/host/
+# The backend's own key-file header ("RSK1" full cloud key, "RSS1" secret key, "RSZ1" compressed cloud key, "RSR1" re-keying key, "RSX1" ring re-keying key, "RSG1" selector; redsec_amd/host/
 # tfhe_shim.cpp ParamHeader): magic, int32 n, N, k, l, Bgbit, ks_t, ks_basebit, then double lwe alpha min / max, tlwe alpha min / max.
 _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"), ("l", "<i4"), ("Bgbit", "<i4"), ("ks_t", "<i4"),
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
 RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352,
-            "RSR1": 0x31525352, "RSX1": 0x31585352}
+            "RSR1": 0x31525352, "RSX1": 0x31585352, "RSG1": 0x31475352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -892,6 +918,70 @@ def read_ring_rekey_key(f):
     if form == 0:
         return RingRekeyKey(src, dst, basebit, t, mask_seed=rest[:32], body=np.frombuffer(rest[32:], np.int32).copy())
     return RingRekeyKey(src, dst, basebit, t, rlwe=np.frombuffer(rest, np.int32).copy())
+
+
+class RingSelector:
+    """The encrypted index of a lookup (include/redsec_hip.h rs_ring_lookup_dev; depth = 1: the bit of rs_ring_cmux_dev;
+    INTEGRATION.md section 23) under the ring key of a secret of set `name`: depth seeded RGSW samples of the digit shape
+    (basebit, l), l basebit <= 31, sample k of bit k of the index. What travels is the public 32-byte mask seed and the bodies int32
+    [depth][2l][N] of the rows k 2l + j of domains 18 / 19; nbytes = 32 + 4 N 2l depth."""
+
+    def __init__(self, name, N, depth, basebit, l, mask_seed, body):
+        self.name, self.N, self.depth, self.basebit, self.l = name, int(N), int(depth), int(basebit), int(l)
+        assert name in PARAM_SETS and PARAM_SETS[name][1] == self.N, "unknown parameter set or another ring"
+        assert 1 <= self.basebit <= 8 and self.l >= 1 and self.l * self.basebit <= 31, "basebit in 1 .. 8, l >= 1, l basebit <= 31"
+        assert 1 <= self.depth <= 30, "depth in 1 .. 30"
+        self.mask_seed = bytes(mask_seed)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        self.body = np.ascontiguousarray(body, np.int32).reshape(-1)
+        assert self.body.size == self.depth * 2 * self.l * self.N, "body must have depth 2l N = %d words" % (self.depth * 2 * self.l * self.N)
+        self.body = self.body.reshape(self.depth, 2 * self.l, self.N)
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.body.size
+
+    def expand(self):
+        """The domain-18 masks of the seed beside the bodies -> int32 [depth][2l][2][N], what rs_ring_lookup_dev takes (and
+        rs_ring_cmux_dev for depth = 1)."""
+        from . import keygen
+        return keygen.ring_selector_expand(self.mask_seed, self.body)
+
+
+def write_ring_selector(f, sel):
+    """A selector file (binary file object): the RS header with magic RSG1 for the set, int32 depth, int32 basebit, int32 l, then the
+    32-byte mask seed and the depth 2l N int32 body words. sel: RingSelector."""
+    f.write(_rs_header("RSG1", sel.name, PARAM_SETS[sel.name][0]))
+    f.write(np.array([sel.depth, sel.basebit, sel.l], "<i4").tobytes())
+    f.write(sel.mask_seed)
+    f.write(sel.body.tobytes())
+
+
+def read_ring_selector(f):
+    """-> RingSelector of a selector file. Raises ValueError for a truncated file, another magic, a parameter shape no set has, a
+    depth outside 1 .. 30, digits outside basebit 1 .. 8, l >= 1, l basebit <= 31, or a payload that is not exactly the words the
+    header promises."""
+    raw = f.read(_RS_HEADER.itemsize)
+    if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSG1"]:
+        raise ValueError("not a selector (RSG1) file")
+    if len(raw) < _RS_HEADER.itemsize:
+        raise ValueError("truncated selector file: short header")
+    h = np.frombuffer(raw, _RS_HEADER)[0]
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    if name is None:
+        raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,))
+    digits, rest = f.read(12), f.read()
+    if len(digits) < 12:
+        raise ValueError("truncated selector file: %d bytes after the header" % len(digits))
+    depth, basebit, l = (int(v) for v in np.frombuffer(digits, "<i4"))
+    if not (1 <= depth <= 30 and 1 <= basebit <= 8 and l >= 1 and l * basebit <= 31):
+        raise ValueError("selector file with depth = %d, basebit = %d, l = %d" % (depth, basebit, l))
+    N = PARAM_SETS[name][1]
+    want = 32 + 4 * depth * 2 * l * N
+    if len(rest) != want:
+        raise ValueError("truncated selector file: %d payload bytes, expected %d" % (len(rest), want))
+    return RingSelector(name, N, depth, basebit, l, rest[:32], np.frombuffer(rest[32:], np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

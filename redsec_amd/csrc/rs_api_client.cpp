@@ -1,5 +1,5 @@
 // rs_api_client.cpp -- key material and client-side calls of the C ABI (include/redsec_hip.h) that need no lane, no launch plan
-// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying (LWE and ring) and the packing key, device
+// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying (LWE and ring), encrypted selection and the packing key, device
 // decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
 // (rs::with_secret_copy; rs_keygen_dev of rs_api_keys.cpp goes through it too) and of the refusals these calls share.
 #include "rs_api_internal.h"
@@ -12,6 +12,7 @@
 #include "rs_pack.h"
 #include "rs_packkey.h"
 #include "rs_rekey.h"
+#include "rs_ring_cmux.h"
 #include "rs_ring_rekey.h"
 #include "rs_rlwe.h"
 
@@ -279,6 +280,80 @@ int rs_ring_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* rlwe, size_t R, co
   if (R > (size_t)INT32_MAX / init_per_r || R > (size_t)INT32_MAX / per_r) return fail(RS_ERR_INVALID, "R = %zu is too large for one launch", R);
   const rs::RingRekeyArgs a{out, rlwe, ring_key, (long)R, (int)N, (int)basebit, (int)t};
   RS_HIP(rs::launch_ring_rekey(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// encrypted selection (include/redsec_hip.h; kernels of rs_ring_cmux.hip, integer arithmetic only): needs no key, the ring is the
+// context's. The checks of digit shape and ring that the two calls share.
+static int ring_cmux_shape(const rs_ctx* c, int32_t basebit, int32_t l, size_t* N_) {
+  if (basebit < 1 || basebit > 8) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
+  if (l < 1) return fail(RS_ERR_INVALID, "l = %d is below 1", (int)l);
+  if ((int64_t)l * basebit > rs::kRcMaxBits)
+    return fail(RS_ERR_INVALID, "l basebit = %d x %d passes %d bits", (int)l, (int)basebit, rs::kRcMaxBits);
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kRcMinN || N > (size_t)rs::kRcMaxN || (N & (N - 1))) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  *N_ = N;
+  return RS_OK;
+}
+// R rows read at `stride`: the row arithmetic and the workgroups of the two launches (one per kRcInitThreads output words, and
+// rs::rc_groups)
+static int ring_cmux_rows(size_t R, size_t stride, size_t N, int32_t l) {
+  const size_t ct_bytes = 2 * N * sizeof(int32_t);
+  if (R > (size_t)LONG_MAX / ct_bytes || (R && stride > (size_t)LONG_MAX / ct_bytes / R))
+    return fail(RS_ERR_INVALID, "R = %zu at stride %zu is too large for ciphertexts of %zu bytes", R, stride, ct_bytes);
+  const size_t init_per_r = 2 * N / rs::kRcInitThreads, per_r = (size_t)rs::rc_groups_per_ct((int)N, (int)l);
+  if (R > (size_t)INT32_MAX / init_per_r || R > (size_t)INT32_MAX / per_r) return fail(RS_ERR_INVALID, "R = %zu is too large for one launch", R);
+  return RS_OK;
+}
+
+int rs_ring_cmux_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride, const int32_t* sel,
+                     int32_t basebit, int32_t l, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !d0 || !sel) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_cmux_shape(c, basebit, l, &N)) != RS_OK) return rc;
+  if (stride == 0) return fail(RS_ERR_INVALID, "stride = 0");
+  if ((rc = ring_cmux_rows(R, stride, N, l)) != RS_OK) return rc;
+  if (R == 0) return RS_OK;
+  const rs::RingCmuxArgs a{out, d1, d0, sel, (long)R, (long)stride, (int)N, (int)basebit, (int)l};
+  RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// the CMUX tree: level k pairs rows (2r, 2r + 1) of the previous level under selector k; an unpaired last row meets the all-zero
+// ciphertext. The levels alternate between the two halves of scratch, ceil(E / 2) and ceil(E / 4) rows; the last one writes out.
+int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
+                       int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !table || !sel) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_cmux_shape(c, basebit, l, &N)) != RS_OK) return rc;
+  if (depth < 1 || depth > rs::kRcMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 1 .. %d", (int)depth, rs::kRcMaxDepth);
+  if (entries < 1 || entries > ((size_t)1 << depth))
+    return fail(RS_ERR_INVALID, "entries = %zu is outside 1 .. 2^%d", entries, (int)depth);
+  if (depth > 1 && !scratch) return fail(RS_ERR_INVALID, "null scratch with depth = %d", (int)depth);
+  if ((rc = ring_cmux_rows(entries / 2 + 1, 2, N, l)) != RS_OK) return rc;     // level 0, the largest launch: entries / 2 pairs at stride 2
+  const size_t ct = 2 * N, sel_words = (size_t)2 * l * ct;
+  int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::rc_level_rows((long)entries) * ct : nullptr};
+  const int32_t* in = table;
+  size_t rows = entries;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = k == depth - 1 ? out : half[k & 1];
+    const size_t pairs = rows / 2;
+    const int32_t* s = sel + (size_t)k * sel_words;
+    if (pairs) {
+      const rs::RingCmuxArgs a{o, in + ct, in, s, (long)pairs, 2, (int)N, (int)basebit, (int)l};
+      RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
+    }
+    if (rows & 1) {
+      const rs::RingCmuxArgs a{o + pairs * ct, nullptr, in + (rows - 1) * ct, s, 1, 1, (int)N, (int)basebit, (int)l};
+      RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
+    }
+    in = o;
+    rows = (size_t)rs::rc_level_rows((long)rows);
+  }
   return RS_OK;
 }
 

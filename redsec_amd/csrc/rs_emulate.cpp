@@ -18,6 +18,7 @@
 #include "rs_pack.h"
 #include "rs_packkey.h"
 #include "rs_rekey.h"
+#include "rs_ring_cmux.h"
 #include "rs_ring_rekey.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
@@ -1557,6 +1558,79 @@ void rs_emu_ring_rekey(const int32_t* rlwe, long R, int N, const int32_t* ring_k
       uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0 + rs::kRrKpt * th;
       for (int q = 0; q < rs::kRrKpt; ++q) o[q] += 0u - acc[q];
     }
+  }
+}
+
+// ---- encrypted selection (rs_ring_cmux_dev, rs_ring_lookup_dev) through the functions of rs_ring_cmux.h ----
+uint32_t rs_emu_ring_cmux_offset(int basebit, int l) { return rs::rc_offset(basebit, l); }
+uint32_t rs_emu_ring_cmux_digit(uint32_t xbar, int basebit, int j) { return rs::rc_digit(xbar, basebit, j); }
+long rs_emu_ring_cmux_groups(long R, int N, int l) { return rs::rc_groups(R, N, l); }
+long rs_emu_ring_lookup_scratch_rows(long entries) { return rs::rc_scratch_rows(entries); }
+// ring_cmux_init_kernel, then ring_cmux_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over
+// (tile, polynomial, source block, selector row, ciphertext), the staged window of the selector row and the block's words
+// d1 - d0 + offset (-d0 + offset under a null d1), a 4-word chunk per thread and four scalar signed digits, the partial sums added
+// into the output
+void rs_emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long stride, int N, const int32_t* sel_, int basebit, int l,
+                      int32_t* out_) {
+  if (R <= 0) return;
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_);
+  const uint32_t* d1 = reinterpret_cast<const uint32_t*>(d1_);
+  const uint32_t* d0 = reinterpret_cast<const uint32_t*>(d0_);
+  const uint32_t* sel = reinterpret_cast<const uint32_t*>(sel_);
+  const long per = 2 * (long)N;
+  for (long idx = 0; idx < R * per; ++idx) out[idx] = d0[(size_t)(idx / per) * (size_t)stride * (size_t)per + (size_t)(idx % per)];
+  const int tiles = rs::rc_tiles(N), blocks = rs::rc_blocks(N);
+  const uint32_t off = rs::rc_offset(basebit, l), mask = (1u << basebit) - 1u, half = 1u << (basebit - 1);
+  std::vector<uint32_t> win((size_t)rs::kRcSlots + rs::kRcTile), sx((size_t)rs::kRcSlots);
+  for (long blk = 0; blk < rs::rc_groups(R, N, l); ++blk) {
+    long g = blk;
+    const int tile = (int)(g % tiles); g /= tiles;
+    const int poly = (int)(g & 1); g >>= 1;
+    const int sb = (int)(g % blocks); g /= blocks;
+    const int jr = (int)(g % (2 * l));
+    const long r = g / (2 * l);
+    const int j = jr < l ? jr : jr - l, spoly = jr < l ? 0 : 1;
+    const int c0 = sb * rs::kRcSlots, k0 = tile * rs::kRcTile, wb = rs::rc_window_base(N, k0, c0);
+    const int shift = 32 - (j + 1) * basebit;
+    const size_t src_at = ((size_t)r * (size_t)stride * 2 + (size_t)spoly) * (size_t)N + (size_t)c0;
+    const uint32_t* p = sel + rs::rc_sel_offset(N, jr, poly);
+    for (int x = 0; x < rs::kRcSlots + rs::kRcTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
+    for (int cc = 0; cc < rs::kRcSlots; ++cc) sx[cc] = (d1 ? d1[src_at + cc] : 0u) - d0[src_at + cc] + off;
+    for (int th = 0; th < rs::kRcThreads; ++th) {
+      uint32_t acc[rs::kRcKpt] = {0u, 0u, 0u, 0u};
+      int c4 = th + rs::kRcSlots / 4;
+      const uint32_t* hi = &win[4 * (size_t)c4];
+      for (int q4 = 0; q4 < rs::kRcSlots / 4; ++q4) {
+        const uint32_t* xv = &sx[4 * (size_t)q4];
+        const uint32_t* lo = &win[4 * (size_t)(--c4)];
+        const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        for (int b = 0; b < 4; ++b) {
+          const uint32_t d = ((xv[b] >> shift) & mask) - half;
+          for (int q = 0; q < rs::kRcKpt; ++q) acc[q] += w[4 + q - b] * d;
+        }
+        hi = lo;
+      }
+      uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0 + rs::kRcKpt * th;
+      for (int q = 0; q < rs::kRcKpt; ++q) o[q] += acc[q];
+    }
+  }
+}
+// rs_ring_lookup_dev's levels as the host code orders them: pairs at stride 2, an unpaired last row against the null d1, the two
+// halves of scratch in turn, the last level into out
+void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
+                        int32_t* scratch, int32_t* out) {
+  const size_t ct = 2 * (size_t)N, sel_words = (size_t)2 * l * ct;
+  int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::rc_level_rows(entries) * ct : nullptr};
+  const int32_t* in = table;
+  long rows = entries;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = k == depth - 1 ? out : half[k & 1];
+    const long pairs = rows / 2;
+    const int32_t* s = sel + (size_t)k * sel_words;
+    if (pairs) rs_emu_ring_cmux(in + ct, in, pairs, 2, N, s, basebit, l, o);
+    if (rows & 1) rs_emu_ring_cmux(nullptr, in + (size_t)(rows - 1) * ct, 1, 1, N, s, basebit, l, o + (size_t)pairs * ct);
+    in = o;
+    rows = rs::rc_level_rows(rows);
   }
 }
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of

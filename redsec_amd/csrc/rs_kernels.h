@@ -197,6 +197,16 @@ struct RingRekeyArgs {
   int N, basebit, t;
 };
 hipError_t launch_ring_rekey(const RingRekeyArgs& a, hipStream_t st);
+// encrypted selection (rs_ring_cmux_dev, rs_ring_lookup_dev; placement and index arithmetic of rs_ring_cmux.h)
+struct RingCmuxArgs {
+  int32_t* out;                                       // [R][2][N], contiguous
+  const int32_t* d1;                                  // row r at d1 + r stride 2 N; null: the all-zero ciphertext
+  const int32_t* d0;                                  // row r at d0 + r stride 2 N
+  const int32_t* sel;                                 // [2l][2][N]: one RGSW sample
+  long R, stride;
+  int N, basebit, l;
+};
+hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st);
 // the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev; streams and placement of rs_packkey.h): row i t + j is
 // (a, a*S + e + s_i g_j X^0), a the domain-14 words of the mask seed, e the domain-15 Gaussians of the noise seed
 struct PackKeygenArgs {

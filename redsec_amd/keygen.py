@@ -100,6 +100,20 @@ basebit), row t the constant row c0 (1 + X + ... + X^(N-1)) S, c0 = (2^basebit -
   rlwe_pk_encrypt (domains 12 / 13) over the same message rows. ring_rekey_messages / ring_rekey_key / ring_rekey_expand /
   ring_rekey / ring_rekey_sigma / ring_rekey_default restate it.
 
+Encrypted selection (rs_ring_cmux_dev, rs_ring_lookup_dev; include/redsec_hip.h): the CMUX of two ring
+ciphertexts under an RGSW sample [2l][2][N] of a bit m under the ring key S, and the CMUX tree over a table under `depth` of them.
+Row j < l of a sample is a ring sample of zero with m h_j added to a, row l + j has m h_j added to b, h_j = 2^(32-(j+1) basebit).
+The seeded form, row = k 2l + j for sample k (bit k of the index, least significant first):
+
+  domain 18  selector mask    row   mask seed (public)              a[i] = word i, i < N (the a the server uses)
+  domain 19  selector noise   row   client's noise seed (private)   e[i] = Gaussian i (words 4i .. 4i+3)
+  body of row j < l: a*S + e - m h_j S (so that (a - m h_j, body) is a sample of zero); of row l + j: a*S + e + m h_j.
+  out = d0 + sum_j Da_j(X) sel[j] + sum_j Db_j(X) sel[l+j], the digits dig_j(w) = (((w + off) >> (32-(j+1) basebit)) & (B - 1)) -
+  B/2 of x = d1 - d0, B = 2^basebit, off = sum_j (B/2) h_j + 2^(31 - l basebit): signed, TFHE's tGswTorus32PolynomialDecompH.
+
+  Domains 18 and 19 are disjoint from domains 1-17. Equal mask and noise seeds are refused. ring_cmux_digits / ring_cmux /
+  ring_lookup / ring_selector_rows / ring_selector_expand / ring_trivial / ring_cmux_sigma / ring_cmux_default restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -123,6 +137,7 @@ DOMAIN_PK_SELECT = 9
 DOMAIN_RLWE_MASK, DOMAIN_RLWE_NOISE, DOMAIN_RLWE_SELECT, DOMAIN_RLWE_ENC_NOISE = 10, 11, 12, 13
 DOMAIN_PACK_MASK, DOMAIN_PACK_NOISE = 14, 15
 DOMAIN_RING_REKEY_MASK, DOMAIN_RING_REKEY_NOISE = 16, 17
+DOMAIN_RING_SELECTOR_MASK, DOMAIN_RING_SELECTOR_NOISE = 18, 19
 _SIGMA = b"expand 32-byte k"
 
 
@@ -992,6 +1007,162 @@ def ring_rekey_sigma(N, basebit, t, sigma_row):
       sigma^2 = (t N (4^basebit - 1)/3 + 1) sigma_row^2  +  (N/2) 2^(-2 t basebit)/12"""
     basebit, t = _check_ring_digits(basebit, t)
     return float(np.sqrt((t * N * (4.0 ** basebit - 1) / 3.0 + 1.0) * float(sigma_row) ** 2 + (N / 2.0) * 2.0 ** (-2 * t * basebit) / 12.0))
+
+
+# ---- encrypted selection (rs_ring_cmux_dev / rs_ring_lookup_dev restated) ----
+
+RING_CMUX_MAX_BITS = 31    # l basebit <= 31: the half step 2^(31 - l basebit) is an integer
+RING_LOOKUP_MAX_DEPTH = 30
+RING_CMUX_USE = 1.0 / 8192   # the half step of the networks' 1/4096-scale values: what 8 sigma has to stay inside
+
+
+def _check_cmux_digits(basebit, l):
+    basebit, l = int(basebit), int(l)
+    if not (1 <= basebit <= 8 and l >= 1 and l * basebit <= RING_CMUX_MAX_BITS):
+        raise ValueError("basebit = %d, l = %d: basebit must lie in 1 .. 8, l >= 1 and l basebit <= 31" % (basebit, l))
+    return basebit, l
+
+
+def ring_cmux_offset(basebit, l):
+    """off = sum_j (B/2) h_j + 2^(31 - l basebit): w + off puts every digit B/2 above the signed one and rounds to nearest."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    return (sum(1 << (31 - j * basebit) for j in range(l)) + (1 << (31 - l * basebit))) & 0xFFFFFFFF
+
+
+def ring_cmux_digits(x, basebit, l):
+    """The signed digits dig_j(w) = (((w + off) >> (32-(j+1) basebit)) & (B - 1)) - B/2 of words x int32 [..., N] -> int64
+    [..., l, N], each in -B/2 .. B/2 - 1; sum_j dig_j h_j = w rounded to l basebit bits (mod 2^32)."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    xbar = (np.asarray(x, np.int32).view(np.uint32).astype(np.int64) + ring_cmux_offset(basebit, l)) & 0xFFFFFFFF
+    B = 1 << basebit
+    return np.stack([((xbar >> (32 - (j + 1) * basebit)) & (B - 1)) - B // 2 for j in range(l)], axis=-2)
+
+
+def ring_cmux(d1, d0, sel, basebit, l):
+    """rs_ring_cmux_dev restated: d0, d1 int32 [R][2][N] (d1 = None: all zero), sel int32 [2l][2][N] -> int32 [R][2][N], out[r] =
+    d0[r] + sum_j Da_j(X) sel[j] + sum_j Db_j(X) sel[l+j] over the digits of d1[r] - d0[r]. Each product is one int64 linear
+    convolution folded negacyclically (numpy.convolve): nothing like the device's tiled 32-bit multiply-adds. A stride is the
+    caller's slice (d0[::2], d1[1::2])."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    sel = np.ascontiguousarray(sel, np.int32)
+    assert sel.ndim == 3 and sel.shape[0] == 2 * l and sel.shape[1] == 2, "sel must hold [2l][2][N] words"
+    N = sel.shape[2]
+    d0 = np.ascontiguousarray(d0, np.int32).reshape(-1, 2, N)
+    with np.errstate(over="ignore"):
+        x = (np.uint32(0) - d0.view(np.uint32)) if d1 is None else (np.ascontiguousarray(d1, np.int32).reshape(-1, 2, N).view(np.uint32) - d0.view(np.uint32))
+    assert x.shape == d0.shape, "d1 and d0 must hold the same number of ciphertexts"
+    D = ring_cmux_digits(x.view(np.int32), basebit, l)            # [R][2][l][N]
+    su = sel.view(np.uint32).astype(np.int64)
+    out = d0.view(np.uint32).astype(np.int64)
+    for r in range(d0.shape[0]):
+        for jr in range(2 * l):
+            for poly in range(2):
+                out[r, poly] = (out[r, poly] + _negacyclic(D[r, jr // l, jr % l], su[jr, poly])) & 0xFFFFFFFF
+    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def ring_lookup(table, sel, basebit, l):
+    """rs_ring_lookup_dev restated: table int32 [entries][2][N], sel int32 [depth][2l][2][N], entries <= 2^depth -> int32 [2][N]:
+    level k is ring_cmux over the pairs (2r, 2r + 1) of the previous level under sel[k]; an unpaired last row meets d1 = None."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    sel = np.ascontiguousarray(sel, np.int32)
+    assert sel.ndim == 4 and sel.shape[1:3] == (2 * l, 2), "sel must hold [depth][2l][2][N] words"
+    depth, N = sel.shape[0], sel.shape[3]
+    rows = np.ascontiguousarray(table, np.int32).reshape(-1, 2, N)
+    if not (1 <= depth <= RING_LOOKUP_MAX_DEPTH and 1 <= rows.shape[0] <= 1 << depth):
+        raise ValueError("depth = %d, entries = %d: depth must lie in 1 .. 30 and entries in 1 .. 2^depth" % (depth, rows.shape[0]))
+    for k in range(depth):
+        pairs = rows.shape[0] // 2
+        nxt = [ring_cmux(rows[1:2 * pairs:2], rows[0:2 * pairs:2], sel[k], basebit, l)] if pairs else []
+        if rows.shape[0] & 1:
+            nxt.append(ring_cmux(None, rows[-1:], sel[k], basebit, l))
+        rows = np.concatenate(nxt)
+    return rows[0]
+
+
+def ring_trivial(values):
+    """Plaintext torus polynomials int32 [..., N] as trivial ring ciphertexts (0, p) -> int32 [..., 2, N]: the rows of a server-held
+    plaintext table."""
+    p = np.ascontiguousarray(values, np.int32)
+    return np.ascontiguousarray(np.stack([np.zeros_like(p), p], axis=-2))
+
+
+def ring_selector_mask(mask_seed, N, rows):
+    """The mask polynomials of selector rows: words 0 .. N-1 of stream (18, row) of the mask seed -> int32 [R][N]."""
+    rows = np.asarray(rows, np.int64).ravel()
+    return chacha20_words(mask_seed, DOMAIN_RING_SELECTOR_MASK, rows.astype(np.uint64), int(N)).reshape(len(rows), int(N)).view(np.int32)
+
+
+def ring_selector_rows(bits, tlwe_key, mask_seed, noise_seed, basebit, l, stdev):
+    """The bodies of the seeded RGSW samples of `bits` (0 / 1, one sample each) under the ring secret -> int32 [depth][2l][N]. Row
+    k 2l + j: a = ring_selector_mask(mask_seed, N, row), e the N Gaussians of stream (19, row) of the private noise seed; the body is
+    a*S + e - m h_j S for j < l and a*S + e + m h_j (coefficient 0) for row l + j, h_j = 2^(32-(j+1) basebit). The products by the
+    binary S run here (_times_binary): there is no device generator. Equal seeds are refused."""
+    _check_seeds(mask_seed, noise_seed)
+    basebit, l = _check_cmux_digits(basebit, l)
+    bits = np.asarray(bits, np.int64).ravel()
+    assert bits.size >= 1 and ((bits == 0) | (bits == 1)).all(), "bits must be 0 / 1"
+    S = np.asarray(tlwe_key).ravel()
+    N, depth = S.size, bits.size
+    rows = np.arange(depth * 2 * l)
+    B = _times_binary(np.ascontiguousarray(ring_selector_mask(mask_seed, N, rows)).view(np.uint32), S)
+    with np.errstate(over="ignore"):
+        if stdev:
+            B += noise32(chacha20_words(noise_seed, DOMAIN_RING_SELECTOR_NOISE, rows.astype(np.uint64), 4 * N), stdev).reshape(len(rows), N).view(np.uint32)
+        B = B.reshape(depth, 2 * l, N)
+        Su = (S.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+        for k in np.flatnonzero(bits):
+            for j in range(l):
+                h = np.uint32(1 << (32 - (j + 1) * basebit))
+                B[k, j] -= h * Su
+                B[k, l + j, 0] += h
+    return B.view(np.int32)
+
+
+def ring_selector_expand(mask_seed, body):
+    """[depth][2l][2][N], what rs_ring_lookup_dev takes (rs_ring_cmux_dev: one sample of it), from the public mask seed and the
+    bodies int32 [depth][2l][N]."""
+    body = np.ascontiguousarray(body, np.int32)
+    assert body.ndim == 3, "body must hold [depth][2l][N] words"
+    depth, rows, N = body.shape
+    mask = ring_selector_mask(mask_seed, N, np.arange(depth * rows)).reshape(depth, rows, N)
+    return np.ascontiguousarray(np.stack([mask, body], axis=2))
+
+
+def ring_cmux_sigma(N, basebit, l, sigma_row, depth=1, bit=1):
+    """Deviation of the error of one coefficient after `depth` CMUXes (a lookup of that depth), as a real in [-1/2, 1/2): the noise
+    of the 2l selector rows under the N signed digits of each (a uniform digit of -B/2 .. B/2 - 1 has mean square (B^2 + 2)/12),
+    and the rounding of x to l basebit bits on its own coefficient and over the N / 2 set key bits. sigma_row is the deviation
+    of one selector row's phase per coefficient.
+      sigma^2 = depth (2 l N (B^2 + 2)/12 sigma_row^2  +  (1 + N/2) 2^(-2 l basebit)/12)
+    The rounding reaches the phase multiplied by the selected bit: the formula is that of a selector of 1 (and of a lookup whose
+    index has every bit set), the larger of the two. bit=0 leaves the second term out: the error under a selector of 0."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    B = 2.0 ** basebit
+    rounding = (1.0 + N / 2.0) * 2.0 ** (-2 * l * basebit) / 12.0 if bit else 0.0
+    return float(np.sqrt(int(depth) * (2.0 * l * N * (B * B + 2.0) / 12.0 * float(sigma_row) ** 2 + rounding)))
+
+
+def ring_selector_default_stdev(name):
+    """The deviation of a selector row by default: the set's rlwe_default_stdev, or 2^-31 where that is refused."""
+    try:
+        return rlwe_default_stdev(name)
+    except ValueError:
+        return MIN_STDEV
+
+
+def ring_cmux_default(name, depth=1):
+    """(basebit, l) of a selector for a lookup of `depth` levels on set `name`: the cheapest shape, meaning the smallest l (the work
+    is 2l rows) and for that l the basebit of the smallest ring_cmux_sigma, with l basebit <= 31, for which 8 ring_cmux_sigma stays
+    inside the half step 1/8192 of the networks' 1/4096-scale values at rows of ring_selector_default_stdev(name). ValueError
+    where no shape reaches it (INTEGRATION.md section 23 lists those)."""
+    N, stdev = _shape(name)["N"], ring_selector_default_stdev(name)
+    for l in range(1, RING_CMUX_MAX_BITS + 1):
+        fits = [(ring_cmux_sigma(N, b, l, stdev, depth), b) for b in range(1, 9) if b * l <= RING_CMUX_MAX_BITS]
+        fits = [f for f in fits if 8 * f[0] <= RING_CMUX_USE]
+        if fits:
+            return (min(fits)[1], l)
+    raise ValueError("no (basebit, l) keeps 8 sigma inside 1/8192 on %s at depth %d" % (name, depth))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
