@@ -340,6 +340,41 @@ int rs_ring_cmux_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t
 int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
                        const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
 
+/* Circuit bootstrapping (CGGI17 section 4): the selectors of rs_ring_cmux_dev / rs_ring_lookup_dev made
+ * on the server from LWE bits it computed itself. rs_ring_selector_dev is the step in the middle, a keyswitch from LWE samples to
+ * ring samples under two key families, one of them private (the message multiplied by -S(X)). Word-wise mod 2^32 with the
+ * unsigned rounding digits of rs_pack_dev / rs_rekey_dev:
+ *   h_j  = 2^(32-(j+1) basebit)                      l basebit <= 31, so h_j/2 is an integer
+ *   ct[k l + j] = (a, b), n_src-dimensional: the bootstrap of bit k at level j, phase +-h_j/2
+ *   x    = (a_0 .. a_{n_src-1}, b + h_j/2)           n_src + 1 coordinates, phase = -sum_i x_i sg_i, sg = (s, -1)
+ *   K[f][i][q]  = ring sample under S of  M_f sg_i 2^(32-(q+1) ks_basebit),   M_1 = 1 (X^0),  M_0 = -S(X)
+ *   d_iq = ((x_i + off) >> (32-(q+1) ks_basebit)) & (2^ks_basebit - 1),   off = 2^(31 - ks_t ks_basebit)  (0 at 32 bits)
+ *   sel[k][f l + j] = - sum_{i <= n_src, q < ks_t} d_iq K[f][i][q]                    f = 0, 1
+ * sel DEVICE int32[depth][2l][2][N], the format rs_ring_cmux_dev / rs_ring_lookup_dev read: rows j < l have phase -m h_j S + noise,
+ * rows l + j have phase m h_j at coefficient 0 and noise elsewhere (m the bit, 1 for a phase of +h_j/2). ct DEVICE
+ * int32[depth l][n_src+1]; sel_key DEVICE int32[2][n_src+1][ks_t][2][N], 16-byte aligned (client.SecretKeySet.selector_key);
+ * sel overlaps no input. n_src is an argument, as in rs_rekey_dev: the context's n (after rs_bootstrap_lut_dev) or N (extracted
+ * samples before the LWE keyswitch); N is the context's ring, 1024 .. 8192. Per coefficient the keyswitch adds an error of variance
+ *   (n_src + 1) ks_t (2^ks_basebit - 1)(2^(ks_basebit+1) - 1)/6 sigma_k^2  +  rho (1 + n_src/2) 2^(-2 ks_t ks_basebit)/12
+ * (sigma_k the deviation of a key row; rho = 1 where the message sits: coefficient 0 of rows l + j and the coefficients of rows
+ * j < l at which S has a bit, 0 elsewhere), beside the bootstrap's own noise, which reaches the same coefficients.
+ * Integer arithmetic only, exact: the words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered
+ * on `stream`; no allocation. depth = 0 is a no-op that returns RS_OK. A second call into the same buffer gives the same words.
+ * RS_ERR_INVALID: a null sel, ct or sel_key; basebit or ks_basebit outside 1 .. 8; l < 1; l basebit > 31; ks_t < 1; ks_t ks_basebit >
+ * 32; depth outside 0 .. 30; n_src outside 1 .. 65536; a misaligned sel_key; row arithmetic that overflows or a grid past one
+ * launch. Without a device or context it fails as rs_pack_dev does. */
+int rs_ring_selector_dev(rs_ctx* ctx, int32_t* sel, const int32_t* ct, int32_t depth, int32_t basebit, int32_t l,
+                         int32_t n_src, const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream);
+/* The composed call: bits DEVICE int32[depth][n+1] at +-1/8 under the context's loaded key (m = 1 is a phase of +1/8) become sel
+ * DEVICE int32[depth][2l][2][N]. On the stream: each bit is replicated l times (rs_gather_rows_dev), ONE rs_bootstrap_lut_dev launch
+ * takes the depth l rows, row k l + j against the constant test polynomial h_j/2, and rs_ring_selector_dev switches the results
+ * from n_src = n. scratch DEVICE int32[l N + depth l (2 (n + 1) + 1)]: the l test polynomials, the row index of the gather, the
+ * replicated bits and their bootstraps; it overlaps neither sel nor an input. Needs a loaded evaluation key (RS_ERR_STATE without
+ * one); all three arithmetic modes, with the certificate and mode rules of the other bootstrapped calls. Otherwise as
+ * rs_ring_selector_dev, and RS_ERR_INVALID also for a null bits or scratch. */
+int rs_circuit_bootstrap_dev(rs_ctx* ctx, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
+                             const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream);
+
 /* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
  * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three
  * need no loaded key and work on every context, N = 1024 .. 8192: 32-bit integer adds, no product, no transform, no mode dependence.

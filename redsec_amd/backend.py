@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "rs_rekey_dev",
     "rs_ring_rekey_dev",
     "rs_ring_cmux_dev", "rs_ring_lookup_dev",
+    "rs_ring_selector_dev", "rs_circuit_bootstrap_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -139,6 +140,8 @@ def load_library(path=None):
     L.rs_ring_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_ring_cmux_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_ring_lookup_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.rs_ring_selector_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
+    L.rs_circuit_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
     L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
     L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
@@ -646,6 +649,71 @@ class Backend:
         if self.p.N != sel.N:
             raise ValueError("the selector is of N = %d (%s), the context's ring N = %d" % (sel.N, sel.name, self.p.N))
         return torch.from_numpy(sel.expand()).to("cuda:%d" % self.device)
+
+    # ---- circuit bootstrapping ----
+    def upload_selector_key(self, key):
+        """The expanded client.SelectorKey on this context's device -> int32 CUDA tensor [2][n+1][ks_t][2][N] (pass it to
+        ring_selector or circuit_bootstrap with key.ks_basebit and key.ks_t). The masks of the seeded rows are regenerated on the
+        host. ValueError for a key of another ring."""
+        import torch
+        if self.p.N != key.N:
+            raise ValueError("the selector key is of N = %d (%s), the context's ring N = %d" % (key.N, key.name, self.p.N))
+        return torch.from_numpy(key.expand()).to("cuda:%d" % self.device)
+
+    def _selector_key(self, key, ks_basebit, ks_t, n_src):
+        from . import keygen
+        if hasattr(key, "body"):
+            if key.n != n_src:
+                raise ValueError("the selector key is of n = %d, the samples of n_src = %d" % (key.n, n_src))
+            ks_basebit, ks_t, key = key.ks_basebit, key.ks_t, self.upload_selector_key(key)
+        if ks_basebit is None or ks_t is None:
+            raise ValueError("a selector key given as a tensor needs explicit ks_basebit and ks_t")
+        ks_basebit, ks_t = keygen._check_selector_digits(ks_basebit, ks_t)
+        assert key.numel() == 2 * (n_src + 1) * ks_t * 2 * self.p.N, "key must hold [2][n_src+1][ks_t][2][N] words"
+        return key, ks_basebit, ks_t
+
+    def ring_selector(self, ct, basebit, l, key, ks_basebit=None, ks_t=None, n_src=None, out=None):
+        """The selector keyswitch (rs_ring_selector_dev, on torch's current stream): ct int32 CUDA tensor [depth l][n_src+1], row k l
+        + j the bootstrap of bit k at level j with phase +-h_j/2 -> int32 CUDA tensor [depth][2l][2][N], what ring_cmux and
+        ring_lookup take (or into `out`, which overlaps no input). key: a client.SelectorKey (uploaded on this context's device:
+        keep the tensor of upload_selector_key for repeated calls) or an int32 CUDA tensor [2][n_src+1][ks_t][2][N] with explicit
+        ks_basebit and ks_t. n_src defaults to the last dimension of ct less one. Needs no loaded key."""
+        from . import keygen
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        n_src = ct.shape[-1] - 1 if n_src is None else int(n_src)
+        if not 1 <= n_src <= keygen.SELECTOR_MAX_SRC:
+            raise ValueError("n_src = %d is outside 1 .. %d" % (n_src, keygen.SELECTOR_MAX_SRC))
+        key, ks_basebit, ks_t = self._selector_key(key, ks_basebit, ks_t, n_src)
+        assert ct.numel() % ((n_src + 1) * l) == 0, "ct must hold [depth l][n_src+1] words"
+        depth = ct.numel() // ((n_src + 1) * l)
+        if depth > keygen.RING_LOOKUP_MAX_DEPTH:
+            raise ValueError("depth = %d is outside 0 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+        out = self.empty(depth, 2 * l, 2, self.p.N) if out is None else out
+        assert out.numel() == depth * 2 * l * 2 * self.p.N, "out must hold [depth][2l][2][N] words"
+        if depth:
+            _check(self.L, self.L.rs_ring_selector_dev(self.h, self._ck_dev(out), self._ck_dev(ct), depth, basebit, l, n_src,
+                                                       self._ck_dev(key), ks_basebit, ks_t, self._stream()))
+        return out
+
+    def circuit_bootstrap(self, bits, basebit, l, key, ks_basebit=None, ks_t=None, out=None):
+        """Selectors from bits the server computed (rs_circuit_bootstrap_dev, on torch's current stream): bits int32 CUDA tensor
+        [depth][n+1] at +-1/8 under the loaded key -> int32 CUDA tensor [depth][2l][2][N] for ring_cmux / ring_lookup, selector k
+        of bit k (or into `out`). key as in ring_selector, of the context's n. The scratch of the call is allocated here. Needs a
+        loaded evaluation key."""
+        from . import keygen
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        key, ks_basebit, ks_t = self._selector_key(key, ks_basebit, ks_t, self.p.n)
+        assert bits.numel() % self.W == 0, "bits must hold [depth][n+1] words"
+        depth = bits.numel() // self.W
+        if depth > keygen.RING_LOOKUP_MAX_DEPTH:
+            raise ValueError("depth = %d is outside 0 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+        out = self.empty(depth, 2 * l, 2, self.p.N) if out is None else out
+        assert out.numel() == depth * 2 * l * 2 * self.p.N, "out must hold [depth][2l][2][N] words"
+        if depth:
+            scratch = self.empty(l * self.p.N + depth * l * (2 * self.W + 1))
+            _check(self.L, self.L.rs_circuit_bootstrap_dev(self.h, self._ck_dev(out), self._ck_dev(bits), depth, basebit, l,
+                                                           self._ck_dev(key), ks_basebit, ks_t, self._ck_dev(scratch), self._stream()))
+        return out
 
     # ---- the packing key on the device (INTEGRATION.md section 19) ----
     def _secrets(self, lwe_key, tlwe_key):

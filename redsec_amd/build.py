@@ -53,6 +53,9 @@ HIP_OBJECTS = [
     ("rs_ring_rekey", "rs_ring_rekey.hip", []),
     # encrypted selection (ring_cmux_init_kernel, ring_cmux_kernel), likewise in an object of their own; integer-only sources, as rs_pack
     ("rs_ring_cmux", "rs_ring_cmux.hip", []),
+    # the selector keyswitch of circuit bootstrapping (ring_selector_init_kernel, ring_selector_kernel, circuit_prepare_kernel),
+    # likewise in an object of its own; integer-only sources, as rs_pack
+    ("rs_ring_selector", "rs_ring_selector.hip", []),
     # the packing key on the device (pack_keygen_kernel, pack_expand_kernel), likewise; not in rs_pack: its sources stay integer-only
     ("rs_packkey", "rs_packkey.hip", []),
     # device decryption and the key audit (lwe_phase_kernel, audit_bk_kernel, audit_ksk_kernel), likewise in an object of their own
@@ -70,9 +73,9 @@ HIP_OBJECTS = [
     ("rs_api_client", "rs_api_client.cpp", []),
 ]
 HIP_SOURCES = [src for _, src, _ in HIP_OBJECTS]
-HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
+HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
 EMU_SOURCES = ["rs_emulate.cpp"]
-EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
+EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
 
 
 def _abs(paths):

@@ -426,6 +426,26 @@ class SecretKeySet:
         body = keygen.ring_selector_rows(bits, self.tlwe_key, mask_seed, noise_seed, basebit, l, stdev)
         return RingSelector(self.name, self.N, depth, basebit, l, mask_seed, body)
 
+    # circuit bootstrapping (include/redsec_hip.h rs_ring_selector_dev / rs_circuit_bootstrap_dev): the key
+    # under which a server turns bits it computed under THIS secret's LWE key into selectors under this secret's ring key
+    def selector_key(self, ks_basebit=None, ks_t=None, mask_seed=None, noise_seed=None, stdev=None, depth=1):
+        """The selector key from this secret's LWE key to its ring key -> SelectorKey: 2 (n + 1) ks_t seeded ring samples (rows (f (n+1)
+        + i) ks_t + q of the public mask seed, domains 20 / 21), 32 + 4 N 2 (n + 1) ks_t bytes. ks_basebit, ks_t default to
+        keygen.circuit_bootstrap_default(name, depth) (ValueError where no shape works: default-128), stdev to the deviation of
+        selector rows (keygen.ring_selector_default_stdev). Equal seeds are refused. The products run on the host: there is no
+        device generator. The key encrypts multiples of S and of s S under S: the circular assumption of the bootstrapping key."""
+        from . import keygen
+        if ks_basebit is None or ks_t is None:
+            d = keygen.circuit_bootstrap_default(self.name, depth)
+            ks_basebit, ks_t = d[2] if ks_basebit is None else ks_basebit, d[3] if ks_t is None else ks_t
+        ks_basebit, ks_t = keygen._check_selector_digits(ks_basebit, ks_t)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        noise_seed = os.urandom(32) if noise_seed is None else bytes(noise_seed)
+        keygen._check_seeds(mask_seed, noise_seed)
+        stdev = keygen.ring_selector_default_stdev(self.name) if stdev is None else float(stdev)
+        body = keygen.selector_key(self.lwe_key, self.tlwe_key, mask_seed, noise_seed, ks_basebit, ks_t, stdev)
+        return SelectorKey(self.name, len(self.lwe_key), ks_basebit, ks_t, mask_seed, body)
+
     def classify(self, logits_ct, backend=None):
         """client/decrypt_image.cpp:61-62 argmax."""
         return int(np.argmax(self.decrypt_ints(logits_ct, backend=backend)))
@@ -504,7 +524,7 @@ _RS_HEADER = np.dtype([("magic", "<u4"), ("n", "<i4"), ("N", "<i4"), ("k", "<i4"
                        ("ks_basebit", "<i4"), ("lwe_alpha_min", "<f8"), ("lwe_alpha_max", "<f8"), ("tlwe_alpha_min", "<f8"),
                        ("tlwe_alpha_max", "<f8")])
 RS_MAGIC = {"RSS1": 0x31535352, "RSK1": 0x314B5352, "RSZ1": 0x315A5352, "RSC1": 0x31435352, "RSP1": 0x31505352,
-            "RSR1": 0x31525352, "RSX1": 0x31585352, "RSG1": 0x31475352}
+            "RSR1": 0x31525352, "RSX1": 0x31585352, "RSG1": 0x31475352, "RSB1": 0x31425352}
 
 
 def write_compressed_cloud_key(f, ck, max_stdev=0.012467):
@@ -982,6 +1002,70 @@ def read_ring_selector(f):
     if len(rest) != want:
         raise ValueError("truncated selector file: %d payload bytes, expected %d" % (len(rest), want))
     return RingSelector(name, N, depth, basebit, l, rest[:32], np.frombuffer(rest[32:], np.int32).copy())
+
+
+class SelectorKey:
+    """A selector key (include/redsec_hip.h rs_ring_selector_dev) of a secret of set `name` with LWE
+    dimension n: 2 (n + 1) ks_t seeded ring samples of the digit shape (ks_basebit, ks_t), ks_t ks_basebit <= 32. What travels is the
+    public 32-byte mask seed and the bodies int32 [2][n+1][ks_t][N] of the rows of domains 20 / 21; nbytes = 32 + 4 N 2 (n + 1) ks_t."""
+
+    def __init__(self, name, n, ks_basebit, ks_t, mask_seed, body):
+        self.name, self.n, self.ks_basebit, self.ks_t = name, int(n), int(ks_basebit), int(ks_t)
+        assert name in PARAM_SETS, "unknown parameter set"
+        self.N = PARAM_SETS[name][1]
+        assert 1 <= self.n <= 65536, "n in 1 .. 65536"
+        assert 1 <= self.ks_basebit <= 8 and self.ks_t >= 1 and self.ks_t * self.ks_basebit <= 32, "ks_basebit in 1 .. 8, ks_t >= 1, ks_t ks_basebit <= 32"
+        self.mask_seed = bytes(mask_seed)
+        assert len(self.mask_seed) == 32, "mask seed must be 32 bytes"
+        self.body = np.ascontiguousarray(body, np.int32).reshape(-1)
+        want = 2 * (self.n + 1) * self.ks_t * self.N
+        assert self.body.size == want, "body must have 2 (n + 1) ks_t N = %d words" % want
+        self.body = self.body.reshape(2, self.n + 1, self.ks_t, self.N)
+
+    @property
+    def nbytes(self):
+        return 32 + 4 * self.body.size
+
+    def expand(self):
+        """The domain-20 masks of the seed beside the bodies -> int32 [2][n+1][ks_t][2][N], what rs_ring_selector_dev takes."""
+        from . import keygen
+        return keygen.selector_key_expand(self.mask_seed, self.body)
+
+
+def write_selector_key(f, key):
+    """A selector key file (binary file object): the RS header with magic RSB1 for the set (its n the key's n), int32 ks_basebit,
+    int32 ks_t, then the 32-byte mask seed and the 2 (n + 1) ks_t N int32 body words. key: SelectorKey."""
+    f.write(_rs_header("RSB1", key.name, key.n))
+    f.write(np.array([key.ks_basebit, key.ks_t], "<i4").tobytes())
+    f.write(key.mask_seed)
+    f.write(key.body.tobytes())
+
+
+def read_selector_key(f):
+    """-> SelectorKey of a selector key file. Raises ValueError for a truncated file, another magic, a parameter shape no set has, an
+    n outside 1 .. 65536, digits outside ks_basebit 1 .. 8, ks_t >= 1, ks_t ks_basebit <= 32, or a payload that is not exactly the
+    words the header promises."""
+    raw = f.read(_RS_HEADER.itemsize)
+    if len(raw) < 4 or np.frombuffer(raw[:4], "<u4")[0] != RS_MAGIC["RSB1"]:
+        raise ValueError("not a selector key (RSB1) file")
+    if len(raw) < _RS_HEADER.itemsize:
+        raise ValueError("truncated selector key file: short header")
+    h = np.frombuffer(raw, _RS_HEADER)[0]
+    shape = (int(h["N"]), int(h["k"]), int(h["l"]), int(h["Bgbit"]), int(h["ks_t"]), int(h["ks_basebit"]))
+    name = next((nm for nm, v in PARAM_SETS.items() if v[1:7] == shape), None)
+    if name is None:
+        raise ValueError("no parameter set with N, k, l, Bgbit, t, basebit = %s" % (shape,))
+    n = int(h["n"])
+    digits, rest = f.read(8), f.read()
+    if len(digits) < 8:
+        raise ValueError("truncated selector key file: %d bytes after the header" % len(digits))
+    ks_basebit, ks_t = (int(v) for v in np.frombuffer(digits, "<i4"))
+    if not (1 <= n <= 65536 and 1 <= ks_basebit <= 8 and ks_t >= 1 and ks_t * ks_basebit <= 32):
+        raise ValueError("selector key file with n = %d, ks_basebit = %d, ks_t = %d" % (n, ks_basebit, ks_t))
+    want = 32 + 4 * 2 * (n + 1) * ks_t * PARAM_SETS[name][1]
+    if len(rest) != want:
+        raise ValueError("truncated selector key file: %d payload bytes, expected %d" % (len(rest), want))
+    return SelectorKey(name, n, ks_basebit, ks_t, rest[:32], np.frombuffer(rest[32:], np.int32).copy())
 
 
 def write_ciphertexts(f, ct):

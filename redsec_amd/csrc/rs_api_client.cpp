@@ -1,6 +1,7 @@
 // rs_api_client.cpp -- key material and client-side calls of the C ABI (include/redsec_hip.h) that need no lane, no launch plan
-// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying (LWE and ring), encrypted selection and the packing key, device
-// decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
+// and no loaded key: seeded ciphertexts, the two public-key encryptions, RLWE extract, pack, re-keying (LWE and ring), encrypted
+// selection, the selector keyswitch (and rs_circuit_bootstrap_dev, the one call here that needs a loaded key: it composes public
+// calls around that keyswitch) and the packing key, device decryption and the three audits. Also the home of the ONE path a secret key takes onto the device and back off it
 // (rs::with_secret_copy; rs_keygen_dev of rs_api_keys.cpp goes through it too) and of the refusals these calls share.
 #include "rs_api_internal.h"
 
@@ -14,6 +15,7 @@
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
 #include "rs_ring_rekey.h"
+#include "rs_ring_selector.h"
 #include "rs_rlwe.h"
 
 using rs::fail;
@@ -355,6 +357,71 @@ int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t ent
     rows = (size_t)rs::rc_level_rows((long)rows);
   }
   return RS_OK;
+}
+
+// circuit bootstrapping (include/redsec_hip.h; kernels of rs_ring_selector.hip, integer arithmetic only). The checks the two calls
+// share: digit shapes, ring, depth, source dimension, and the workgroups of the launches. The keyswitch itself needs no key.
+static int ring_selector_shape(const rs_ctx* c, int32_t depth, int32_t basebit, int32_t l, int32_t n_src, const int32_t* sel_key,
+                               int32_t ks_basebit, int32_t ks_t, size_t* N_) {
+  if (basebit < 1 || basebit > 8) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
+  if (l < 1) return fail(RS_ERR_INVALID, "l = %d is below 1", (int)l);
+  if ((int64_t)l * basebit > rs::kSeMaxBits)
+    return fail(RS_ERR_INVALID, "l basebit = %d x %d passes %d bits", (int)l, (int)basebit, rs::kSeMaxBits);
+  if (ks_basebit < 1 || ks_basebit > 8) return fail(RS_ERR_INVALID, "ks_basebit = %d is outside 1 .. 8", (int)ks_basebit);
+  if (ks_t < 1) return fail(RS_ERR_INVALID, "ks_t = %d is below 1", (int)ks_t);
+  if ((int64_t)ks_t * ks_basebit > 32) return fail(RS_ERR_INVALID, "ks_t ks_basebit = %d x %d passes 32 bits", (int)ks_t, (int)ks_basebit);
+  if (depth < 0 || depth > rs::kSeMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 0 .. %d", (int)depth, rs::kSeMaxDepth);
+  if (n_src < 1 || n_src > rs::kSeMaxSrc) return fail(RS_ERR_INVALID, "n_src = %d is outside 1 .. %d", (int)n_src, rs::kSeMaxSrc);
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kSeMinN || N > (size_t)rs::kSeMaxN || (N & (N - 1))) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  if ((uintptr_t)sel_key & 15u) return fail(RS_ERR_INVALID, "sel_key must be 16-byte aligned");
+  // the key's words, the init kernel's workgroups and rs::se_groups, each inside what a launch and a long can index
+  const size_t rows = (size_t)depth * (size_t)l, key_polys = 2 * ((size_t)n_src + 1) * (size_t)ks_t * 2;
+  if (key_polys > (size_t)LONG_MAX / sizeof(int32_t) / N) return fail(RS_ERR_INVALID, "a key of %zu polynomials is too large", key_polys);
+  if (rows * 4 * N / rs::kSeInitThreads > (size_t)INT32_MAX ||
+      (size_t)rs::se_row_blocks((long)rows) > (size_t)INT32_MAX / (size_t)rs::se_groups_per_block((int)N, (int)n_src))
+    return fail(RS_ERR_INVALID, "depth l = %zu rows are too many for one launch", rows);
+  *N_ = N;
+  return RS_OK;
+}
+
+int rs_ring_selector_dev(rs_ctx* c, int32_t* sel, const int32_t* ct, int32_t depth, int32_t basebit, int32_t l, int32_t n_src,
+                         const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!sel || !ct || !sel_key) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_selector_shape(c, depth, basebit, l, n_src, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
+  if (depth == 0) return RS_OK;
+  const rs::RingSelectorArgs a{sel, ct, sel_key, (long)depth * l, (int)N, (int)n_src, (int)basebit, (int)l, (int)ks_basebit, (int)ks_t};
+  RS_HIP(rs::launch_ring_selector(a, (hipStream_t)stream));
+  return RS_OK;
+}
+
+// LWE bit -> l bootstraps at the gadget's levels -> selector keyswitch. The steps are the public calls: the gather that replicates
+// each bit l times, ONE programmable bootstrap over the depth l rows whose test polynomial of level j is the constant h_j / 2, and
+// rs_ring_selector_dev from the context's n. scratch (rs_ring_selector.h se_scratch_*): test polynomials, row index, replicated
+// bits, bootstraps.
+int rs_circuit_bootstrap_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
+                             const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!c->keys) return fail(RS_ERR_STATE, "rs_load_keys has not been called");
+  if (!sel || !bits || !sel_key || !scratch) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  const int n = c->p.n;
+  if ((rc = ring_selector_shape(c, depth, basebit, l, n, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
+  if (depth == 0) return RS_OK;
+  const long rows = (long)depth * l;
+  int32_t* lut = scratch;
+  int32_t* index = scratch + rs::se_scratch_index((int)N, (int)l, rows);
+  int32_t* rep = scratch + rs::se_scratch_bits((int)N, (int)l, rows);
+  int32_t* boot = scratch + rs::se_scratch_boot((int)N, (int)l, rows, n);
+  const rs::CircuitPrepareArgs pa{lut, index, rows, (int)N, (int)basebit, (int)l};
+  RS_HIP(rs::launch_circuit_prepare(pa, (hipStream_t)stream));
+  if ((rc = rs_gather_rows_dev(c, rep, bits, index, (size_t)rows, stream)) != RS_OK) return rc;
+  if ((rc = rs_bootstrap_lut_dev(c, boot, rep, lut, (size_t)l, 0, (size_t)rows, stream)) != RS_OK) return rc;
+  return rs_ring_selector_dev(c, sel, boot, depth, basebit, l, n, sel_key, ks_basebit, ks_t, stream);
 }
 
 // the packing key on the device (include/redsec_hip.h; kernels of rs_packkey.hip): the checks the three calls share. rows = n t.

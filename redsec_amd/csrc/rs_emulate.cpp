@@ -20,6 +20,7 @@
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
 #include "rs_ring_rekey.h"
+#include "rs_ring_selector.h"
 #include "rs_rlwe.h"
 #include "rs_launch_plan.h"
 #include "rs_lds_plan.h"
@@ -1631,6 +1632,65 @@ void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t
     if (rows & 1) rs_emu_ring_cmux(nullptr, in + (size_t)(rows - 1) * ct, 1, 1, N, s, basebit, l, o + (size_t)pairs * ct);
     in = o;
     rows = rs::rc_level_rows(rows);
+  }
+}
+// ---- the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev) through the functions of rs_ring_selector.h ----
+uint32_t rs_emu_ring_selector_offset(int ks_basebit, int ks_t) { return rs::se_offset(ks_basebit, ks_t); }
+long rs_emu_ring_selector_groups(long rows, int N, int n_src) { return rs::se_groups(rows, N, n_src); }
+int rs_emu_ring_selector_chunk() { return rs::kSeChunk; }
+int rs_emu_ring_selector_rows() { return rs::kSeRows; }
+long rs_emu_circuit_scratch_words(int N, int l, long rows, int n) { return (long)rs::se_scratch_words(N, l, rows, n); }
+// ring_selector_init_kernel, then ring_selector_kernel workgroup by workgroup and thread by thread as the kernel places them: the
+// grid over (tile, polynomial, family, chunk, row block), the staged words x_i + off of the chunk's coordinates and the block's rows
+// (zero where none), the chunk's key polynomials in storage order, four coefficients a thread, the negated partial sums added into
+// the output
+void rs_emu_ring_selector(const int32_t* ct_, int depth, int basebit, int l, int n_src, int N, const int32_t* key_, int ks_basebit,
+                          int ks_t, int32_t* sel_) {
+  const long rows = (long)depth * l;
+  if (rows <= 0) return;
+  uint32_t* sel = reinterpret_cast<uint32_t*>(sel_);
+  const uint32_t* ct = reinterpret_cast<const uint32_t*>(ct_);
+  const uint32_t* key = reinterpret_cast<const uint32_t*>(key_);
+  for (long idx = 0; idx < rows * 4 * (long)N; ++idx) sel[idx] = 0u;
+  const unsigned tiles = (unsigned)rs::se_tiles(N), chunks = (unsigned)rs::se_chunks(n_src);
+  const uint32_t off = rs::se_offset(ks_basebit, ks_t), mask = (1u << ks_basebit) - 1u;
+  uint32_t sx[rs::kSeChunk * rs::kSeRows];
+  for (long blk = 0; blk < rs::se_groups(rows, N, n_src); ++blk) {
+    unsigned g = (unsigned)blk;
+    const int tile = (int)(g % tiles); g /= tiles;
+    const int p = (int)(g & 1u); g >>= 1;
+    const int f = (int)(g & 1u); g >>= 1;
+    const int chunk = (int)(g % chunks);
+    const int r0 = (int)(g / chunks) * rs::kSeRows;
+    const int i0 = chunk * rs::kSeChunk, cn = n_src + 1 - i0 < rs::kSeChunk ? n_src + 1 - i0 : rs::kSeChunk;
+    const int rn = (int)rows - r0 < rs::kSeRows ? (int)rows - r0 : rs::kSeRows;
+    for (int t = 0; t < rs::kSeChunk * rs::kSeRows; ++t) {
+      const int ii = t / rs::kSeRows, r = t - ii * rs::kSeRows;
+      uint32_t x = 0u;
+      if (ii < cn && r < rn) {
+        const int i = i0 + ii;
+        x = ct[(size_t)(r0 + r) * ((size_t)n_src + 1) + (size_t)i] + off;
+        if (i == n_src) x += rs::se_half_step(basebit, (r0 + r) % l);
+      }
+      sx[t] = x;
+    }
+    for (int t = 0; t < rs::kSeThreads; ++t) {
+      const int k0 = tile * rs::kSeTile + rs::kSeKpt * t;
+      uint32_t acc[rs::kSeRows][rs::kSeKpt] = {};
+      for (int ii = 0; ii < cn; ++ii)
+        for (int q = 0; q < ks_t; ++q) {
+          const uint32_t* kw = key + rs::se_key_offset(N, n_src, ks_t, f, i0 + ii, q, p) + k0;
+          const int shift = 32 - (q + 1) * ks_basebit;
+          for (int r = 0; r < rs::kSeRows; ++r) {
+            const uint32_t d = (sx[ii * rs::kSeRows + r] >> shift) & mask;
+            for (int c = 0; c < rs::kSeKpt; ++c) acc[r][c] += kw[c] * d;
+          }
+        }
+      for (int r = 0; r < rn; ++r) {
+        uint32_t* o = sel + rs::se_out_offset(N, l, r0 + r, f, p) + k0;
+        for (int c = 0; c < rs::kSeKpt; ++c) o[c] += 0u - acc[r][c];
+      }
+    }
   }
 }
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of

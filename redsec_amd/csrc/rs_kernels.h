@@ -207,6 +207,23 @@ struct RingCmuxArgs {
   int N, basebit, l;
 };
 hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st);
+// the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev; placement and index arithmetic of rs_ring_selector.h)
+struct RingSelectorArgs {
+  int32_t* sel;                                       // [rows / l][2l][2][N]
+  const int32_t* ct;                                  // [rows][n_src+1]: row k l + j the bootstrap of bit k at level j
+  const int32_t* key;                                 // [2][n_src+1][ks_t][2][N], 16-byte aligned
+  long rows;                                          // depth l
+  int N, n_src, basebit, l, ks_basebit, ks_t;
+};
+hipError_t launch_ring_selector(const RingSelectorArgs& a, hipStream_t st);
+// rs_circuit_bootstrap_dev: lut[j] = the constant polynomial h_j / 2, index[r] = r / l (the gather that replicates each bit l times)
+struct CircuitPrepareArgs {
+  int32_t* lut;                                       // [l][N]
+  int32_t* index;                                     // [rows]
+  long rows;
+  int N, basebit, l;
+};
+hipError_t launch_circuit_prepare(const CircuitPrepareArgs& a, hipStream_t st);
 // the packing key on the device (rs_pack_keygen_dev, rs_pack_expand_dev; streams and placement of rs_packkey.h): row i t + j is
 // (a, a*S + e + s_i g_j X^0), a the domain-14 words of the mask seed, e the domain-15 Gaussians of the noise seed
 struct PackKeygenArgs {

@@ -114,6 +114,21 @@ The seeded form, row = k 2l + j for sample k (bit k of the index, least signific
   Domains 18 and 19 are disjoint from domains 1-17. Equal mask and noise seeds are refused. ring_cmux_digits / ring_cmux /
   ring_lookup / ring_selector_rows / ring_selector_expand / ring_trivial / ring_cmux_sigma / ring_cmux_default restate it.
 
+Circuit bootstrapping (rs_ring_selector_dev, rs_circuit_bootstrap_dev; include/redsec_hip.h): the
+selectors of the section above made by the server from LWE bits. Bit k is bootstrapped at the l levels to phase +-h_j/2, and a
+keyswitch from the n_src + 1 coordinates x = (a, b + h_j/2) to the ring key, under two key families, gives the rows of the RGSW
+sample. The selector key, row = (f (n_src+1) + i) ks_t + q with sg = (s, -1), g_q = 2^(32-(q+1) ks_basebit):
+
+  domain 20  selector-key mask    row   mask seed (public)             a[c] = word c, c < N
+  domain 21  selector-key noise   row   owner's noise seed (private)   e[c] = Gaussian c (words 4c .. 4c+3)
+  body of family 1: a*S + e + sg_i g_q (coefficient 0); of family 0: a*S + e - sg_i g_q S, a sample of zero with the message
+  folded into the mask side, as selector rows are.
+  sel[k][f l + j] = - sum_{i, q} d_iq K[f][i][q],  d_iq = ((x_i + off) >> (32-(q+1) ks_basebit)) & (2^ks_basebit - 1), the unsigned
+  rounding digits of pack / rekey, off = 2^(31 - ks_t ks_basebit).
+
+  Domains 20 and 21 are disjoint from domains 1-19. Equal mask and noise seeds are refused. selector_key / selector_key_expand /
+  ring_selector_switch / bootstrap_sigma / circuit_bootstrap_sigma / circuit_bootstrap_default restate it.
+
 Noise audit (rs_audit_keys_dev, rs_audit_compressed_keys_dev; include/redsec_hip.h): the noise words of a key under its secret,
 all arithmetic mod 2^32, g_j = 2^(32 - (j+1) Bgbit):
 
@@ -138,6 +153,7 @@ DOMAIN_RLWE_MASK, DOMAIN_RLWE_NOISE, DOMAIN_RLWE_SELECT, DOMAIN_RLWE_ENC_NOISE =
 DOMAIN_PACK_MASK, DOMAIN_PACK_NOISE = 14, 15
 DOMAIN_RING_REKEY_MASK, DOMAIN_RING_REKEY_NOISE = 16, 17
 DOMAIN_RING_SELECTOR_MASK, DOMAIN_RING_SELECTOR_NOISE = 18, 19
+DOMAIN_SELECTOR_KEY_MASK, DOMAIN_SELECTOR_KEY_NOISE = 20, 21
 _SIGMA = b"expand 32-byte k"
 
 
@@ -1163,6 +1179,161 @@ def ring_cmux_default(name, depth=1):
         if fits:
             return (min(fits)[1], l)
     raise ValueError("no (basebit, l) keeps 8 sigma inside 1/8192 on %s at depth %d" % (name, depth))
+
+
+# ---- circuit bootstrapping (rs_ring_selector_dev restated) ----
+
+SELECTOR_MAX_SRC = 65536
+CIRCUIT_BOOTSTRAP_STEP = 1.0 / 16   # the payload step of the default shape: 8 sigma has to stay inside half of it
+
+
+def _check_selector_digits(ks_basebit, ks_t):
+    ks_basebit, ks_t = int(ks_basebit), int(ks_t)
+    if not (1 <= ks_basebit <= 8 and ks_t >= 1 and ks_t * ks_basebit <= 32):
+        raise ValueError("ks_basebit = %d, ks_t = %d: ks_basebit must lie in 1 .. 8, ks_t >= 1 and ks_t ks_basebit <= 32" % (ks_basebit, ks_t))
+    return ks_basebit, ks_t
+
+
+def selector_key_mask(mask_seed, N, rows):
+    """The mask polynomials of selector-key rows: words 0 .. N-1 of stream (20, row) of the mask seed -> int32 [R][N]."""
+    rows = np.asarray(rows, np.int64).ravel()
+    return chacha20_words(mask_seed, DOMAIN_SELECTOR_KEY_MASK, rows.astype(np.uint64), int(N)).reshape(len(rows), int(N)).view(np.int32)
+
+
+def selector_key(lwe_key, tlwe_key, mask_seed, noise_seed, ks_basebit, ks_t, stdev, chunk=512):
+    """The bodies of the seeded selector key from the LWE secret lwe_key (any dimension n_src) to the ring secret tlwe_key -> int32
+    [2][n_src+1][ks_t][N]. Row (f (n_src+1) + i) ks_t + q: a = selector_key_mask(mask_seed, N, row), e the N Gaussians of stream (21,
+    row) of the private noise seed, sg = (s, -1), g_q = 2^(32-(q+1) ks_basebit); the body is a*S + e + sg_i g_q (coefficient 0) for
+    family f = 1 and a*S + e - sg_i g_q S for family 0: a sample of zero with the message folded into the mask side, as selector
+    rows are. The products by the binary S run here (_times_binary): there is no device generator. Equal seeds are refused."""
+    _check_seeds(mask_seed, noise_seed)
+    ks_basebit, ks_t = _check_selector_digits(ks_basebit, ks_t)
+    s = np.asarray(lwe_key, np.int64).ravel()
+    S = np.asarray(tlwe_key).ravel()
+    n, N = s.size, S.size
+    assert 1 <= n <= SELECTOR_MAX_SRC, "n_src must lie in 1 .. 65536"
+    per = (n + 1) * ks_t
+    body = np.empty((2 * per, N), np.uint32)
+    for lo in range(0, 2 * per, chunk):
+        rows = np.arange(lo, min(lo + chunk, 2 * per))
+        B = _times_binary(np.ascontiguousarray(selector_key_mask(mask_seed, N, rows)).view(np.uint32), S)
+        if stdev:
+            with np.errstate(over="ignore"):
+                B += noise32(chacha20_words(noise_seed, DOMAIN_SELECTOR_KEY_NOISE, rows.astype(np.uint64), 4 * N), stdev).reshape(len(rows), N).view(np.uint32)
+        body[lo:lo + len(rows)] = B
+    body = body.reshape(2, n + 1, ks_t, N)
+    sg = np.concatenate([s, [-1]])
+    Su = (S.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        for q in range(ks_t):
+            m = ((sg << (32 - (q + 1) * ks_basebit)) & 0xFFFFFFFF).astype(np.uint32)      # sg_i g_q
+            body[1, :, q, 0] += m
+            body[0, :, q, :] -= m[:, None] * Su[None, :]
+    return body.view(np.int32)
+
+
+def selector_key_expand(mask_seed, body):
+    """[2][n_src+1][ks_t][2][N], what rs_ring_selector_dev takes, from the public mask seed and the bodies int32 [2][n_src+1][ks_t][N]."""
+    body = np.ascontiguousarray(body, np.int32)
+    assert body.ndim == 4 and body.shape[0] == 2, "body must hold [2][n_src+1][ks_t][N] words"
+    N = body.shape[3]
+    mask = selector_key_mask(mask_seed, N, np.arange(body.size // N)).reshape(body.shape)
+    return np.ascontiguousarray(np.stack([mask, body], axis=3))
+
+
+def ring_selector_switch(ct, basebit, l, key, ks_basebit, ks_t):
+    """rs_ring_selector_dev restated: ct int32 [depth l][n_src+1] (row k l + j the bootstrap of bit k at level j, phase +-h_j/2),
+    key int32 [2][n_src+1][ks_t][2][N] -> int32 [depth][2l][2][N], sel[k][f l + j] = - sum_{i,q} d_iq K[f][i][q] over the unsigned
+    rounding digits of x = (a, b + h_j/2). One uint64 matrix product of the digit matrix [rows][(n_src+1) ks_t] with each family's
+    key [(n_src+1) ks_t][2 N], reduced mod 2^32: nothing like the device's tiled 32-bit multiply-adds."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    ks_basebit, ks_t = _check_selector_digits(ks_basebit, ks_t)
+    key = np.ascontiguousarray(key, np.int32)
+    assert key.ndim == 5 and key.shape[0] == 2 and key.shape[2] == ks_t and key.shape[3] == 2, "key must hold [2][n_src+1][ks_t][2][N] words"
+    n_src, N = key.shape[1] - 1, key.shape[4]
+    x = np.ascontiguousarray(ct, np.int32).reshape(-1, n_src + 1).view(np.uint32).astype(np.int64)
+    rows = x.shape[0]
+    assert rows % l == 0, "ct must hold depth l rows"
+    x[:, n_src] += np.array([1 << (31 - (j + 1) * basebit) for j in range(l)], np.int64)[np.arange(rows) % l]
+    off = 0 if ks_t * ks_basebit >= 32 else 1 << (31 - ks_t * ks_basebit)
+    xbar = (x + off) & 0xFFFFFFFF
+    D = np.stack([(xbar >> (32 - (q + 1) * ks_basebit)) & ((1 << ks_basebit) - 1) for q in range(ks_t)], axis=-1)   # [rows][n_src+1][ks_t]
+    D = D.reshape(rows, -1).astype(np.uint64)
+    out = np.empty((rows // l, 2, l, 2 * N), np.uint32)
+    for f in range(2):
+        K = key[f].view(np.uint32).reshape(-1, 2 * N).astype(np.uint64)
+        with np.errstate(over="ignore"):
+            acc = (np.uint64(0) - D @ K) & np.uint64(0xFFFFFFFF)
+        out[:, f] = acc.astype(np.uint32).reshape(rows // l, l, 2 * N)
+    return out.reshape(rows // l, 2 * l, 2, N).view(np.int32)
+
+
+def bootstrap_sigma(name, n=None):
+    """Deviation sigma_u of the phase error of one bootstrapped sample of set `name` (blind rotation and LWE keyswitch), as a real:
+      sigma_u^2 = n (2 l N (Bg^2 + 2)/12 sigma_bk^2 + (1/2)(1 + N/2) 2^(-2 l Bgbit)/12)  +  N t sigma_ks^2 + (N/2) 2^(-2 t basebit)/12
+    n CMUXes under the signed gadget digits (the rounding reaches the phase where the key bit is set), then the keyswitch's N t
+    table rows and the rounding of the N mask words over the N / 2 set ring-key bits."""
+    s = _shape(name, n)
+    Bg = 2.0 ** s["Bgbit"]
+    rotate = s["n"] * (2.0 * s["l"] * s["N"] * (Bg * Bg + 2.0) / 12.0 * s["bk_stdev"] ** 2
+                       + 0.5 * (1.0 + s["N"] / 2.0) * 2.0 ** (-2 * s["l"] * s["Bgbit"]) / 12.0)
+    switch = s["N"] * s["t"] * s["ks_stdev"] ** 2 + s["N"] / 2.0 * 2.0 ** (-2 * s["t"] * s["basebit"]) / 12.0
+    return float(np.sqrt(rotate + switch))
+
+
+def selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k):
+    """(sigma_w, sigma_key) of one produced selector row, as reals. sigma_w is the deviation of the message-side error w = u -
+    sum_i r_i sg_i: the bootstrap's sigma_u and the rounding of the n_src + 1 coordinates to ks_t ks_basebit bits (the b word and
+    the n_src / 2 set key bits); family 1 carries it on coefficient 0, family 0 multiplied by -S(X), so on every coefficient where S
+    has a bit. sigma_key is the key noise under the unsigned digits, on every coefficient of both families:
+      sigma_w^2 = sigma_u^2 + (1 + n_src/2) 2^(-2 ks_t ks_basebit)/12,   sigma_key^2 = (n_src + 1) ks_t (Bk - 1)(2 Bk - 1)/6 sigma_k^2"""
+    ks_basebit, ks_t = _check_selector_digits(ks_basebit, ks_t)
+    Bk = 2.0 ** ks_basebit
+    w = float(sigma_u) ** 2 + (1.0 + n_src / 2.0) * 2.0 ** (-2 * ks_t * ks_basebit) / 12.0
+    key = (n_src + 1.0) * ks_t * (Bk - 1.0) * (2.0 * Bk - 1.0) / 6.0 * float(sigma_k) ** 2
+    return float(np.sqrt(w)), float(np.sqrt(key))
+
+
+def circuit_bootstrap_sigma(N, n_src, basebit, l, ks_basebit, ks_t, sigma_u, sigma_k, depth=1, bit=1, coefficient=0):
+    """Deviation of the error of coefficient c = `coefficient` after `depth` CMUXes under produced selectors (a lookup of that
+    depth), as a real. Both families of a level come from the SAME bootstrapped sample, so its error w_j multiplies the digit
+    polynomial Db_j(X) - Da_j(X) S(X), and it is the same w_j on every coefficient. The signed digits of rs_ring_cmux_dev have
+    variance (B^2 - 1)/12 and MEAN -1/2; under independent row noise the mean only adds 1/4 to the mean square, but here the
+    means of the N digits of Da_j add up along S: coefficient c collects -(1 - T_c)/2 of w_j, T_c = (bits of S at or below c) -
+    (bits above c), of expectation t_c = c + 1 - N/2 and variance N/4. The term is largest at the two ends of the polynomial
+    (c = 0, the default: the worst coefficient) and vanishes in the middle. The key noise enters as the row noise of
+    ring_cmux_sigma, and the CMUX's own rounding is unchanged (bit=0 leaves it out):
+      sigma^2 = depth (l sigma_w^2 ((1 + N/2)(B^2 - 1)/12 + ((1 - t_c)^2 + N/4)/4)  +  2 l N (B^2 + 2)/12 sigma_key^2  +  (1 + N/2) 2^(-2 l basebit)/12)
+    with (sigma_w, sigma_key) = selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k). `coefficient` may be an array. A
+    trivial ciphertext (a = 0, a plaintext table row) has Da_j = 0, and the first term is then far smaller: an upper bound there."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    sw, sk = selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k)
+    B = 2.0 ** basebit
+    t = np.asarray(coefficient, np.float64) + 1.0 - N / 2.0
+    sample = l * sw * sw * ((1.0 + N / 2.0) * (B * B - 1.0) / 12.0 + ((1.0 - t) ** 2 + N / 4.0) / 4.0)
+    rounding = (1.0 + N / 2.0) * 2.0 ** (-2 * l * basebit) / 12.0 if bit else 0.0
+    out = np.sqrt(int(depth) * (sample + 2.0 * l * N * (B * B + 2.0) / 12.0 * sk * sk + rounding))
+    return float(out) if out.ndim == 0 else out
+
+
+def circuit_bootstrap_default(name, depth=1, step=CIRCUIT_BOOTSTRAP_STEP):
+    """(basebit, l, ks_basebit, ks_t) of circuit bootstrapping for a lookup of `depth` levels on set `name`: the cheapest shape for
+    which 8 circuit_bootstrap_sigma of the worst coefficient stays inside step / 2, the half step of payloads that are multiples of
+    `step`, at sigma_u =
+    bootstrap_sigma(name) and key rows of ring_selector_default_stdev(name). Cheapest: the smallest l (l bootstraps a bit), for that
+    l the smallest ks_t (the key is 2 (n + 1) ks_t ring samples), and for that pair the (basebit, ks_basebit) of the smallest
+    sigma. ValueError where no shape reaches it: default-128, whose bootstrap output noise alone is too large for every shape."""
+    sh = _shape(name)
+    N, n, su, sk = sh["N"], sh["n"], bootstrap_sigma(name), ring_selector_default_stdev(name)
+    for l in range(1, RING_CMUX_MAX_BITS + 1):
+        for ks_t in range(1, 33):
+            fits = [(circuit_bootstrap_sigma(N, n, b, l, kb, ks_t, su, sk, depth), b, kb)
+                    for b in range(1, 9) if b * l <= RING_CMUX_MAX_BITS for kb in range(1, 9) if kb * ks_t <= 32]
+            fits = [f for f in fits if 8 * f[0] <= step / 2.0]
+            if fits:
+                _, b, kb = min(fits)
+                return (b, l, kb, ks_t)
+    raise ValueError("no shape keeps 8 sigma inside half of %g on %s at depth %d" % (step, name, depth))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----
