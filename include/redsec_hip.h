@@ -240,11 +240,13 @@ int rs_rlwe_extract_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t cou
  * (sigma_k the key's deviation; the first term is the key noise under the digits, the second the digits' rounding). Slots at or
  * past count hold noise around 0. rs_rlwe_extract_dev + rs_keyswitch_dev turn a packed ciphertext back into LWE inputs, and
  * rs_rlwe_extract_dev + rs_phase_dev(dim = N) decrypt it on the device.
- * ct DEVICE int32[count][n+1]; rlwe DEVICE int32[R][2][N], must not overlap ct; pack_key DEVICE int32[n][t][2][N]. Integer
+ * ct DEVICE int32[count][n+1]; rlwe DEVICE int32[R][2][N]; pack_key DEVICE int32[n][t][2][N]. The kernels add into rlwe with
+ * atomics after an init kernel has set it: an rlwe that overlaps ct or pack_key is refused (the inputs may overlap each other). Integer
  * arithmetic only, exact: the words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on
  * `stream`; no allocation. count = 0 is a no-op that returns RS_OK.
  * RS_ERR_INVALID: a null rlwe, ct or pack_key; basebit outside 1 .. 8; t < 1; t basebit > 32; a count whose row arithmetic would
- * overflow. Without a device or context it fails as rs_rlwe_extract_dev does. */
+ * overflow; an rlwe that shares a byte with ct or pack_key ("rlwe overlaps ct"). Without a device or context it fails as
+ * rs_rlwe_extract_dev does. */
 int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
                 const int32_t* pack_key, int32_t basebit, int32_t t, void* stream);
 
@@ -267,12 +269,13 @@ int rs_pack_dev(rs_ctx* ctx, int32_t* rlwe, const int32_t* ct, size_t count,
  * key read as an LWE key, under which rs_phase_dev(dim = N) decrypts. The rows of one such ciphertext share its selector and
  * noise polynomials, so their noise has a common part that the unsigned digits would add up; redsec_amd encrypts every odd row
  * negated and negates it back after the extraction (keygen.py rekey_alternate), and the formula above then holds for this form.
- * ct DEVICE int32[B][n_src+1]; rekey_key DEVICE int32[n_src][t][n_dst+1]; out DEVICE int32[B][n_dst+1], overlaps neither input.
- * Both dimensions are arguments, not the context's: a server context of any set re-keys to any recipient. Integer arithmetic
+ * ct DEVICE int32[B][n_src+1]; rekey_key DEVICE int32[n_src][t][n_dst+1]; out DEVICE int32[B][n_dst+1]; an out that overlaps
+ * ct or rekey_key is refused (the kernels add into out with atomics; the inputs may overlap each other). Both dimensions are arguments, not the context's: a server context of any set re-keys to any recipient. Integer arithmetic
  * only, exact: the words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on `stream`; no
  * allocation. B = 0 is a no-op that returns RS_OK. A second call into the same buffer gives the same words.
  * RS_ERR_INVALID: a null out, ct or rekey_key; n_src or n_dst outside 1 .. 65536; basebit outside 1 .. 8; t < 1; t basebit > 32; a
- * B whose row arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_pack_dev does. */
+ * B whose row arithmetic would overflow or whose grid passes one launch; an out that shares a byte with ct or rekey_key ("out
+ * overlaps ct"). Without a device or context it fails as rs_pack_dev does. */
 int rs_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* ct, size_t B, int32_t n_src,
                  const int32_t* rekey_key, int32_t n_dst, int32_t basebit, int32_t t, void* stream);
 
@@ -294,12 +297,14 @@ int rs_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* ct, size_t B, int32_t
  * a digit polynomial with a mean would add the common part up along the coefficients (16 .. 22 times the formula with unsigned
  * digits; section 22 has the comparison). The key needs no call of its own: t + 1 seeded ring samples under S', or, without the
  * recipient's secret, the t + 1 ciphertexts of rs_rlwe_pk_encrypt_dev over the message rows under the recipient's RLWE public key.
- * rlwe, out DEVICE int32[R][2][N]; ring_key DEVICE int32[t+1][2][N]; out overlaps neither input. N is the context's ring; source
+ * rlwe, out DEVICE int32[R][2][N]; ring_key DEVICE int32[t+1][2][N]; an out that overlaps rlwe or ring_key is refused (the
+ * kernels add into out with atomics: re-keying in place is not offered; the inputs may overlap each other). N is the context's ring; source
  * and destination share it (crossing between rings of different degree is out of scope). Integer arithmetic only, exact: the
  * words do not depend on how the work is tiled. Needs no loaded key. Asynchronous and ordered on `stream`; no allocation. R = 0 is
  * a no-op that returns RS_OK. A second call into the same buffer gives the same words.
  * RS_ERR_INVALID: a null out, rlwe or ring_key; basebit outside 1 .. 8; t < 1; t basebit > 31 (h_j is an integer); an R whose row
- * arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_pack_dev does. */
+ * arithmetic would overflow or whose grid passes one launch; an out that shares a byte with rlwe or ring_key ("out overlaps
+ * rlwe"). Without a device or context it fails as rs_pack_dev does. */
 int rs_ring_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* rlwe, size_t R,
                       const int32_t* ring_key, int32_t basebit, int32_t t, void* stream);
 
@@ -322,11 +327,13 @@ int rs_ring_rekey_dev(rs_ctx* ctx, int32_t* out, const int32_t* rlwe, size_t R,
  * (sigma_row the deviation of one selector row's phase per coefficient; a signed digit has mean square (B^2 + 2)/12; the second
  * term is the rounding of x to l basebit bits, present where m = 1). A lookup adds `depth` of them.
  * d0[r] and d1[r] are read at row r stride (int32[2][N] each; stride >= 1, 2 for the even and odd entries of a table); out DEVICE
- * int32[R][2][N], contiguous, overlaps no input. The first kernel sets out = d0, so a second call into the same buffer gives the
- * same words. N is the context's ring. Integer arithmetic only, exact: the words do not depend on how the work is tiled. Needs no
+ * int32[R][2][N], contiguous. The first kernel sets out = d0 and the second adds into it with atomics, so a second call into the
+ * same buffer gives the same words and an out that overlaps an input is refused: the ((R - 1) stride + 1) ciphertexts that d0 and
+ * d1 are read from, or sel (out = d0 is not offered; d0, d1 and sel may overlap each other, as table[1:] / table do at stride 2). N is the context's ring. Integer arithmetic only, exact: the words do not depend on how the work is tiled. Needs no
  * loaded key. Asynchronous and ordered on `stream`; no allocation. R = 0 is a no-op that returns RS_OK.
  * RS_ERR_INVALID: a null out, d0 or sel; basebit outside 1 .. 8; l < 1; l basebit > 31; stride = 0; an R and stride whose row
- * arithmetic would overflow or whose grid passes one launch. Without a device or context it fails as rs_ring_rekey_dev does. */
+ * arithmetic would overflow or whose grid passes one launch; an out that shares a byte with d0, d1 or sel ("out overlaps d0").
+ * Without a device or context it fails as rs_ring_rekey_dev does. */
 int rs_ring_cmux_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride,
                      const int32_t* sel, int32_t basebit, int32_t l, void* stream);
 /* out DEVICE int32[2][N] = table[index] for table DEVICE int32[entries][2][N], 1 <= entries <= 2^depth, 1 <= depth <= 30, and sel
@@ -334,9 +341,9 @@ int rs_ring_cmux_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t
  * count as the all-zero ciphertext, so an index past `entries` yields an encryption of zero. Level k is one rs_ring_cmux_dev-shaped
  * launch over the pairs (2r, 2r + 1) of the previous level with stride 2; an unpaired last row runs as a second launch with d1 =
  * NULL, also where it is the only row of its level. scratch DEVICE int32[ceil(E/2) + ceil(E/4)][2][N], E = entries, used as two
- * ping-pong halves; it may be NULL when depth = 1. The last level writes out. out and scratch overlap neither each other nor an
- * input. Otherwise as rs_ring_cmux_dev, and RS_ERR_INVALID also for a null table, depth or entries out of range, and a null
- * scratch with depth > 1. */
+ * ping-pong halves; it may be NULL when depth = 1. The last level writes out. An out that overlaps table, sel or scratch, and a
+ * scratch that overlaps table or sel, are refused. Otherwise as rs_ring_cmux_dev, and RS_ERR_INVALID also for a null table, depth
+ * or entries out of range, a null scratch with depth > 1, and those overlaps ("out overlaps scratch"). */
 int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
                        const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
 
@@ -353,7 +360,7 @@ int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t e
  * sel DEVICE int32[depth][2l][2][N], the format rs_ring_cmux_dev / rs_ring_lookup_dev read: rows j < l have phase -m h_j S + noise,
  * rows l + j have phase m h_j at coefficient 0 and noise elsewhere (m the bit, 1 for a phase of +h_j/2). ct DEVICE
  * int32[depth l][n_src+1]; sel_key DEVICE int32[2][n_src+1][ks_t][2][N], 16-byte aligned (client.SecretKeySet.selector_key);
- * sel overlaps no input. n_src is an argument, as in rs_rekey_dev: the context's n (after rs_bootstrap_lut_dev) or N (extracted
+ * a sel that overlaps ct or sel_key is refused (the kernels add into sel with atomics). n_src is an argument, as in rs_rekey_dev: the context's n (after rs_bootstrap_lut_dev) or N (extracted
  * samples before the LWE keyswitch); N is the context's ring, 1024 .. 8192. Per coefficient the keyswitch adds an error of variance
  *   (n_src + 1) ks_t (2^ks_basebit - 1)(2^(ks_basebit+1) - 1)/6 sigma_k^2  +  rho (1 + n_src/2) 2^(-2 ks_t ks_basebit)/12
  * (sigma_k the deviation of a key row; rho = 1 where the message sits: coefficient 0 of rows l + j and the coefficients of rows
@@ -362,16 +369,17 @@ int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t e
  * on `stream`; no allocation. depth = 0 is a no-op that returns RS_OK. A second call into the same buffer gives the same words.
  * RS_ERR_INVALID: a null sel, ct or sel_key; basebit or ks_basebit outside 1 .. 8; l < 1; l basebit > 31; ks_t < 1; ks_t ks_basebit >
  * 32; depth outside 0 .. 30; n_src outside 1 .. 65536; a misaligned sel_key; row arithmetic that overflows or a grid past one
- * launch. Without a device or context it fails as rs_pack_dev does. */
+ * launch; a sel that shares a byte with ct or sel_key ("sel overlaps ct"). Without a device or context it fails as rs_pack_dev does. */
 int rs_ring_selector_dev(rs_ctx* ctx, int32_t* sel, const int32_t* ct, int32_t depth, int32_t basebit, int32_t l,
                          int32_t n_src, const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream);
 /* The composed call: bits DEVICE int32[depth][n+1] at +-1/8 under the context's loaded key (m = 1 is a phase of +1/8) become sel
  * DEVICE int32[depth][2l][2][N]. On the stream: each bit is replicated l times (rs_gather_rows_dev), ONE rs_bootstrap_lut_dev launch
  * takes the depth l rows, row k l + j against the constant test polynomial h_j/2, and rs_ring_selector_dev switches the results
  * from n_src = n. scratch DEVICE int32[l N + depth l (2 (n + 1) + 1)]: the l test polynomials, the row index of the gather, the
- * replicated bits and their bootstraps; it overlaps neither sel nor an input. Needs a loaded evaluation key (RS_ERR_STATE without
+ * replicated bits and their bootstraps; a sel that overlaps bits, sel_key or scratch, and a scratch that overlaps bits or sel_key,
+ * are refused. Needs a loaded evaluation key (RS_ERR_STATE without
  * one); all three arithmetic modes, with the certificate and mode rules of the other bootstrapped calls. Otherwise as
- * rs_ring_selector_dev, and RS_ERR_INVALID also for a null bits or scratch. */
+ * rs_ring_selector_dev, and RS_ERR_INVALID also for a null bits or scratch and for those overlaps ("sel overlaps scratch"). */
 int rs_circuit_bootstrap_dev(rs_ctx* ctx, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
                              const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream);
 

@@ -222,6 +222,16 @@ def params(name, n=None):
     return p
 
 
+def _refuse_overlap(name, out, words, others):
+    """ValueError where the tensor `out` of a call (its first `words` words) shares memory with an input: others = (name, tensor or
+    None, words read). What the ABI refuses with RS_ERR_INVALID (include/redsec_hip.h): these kernels add into out with atomics
+    after an init kernel has set it, so an overlap is refused, never computed. Inputs may overlap each other."""
+    lo, hi = out.data_ptr(), out.data_ptr() + 4 * words
+    for other, t, read in others:
+        if t is not None and words and read and t.data_ptr() < hi and lo < t.data_ptr() + 4 * read:
+            raise ValueError("%s overlaps %s" % (name, other))
+
+
 def _np_i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(_i32p)
@@ -497,6 +507,7 @@ class Backend:
         R = -(-count // N)
         out = self.empty(R, 2, N) if out is None else out
         assert out.numel() == R * 2 * N, "out must hold [ceil(count / N)][2][N] words"
+        _refuse_overlap("rlwe", out, out.numel(), (("ct", ct, ct.numel()), ("pack_key", key, key.numel())))
         _check(self.L, self.L.rs_pack_dev(self.h, self._ck_dev(out), self._ck_dev(ct), count, self._ck_dev(key), basebit, t, self._stream()))
         return out
 
@@ -531,6 +542,7 @@ class Backend:
         B = ct.numel() // (n_src + 1)
         out = self.empty(B, n_dst + 1) if out is None else out
         assert out.numel() == B * (n_dst + 1), "out must hold [B][n_dst+1] words"
+        _refuse_overlap("out", out, out.numel(), (("ct", ct, ct.numel()), ("rekey_key", key, key.numel())))
         _check(self.L, self.L.rs_rekey_dev(self.h, self._ck_dev(out), self._ck_dev(ct), B, n_src, self._ck_dev(key), n_dst, basebit, t,
                                            self._stream()))
         return out
@@ -557,8 +569,8 @@ class Backend:
     # ---- ring re-keying ----
     def ring_rekey(self, rlwe, key, basebit=None, t=None, out=None):
         """Packed ciphertexts rlwe (int32 CUDA tensor [R][2][N]) keyswitched to a recipient's ring key under a caller-supplied key
-        (rs_ring_rekey_dev, on torch's current stream) -> int32 CUDA tensor [R][2][N] (or into `out`, which overlaps neither input).
-        key: a client.RingRekeyKey (uploaded on this context's device, whose ring must be the key's: keep the tensor of
+        (rs_ring_rekey_dev, on torch's current stream) -> int32 CUDA tensor [R][2][N] (or into `out`; an `out` that overlaps an input is
+        refused with ValueError). key: a client.RingRekeyKey (uploaded on this context's device, whose ring must be the key's: keep the tensor of
         upload_ring_rekey_key for repeated calls) or an int32 CUDA tensor [t+1][2][N] with explicit basebit and t. Needs no loaded
         key."""
         from . import keygen
@@ -573,6 +585,7 @@ class Backend:
         R = rlwe.numel() // (2 * N)
         out = self.empty(R, 2, N) if out is None else out
         assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        _refuse_overlap("out", out, out.numel(), (("rlwe", rlwe, rlwe.numel()), ("ring_key", key, key.numel())))
         _check(self.L, self.L.rs_ring_rekey_dev(self.h, self._ck_dev(out), self._ck_dev(rlwe), R, self._ck_dev(key), basebit, t, self._stream()))
         return out
 
@@ -601,8 +614,8 @@ class Backend:
 
     def ring_cmux(self, d1, d0, sel, basebit=None, l=None, stride=1, out=None):
         """out[r] = d1[r stride] where the selector encrypts 1, d0[r stride] where it encrypts 0 (rs_ring_cmux_dev, on torch's
-        current stream) -> int32 CUDA tensor [R][2][N], R = ceil(rows of d0 / stride) (or into `out`, which overlaps no input).
-        d0, d1: int32 CUDA tensors [rows][2][N] of packed ciphertexts (Backend.pack, rlwe_pk_encrypt) or trivial ones
+        current stream) -> int32 CUDA tensor [R][2][N], R = ceil(rows of d0 / stride) (or into `out`; an `out` that overlaps an input is
+        refused with ValueError). d0, d1: int32 CUDA tensors [rows][2][N] of packed ciphertexts (Backend.pack, rlwe_pk_encrypt) or trivial ones
         (keygen.ring_trivial); d1 = None is the all-zero ciphertext. sel: a client.RingSelector of depth 1 (uploaded on this
         context's device: keep the tensor of upload_ring_selector for repeated calls) or an int32 CUDA tensor [2l][2][N] with
         explicit basebit and l. Needs no loaded key."""
@@ -617,6 +630,8 @@ class Backend:
         assert d1 is None or d1.numel() >= ((R - 1) * stride + 1) * 2 * N, "d1 must hold a row for every row read of d0"
         out = self.empty(R, 2, N) if out is None else out
         assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        read = ((R - 1) * stride + 1) * 2 * N if R else 0                    # rows 0, stride, .. (R - 1) stride
+        _refuse_overlap("out", out, out.numel(), (("d0", d0, read), ("d1", d1, read), ("sel", sel, sel.numel())))
         _check(self.L, self.L.rs_ring_cmux_dev(self.h, self._ck_dev(out), None if d1 is None else self._ck_dev(d1), self._ck_dev(d0),
                                                R, stride, self._ck_dev(sel), basebit, l, self._stream()))
         return out
@@ -635,6 +650,7 @@ class Backend:
             raise ValueError("%d entries need more than the %d selectors given" % (entries, depth))
         out = self.empty(2, N) if out is None else out
         assert out.numel() == 2 * N, "out must hold [2][N] words"
+        _refuse_overlap("out", out, out.numel(), (("table", table, table.numel()), ("sel", sel, sel.numel())))
         first = (entries + 1) // 2
         scratch = self.empty(first + (first + 1) // 2, 2, N) if depth > 1 else None
         _check(self.L, self.L.rs_ring_lookup_dev(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
@@ -675,7 +691,7 @@ class Backend:
     def ring_selector(self, ct, basebit, l, key, ks_basebit=None, ks_t=None, n_src=None, out=None):
         """The selector keyswitch (rs_ring_selector_dev, on torch's current stream): ct int32 CUDA tensor [depth l][n_src+1], row k l
         + j the bootstrap of bit k at level j with phase +-h_j/2 -> int32 CUDA tensor [depth][2l][2][N], what ring_cmux and
-        ring_lookup take (or into `out`, which overlaps no input). key: a client.SelectorKey (uploaded on this context's device:
+        ring_lookup take (or into `out`; an `out` that overlaps an input is refused with ValueError). key: a client.SelectorKey (uploaded on this context's device:
         keep the tensor of upload_selector_key for repeated calls) or an int32 CUDA tensor [2][n_src+1][ks_t][2][N] with explicit
         ks_basebit and ks_t. n_src defaults to the last dimension of ct less one. Needs no loaded key."""
         from . import keygen
@@ -690,6 +706,7 @@ class Backend:
             raise ValueError("depth = %d is outside 0 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
         out = self.empty(depth, 2 * l, 2, self.p.N) if out is None else out
         assert out.numel() == depth * 2 * l * 2 * self.p.N, "out must hold [depth][2l][2][N] words"
+        _refuse_overlap("sel", out, out.numel(), (("ct", ct, ct.numel()), ("sel_key", key, key.numel())))
         if depth:
             _check(self.L, self.L.rs_ring_selector_dev(self.h, self._ck_dev(out), self._ck_dev(ct), depth, basebit, l, n_src,
                                                        self._ck_dev(key), ks_basebit, ks_t, self._stream()))
@@ -709,6 +726,7 @@ class Backend:
             raise ValueError("depth = %d is outside 0 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
         out = self.empty(depth, 2 * l, 2, self.p.N) if out is None else out
         assert out.numel() == depth * 2 * l * 2 * self.p.N, "out must hold [depth][2l][2][N] words"
+        _refuse_overlap("sel", out, out.numel(), (("bits", bits, bits.numel()), ("sel_key", key, key.numel())))
         if depth:
             scratch = self.empty(l * self.p.N + depth * l * (2 * self.W + 1))
             _check(self.L, self.L.rs_circuit_bootstrap_dev(self.h, self._ck_dev(out), self._ck_dev(bits), depth, basebit, l,

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <initializer_list>
 
 #include "rs_keygen.h"
 #include "rs_pack.h"
@@ -64,6 +65,15 @@ int refuse_digits(int32_t basebit, int32_t t, bool digits) {
   if (digits && (int64_t)t * basebit > 32) return fail(RS_ERR_INVALID, "t basebit = %d x %d passes 32 bits", (int)t, (int)basebit);
   return RS_OK;
 }
+
+// `written` (the out of a call, or its scratch) shares no byte with any of `others`: the kernels add into what they write with
+// atomics after an init kernel has set it, so an overlap would give words that depend on scheduling. Inputs may overlap each other.
+int refuse_overlap(const rs::Extent& written, std::initializer_list<rs::Extent> others) {
+  const int i = rs::first_overlap(written, others.begin(), (int)others.size());
+  if (i >= 0) return fail(RS_ERR_INVALID, "%s overlaps %s", written.name, others.begin()[i].name);
+  return RS_OK;
+}
+constexpr size_t kWord = sizeof(int32_t);
 
 }  // namespace
 
@@ -237,6 +247,8 @@ int rs_pack_dev(rs_ctx* c, int32_t* rlwe, const int32_t* ct, size_t count, const
   const size_t per_r = 2 * (N / rs::kPaTile) * (size_t)rs::pa_slot_blocks((long)count, (int)N) * (size_t)rs::pa_chunks((int)n);
   if (R > (size_t)INT32_MAX / per_r)                                        // workgroups of one launch (rs::pa_groups)
     return fail(RS_ERR_INVALID, "count = %zu is too large for one launch", count);
+  if ((rc = refuse_overlap({"rlwe", rlwe, R * 2 * N * kWord}, {{"ct", ct, count * row_bytes}, {"pack_key", pack_key, n * (size_t)t * 2 * N * kWord}})) != RS_OK)
+    return rc;
   const rs::PackArgs a{rlwe, ct, pack_key, (long)count, (int)n, (int)N, (int)basebit, (int)t};
   RS_HIP(rs::launch_pack(a, (hipStream_t)stream));
   return RS_OK;
@@ -259,6 +271,10 @@ int rs_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* ct, size_t B, int32_t n
   const size_t per_tile = (size_t)rs::rk_word_tiles(n_dst) * (size_t)rs::rk_splits((long)B, n_src, n_dst);
   if (init_groups > (size_t)INT32_MAX || (size_t)rs::rk_ct_tiles((long)B) > (size_t)INT32_MAX / per_tile)
     return fail(RS_ERR_INVALID, "B = %zu is too large for one launch", B);
+  const size_t dst_words = (size_t)n_dst + 1;
+  if ((rc = refuse_overlap({"out", out, B * dst_words * kWord}, {{"ct", ct, B * ((size_t)n_src + 1) * kWord},
+                                                                  {"rekey_key", rekey_key, (size_t)n_src * (size_t)t * dst_words * kWord}})) != RS_OK)
+    return rc;
   const rs::RekeyArgs a{out, ct, rekey_key, (long)B, (int)n_src, (int)n_dst, (int)basebit, (int)t};
   RS_HIP(rs::launch_rekey(a, (hipStream_t)stream));
   return RS_OK;
@@ -280,6 +296,9 @@ int rs_ring_rekey_dev(rs_ctx* c, int32_t* out, const int32_t* rlwe, size_t R, co
   // workgroups of the two launches: one per kRrInitThreads output words, and rs::rr_groups
   const size_t init_per_r = 2 * N / rs::kRrInitThreads, per_r = (size_t)rs::rr_groups_per_ct((int)N, (int)t);
   if (R > (size_t)INT32_MAX / init_per_r || R > (size_t)INT32_MAX / per_r) return fail(RS_ERR_INVALID, "R = %zu is too large for one launch", R);
+  if ((rc = refuse_overlap({"out", out, R * 2 * N * kWord}, {{"rlwe", rlwe, R * 2 * N * kWord},
+                                                            {"ring_key", ring_key, ((size_t)t + 1) * 2 * N * kWord}})) != RS_OK)
+    return rc;
   const rs::RingRekeyArgs a{out, rlwe, ring_key, (long)R, (int)N, (int)basebit, (int)t};
   RS_HIP(rs::launch_ring_rekey(a, (hipStream_t)stream));
   return RS_OK;
@@ -318,6 +337,9 @@ int rs_ring_cmux_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* 
   if (stride == 0) return fail(RS_ERR_INVALID, "stride = 0");
   if ((rc = ring_cmux_rows(R, stride, N, l)) != RS_OK) return rc;
   if (R == 0) return RS_OK;
+  const size_t ct_bytes = 2 * N * kWord, read_bytes = ((R - 1) * stride + 1) * ct_bytes;     // rows 0, stride, .. (R - 1) stride
+  if ((rc = refuse_overlap({"out", out, R * ct_bytes}, {{"d0", d0, read_bytes}, {"d1", d1, read_bytes}, {"sel", sel, (size_t)2 * l * ct_bytes}})) != RS_OK)
+    return rc;
   const rs::RingCmuxArgs a{out, d1, d0, sel, (long)R, (long)stride, (int)N, (int)basebit, (int)l};
   RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
   return RS_OK;
@@ -338,6 +360,10 @@ int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t ent
   if (depth > 1 && !scratch) return fail(RS_ERR_INVALID, "null scratch with depth = %d", (int)depth);
   if ((rc = ring_cmux_rows(entries / 2 + 1, 2, N, l)) != RS_OK) return rc;     // level 0, the largest launch: entries / 2 pairs at stride 2
   const size_t ct = 2 * N, sel_words = (size_t)2 * l * ct;
+  const rs::Extent x_table{"table", table, entries * ct * kWord}, x_sel{"sel", sel, (size_t)depth * sel_words * kWord};
+  const rs::Extent x_scratch{"scratch", depth > 1 ? scratch : nullptr, (size_t)rs::rc_scratch_rows((long)entries) * ct * kWord};
+  if ((rc = refuse_overlap({"out", out, ct * kWord}, {x_table, x_sel, x_scratch})) != RS_OK) return rc;
+  if ((rc = refuse_overlap(x_scratch, {x_table, x_sel})) != RS_OK) return rc;
   int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::rc_level_rows((long)entries) * ct : nullptr};
   const int32_t* in = table;
   size_t rows = entries;
@@ -393,6 +419,10 @@ int rs_ring_selector_dev(rs_ctx* c, int32_t* sel, const int32_t* ct, int32_t dep
   size_t N = 0;
   if ((rc = ring_selector_shape(c, depth, basebit, l, n_src, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
   if (depth == 0) return RS_OK;
+  const size_t rows = (size_t)depth * (size_t)l, src_words = (size_t)n_src + 1;
+  if ((rc = refuse_overlap({"sel", sel, rows * 4 * N * kWord}, {{"ct", ct, rows * src_words * kWord},
+                                                                {"sel_key", sel_key, 2 * src_words * (size_t)ks_t * 2 * N * kWord}})) != RS_OK)
+    return rc;
   const rs::RingSelectorArgs a{sel, ct, sel_key, (long)depth * l, (int)N, (int)n_src, (int)basebit, (int)l, (int)ks_basebit, (int)ks_t};
   RS_HIP(rs::launch_ring_selector(a, (hipStream_t)stream));
   return RS_OK;
@@ -413,6 +443,12 @@ int rs_circuit_bootstrap_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, int32
   if ((rc = ring_selector_shape(c, depth, basebit, l, n, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
   if (depth == 0) return RS_OK;
   const long rows = (long)depth * l;
+  const size_t src_words = (size_t)n + 1;
+  const rs::Extent x_bits{"bits", bits, (size_t)depth * src_words * kWord};
+  const rs::Extent x_key{"sel_key", sel_key, 2 * src_words * (size_t)ks_t * 2 * N * kWord};
+  const rs::Extent x_scratch{"scratch", scratch, rs::se_scratch_words((int)N, (int)l, rows, n) * kWord};
+  if ((rc = refuse_overlap({"sel", sel, (size_t)rows * 4 * N * kWord}, {x_bits, x_key, x_scratch})) != RS_OK) return rc;
+  if ((rc = refuse_overlap(x_scratch, {x_bits, x_key})) != RS_OK) return rc;
   int32_t* lut = scratch;
   int32_t* index = scratch + rs::se_scratch_index((int)N, (int)l, rows);
   int32_t* rep = scratch + rs::se_scratch_bits((int)N, (int)l, rows);

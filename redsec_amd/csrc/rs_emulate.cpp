@@ -1634,6 +1634,14 @@ void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t
     rows = rs::rc_level_rows(rows);
   }
 }
+// ---- the refusal of an out that overlaps an input (rs_api_client.cpp refuse_overlap) through rs_host.h first_overlap ----
+// written = (address, bytes); others [count][2] the same pairs -> the index of the first one that shares a byte with it, or -1.
+// Addresses are plain numbers here: nothing is read or written through them.
+int rs_emu_first_overlap(uint64_t address, uint64_t bytes, const uint64_t* others, int count) {
+  std::vector<rs::Extent> x;
+  for (int i = 0; i < count; ++i) x.push_back({"", (const void*)(uintptr_t)others[2 * i], (size_t)others[2 * i + 1]});
+  return rs::first_overlap({"", (const void*)(uintptr_t)address, (size_t)bytes}, x.data(), count);
+}
 // ---- the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev) through the functions of rs_ring_selector.h ----
 uint32_t rs_emu_ring_selector_offset(int ks_basebit, int ks_t) { return rs::se_offset(ks_basebit, ks_t); }
 long rs_emu_ring_selector_groups(long rows, int N, int n_src) { return rs::se_groups(rows, N, n_src); }

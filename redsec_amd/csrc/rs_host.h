@@ -295,4 +295,20 @@ inline std::string validate_schedule(double p, int l, int bgbit, unsigned fwd_ma
   return "";
 }
 
+// ---- arguments that must not share memory (rs_api_client.cpp refuse_overlap; walked on the CPU through rs_emu_first_overlap) ----
+// One argument of a call: the bytes [p, p + bytes) of device memory. A null pointer or an empty range overlaps nothing.
+struct Extent { const char* name; const void* p; size_t bytes; };
+inline bool extents_overlap(const Extent& a, const Extent& b) {
+  if (!a.p || !b.p || a.bytes == 0 || b.bytes == 0) return false;
+  const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+  // a0 < b0 + b.bytes and b0 < a0 + a.bytes, written so that a range which ends at the top of the address space cannot wrap
+  return (a0 >= b0 ? a0 - b0 < b.bytes : b0 - a0 < a.bytes);
+}
+// index of the first of `count` ranges that `written` shares a byte with, or -1
+inline int first_overlap(const Extent& written, const Extent* others, int count) {
+  for (int i = 0; i < count; ++i)
+    if (extents_overlap(written, others[i])) return i;
+  return -1;
+}
+
 }  // namespace rs

@@ -30,6 +30,7 @@ def lib():
         L.rs_emu_gen_polymul.argtypes = [C.c_int, _i32p, _i32p, _i32p, C.POINTER(C.c_double)]
         L.rs_emu_launch_plan.restype = C.c_long
         L.rs_emu_launch_plan.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_long, C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_long)]
+        L.rs_emu_first_overlap.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
         _lib = L
     return _lib
 

@@ -243,10 +243,26 @@ def test_invalid_arguments_and_the_empty_batch():
     assert pack(cnt=1 << 62) == -1 and b"too large" in L.rs_last_error()
     assert pack(cnt=(1 << 64) - 1) == -1 and b"too large" in L.rs_last_error()
     assert pack(cnt=1 << 44) == -1 and b"too large" in L.rs_last_error()          # fits the address space, not one launch
+    # an rlwe that shares a byte with an input is refused: the kernels add into it with atomics after an init kernel has set it.
+    # Every range named below lies inside one allocation of four ciphertexts (ct at its start or behind its first ciphertext) or
+    # inside the key
+    arena = _dev(_words(rng, 4 * 2 * N))
+    held, held_key = arena.cpu().numpy(), key.cpu().numpy()
+    A, K, row = arena.data_ptr(), key.data_ptr(), 4 * (n + 1)
+    for o in (A, A + row, A + count * row - 4):                               # rlwe == ct, one sample into ct, on its last word
+        assert pack(o=vp(o), c=vp(A)) == -1 and b"rlwe overlaps ct" in L.rs_last_error()
+    assert pack(o=vp(A), c=vp(A + 8 * N - 4)) == -1 and b"rlwe overlaps ct" in L.rs_last_error()   # the last word of rlwe is ct's first
+    for o in (K, K + 8 * N, K + 4 * key.numel() - 8 * N):                     # rlwe on the key's first, second and last sample
+        assert pack(o=vp(o)) == -1 and b"rlwe overlaps pack_key" in L.rs_last_error()
+    with pytest.raises(ValueError, match="rlwe overlaps ct"):
+        be.pack(arena[:count * (n + 1)].view(count, n + 1), key, 4, 5, out=arena[:2 * N])
+    with pytest.raises(ValueError, match="rlwe overlaps pack_key"):
+        be.pack(ct, key, 4, 5, out=key[n - 1, 4])
     # nothing above launched anything; count = 0 is a no-op
     assert pack(cnt=0) == 0
     torch.cuda.synchronize()
     assert bool((out == 7).all())
+    assert np.array_equal(arena.cpu().numpy(), held) and np.array_equal(key.cpu().numpy(), held_key)
     assert pack() == 0
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), keygen.pack(ct.cpu().numpy(), key.cpu().numpy(), 4, 5))

@@ -262,10 +262,25 @@ def test_invalid_arguments_and_the_empty_batch():
     assert rekey(b=1 << 62) == -1 and b"too large" in L.rs_last_error()
     assert rekey(b=(1 << 64) - 1) == -1 and b"too large" in L.rs_last_error()
     assert rekey(b=1 << 44) == -1 and b"too large for one launch" in L.rs_last_error()   # fits the address space, not one launch
+    # an out that shares a byte with an input is refused: the kernels add into it with atomics after an init kernel has set it.
+    # Every range named below lies inside one allocation of 512 words or inside the key (765 words, out is 85)
+    arena = _dev(_words(rng, 512))
+    held, held_key = arena.cpu().numpy(), key.cpu().numpy()
+    A, K, row = arena.data_ptr(), key.data_ptr(), 4 * (n_src + 1)
+    for o in (A, A + row, A + B * row - 4):                                   # out == ct, one sample into ct, on its last word
+        assert rekey(o=vp(o), c=vp(A)) == -1 and b"out overlaps ct" in L.rs_last_error()
+    assert rekey(o=vp(A), c=vp(A + 4 * B * (n_dst + 1) - 4)) == -1 and b"out overlaps ct" in L.rs_last_error()   # out's last word is ct's first
+    for o in (K, K + 4 * (n_dst + 1), K + 4 * (key.numel() - B * (n_dst + 1))):   # out on the key's first and second row and its end
+        assert rekey(o=vp(o)) == -1 and b"out overlaps rekey_key" in L.rs_last_error()
+    with pytest.raises(ValueError, match="out overlaps ct"):
+        be.rekey(arena[:B * (n_src + 1)].view(B, n_src + 1), key, 4, 5, out=arena[:B * (n_dst + 1)])
+    with pytest.raises(ValueError, match="out overlaps rekey_key"):
+        be.rekey(ct, key, 4, 5, out=key.view(-1)[:B * (n_dst + 1)])
     # nothing above launched anything; B = 0 is a no-op
     assert rekey(b=0) == 0
     torch.cuda.synchronize()
     assert bool((out == 7).all())
+    assert np.array_equal(arena.cpu().numpy(), held) and np.array_equal(key.cpu().numpy(), held_key)
     assert rekey() == 0
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), keygen.rekey(ct.cpu().numpy(), key.cpu().numpy(), 4, 5))

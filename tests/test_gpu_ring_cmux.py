@@ -196,10 +196,53 @@ def test_ring_cmux_invalid_arguments_and_the_empty_batch():
         assert look(entries=entries, depth=depth) == -1 and b"entries" in L.rs_last_error()
     assert look(sc=None) == -1 and b"null scratch" in L.rs_last_error()
     assert look(entries=1 << 30, depth=30) == -1 and b"too large for one launch" in L.rs_last_error()
+    # an out that shares a byte with an input is refused: the kernels add into it with atomics after an init kernel has set it to
+    # d0, so out = d0 is not offered. Every range named below lies inside one allocation of eight ciphertexts, the selectors (36)
+    # or the scratch
+    arena = _dev(_words(rng, 8, 2, N))
+    held, held_sel = arena.cpu().numpy(), sel.cpu().numpy()
+    A, S, ct = arena.data_ptr(), sel.data_ptr(), 8 * N
+    for o in (A, A + ct, A + 2 * ct - 4):                                     # out == d0, one ciphertext into it, on its last word
+        assert call(o=vp(o), b=vp(A)) == -1 and b"out overlaps d0" in L.rs_last_error()
+        assert call(o=vp(o), a=vp(A)) == -1 and b"out overlaps d1" in L.rs_last_error()
+        assert call(o=vp(o), a=None, b=vp(A)) == -1 and b"out overlaps d0" in L.rs_last_error()
+    assert call(o=vp(A), b=vp(A + 2 * ct - 4)) == -1 and b"out overlaps d0" in L.rs_last_error()      # out's last word is d0's first
+    # rows 0 and 2 at stride 2 are read from three ciphertexts, d0 from the arena's rows 0 .. 2 and d1 from its rows 3 .. 5: an out
+    # that touches only the third of either is refused (an out behind it is accepted: below)
+    assert call(o=vp(A + 2 * ct), b=vp(A), a=vp(A + 4 * ct), stride=2) == -1 and b"out overlaps d0" in L.rs_last_error()
+    assert call(o=vp(A + 5 * ct), b=vp(A), a=vp(A + 3 * ct), stride=2) == -1 and b"out overlaps d1" in L.rs_last_error()
+    for o in (S, S + 11 * ct, S + 12 * ct - 4):                               # out on the first and the last row of the selector
+        assert call(o=vp(o)) == -1 and b"out overlaps sel" in L.rs_last_error()
+    assert look(o=vp(A), tb=vp(A)) == -1 and b"out overlaps table" in L.rs_last_error()
+    assert look(o=vp(A + ct), tb=vp(A)) == -1 and b"out overlaps table" in L.rs_last_error()
+    assert look(o=vp(S + 23 * ct)) == -1 and b"out overlaps sel" in L.rs_last_error()               # the last row of selector 1
+    assert look(o=P(scratch)) == -1 and b"out overlaps scratch" in L.rs_last_error()
+    assert look(o=vp(scratch.data_ptr() + ct)) == -1 and b"out overlaps scratch" in L.rs_last_error()
+    assert look(sc=vp(A + ct), tb=vp(A)) == -1 and b"scratch overlaps table" in L.rs_last_error()
+    assert look(sc=vp(S + 22 * ct)) == -1 and b"scratch overlaps sel" in L.rs_last_error()
+    with pytest.raises(ValueError, match="out overlaps d0"):
+        be.ring_cmux(d1, arena[:2], sel[0], 4, 6, out=arena[:2])
+    with pytest.raises(ValueError, match="out overlaps d0"):
+        be.ring_cmux(d1, arena[:2], sel[0], 4, 6, out=arena[1:3])
+    with pytest.raises(ValueError, match="out overlaps d1"):
+        be.ring_cmux(arena[:2], d0, sel[0], 4, 6, out=arena[1:3])
+    with pytest.raises(ValueError, match="out overlaps sel"):
+        be.ring_cmux(d1, d0, sel[0], 4, 6, out=sel[0, 10:])
+    with pytest.raises(ValueError, match="out overlaps table"):
+        be.ring_lookup(arena[:4], sel[:2], 4, 6, out=arena[3])
+    with pytest.raises(ValueError, match="out overlaps sel"):
+        be.ring_lookup(arena[:4], sel[:2], 4, 6, out=sel[1, 11])
     # nothing above launched anything; R = 0 is a no-op
     assert call(r=0) == 0
     torch.cuda.synchronize()
     assert bool((out == 7).all())
+    assert np.array_equal(arena.cpu().numpy(), held) and np.array_equal(sel.cpu().numpy(), held_sel)
+    # inputs may overlap each other, and an out that begins where the strided rows end is accepted: rows 0 and 2 of the arena
+    # against rows 1 and 3, into rows 4 and 5
+    assert call(o=vp(A + 4 * ct), a=vp(A + ct), b=vp(A), stride=2) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(arena[4:6].cpu().numpy(), keygen.ring_cmux(held[1:4:2], held[0:4:2], held_sel[0], 4, 6))
+    assert np.array_equal(arena[:4].cpu().numpy(), held[:4]) and np.array_equal(arena[6:].cpu().numpy(), held[6:])
     assert call() == 0
     torch.cuda.synchronize()
     h_sel = sel.cpu().numpy()

@@ -153,10 +153,27 @@ def test_ring_rekey_invalid_arguments_and_the_empty_batch():
     assert call(r=1 << 62) == -1 and b"too large" in L.rs_last_error()
     assert call(r=(1 << 64) - 1) == -1 and b"too large" in L.rs_last_error()
     assert call(r=1 << 40) == -1 and b"too large for one launch" in L.rs_last_error()    # fits the address space, not one launch
+    # an out that shares a byte with an input is refused: the kernels add into it with atomics after an init kernel has set it, so
+    # there is no re-keying in place. Every range named below lies inside one allocation of four ciphertexts or inside the key (six)
+    arena = _dev(_words(rng, 4, 2, N))
+    held, held_key = arena.cpu().numpy(), key.cpu().numpy()
+    A, K, ct = arena.data_ptr(), key.data_ptr(), 8 * N
+    for o in (A, A + ct, A + 2 * ct - 4):                                     # out == rlwe, one ciphertext into it, on its last word
+        assert call(o=vp(o), c=vp(A)) == -1 and b"out overlaps rlwe" in L.rs_last_error()
+    assert call(o=vp(A), c=vp(A + 2 * ct - 4)) == -1 and b"out overlaps rlwe" in L.rs_last_error()    # out's last word is rlwe's first
+    for o in (K, K + ct, K + 4 * ct):                                         # out on the key's first and second row and its last two
+        assert call(o=vp(o)) == -1 and b"out overlaps ring_key" in L.rs_last_error()
+    with pytest.raises(ValueError, match="out overlaps rlwe"):
+        be.ring_rekey(arena[:2], key, 4, 5, out=arena[:2])
+    with pytest.raises(ValueError, match="out overlaps rlwe"):
+        be.ring_rekey(arena[:2], key, 4, 5, out=arena[1:3])
+    with pytest.raises(ValueError, match="out overlaps ring_key"):
+        be.ring_rekey(rl, key, 4, 5, out=key[4:])
     # nothing above launched anything; R = 0 is a no-op
     assert call(r=0) == 0
     torch.cuda.synchronize()
     assert bool((out == 7).all())
+    assert np.array_equal(arena.cpu().numpy(), held) and np.array_equal(key.cpu().numpy(), held_key)
     assert call() == 0
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), keygen.ring_rekey(rl.cpu().numpy(), key.cpu().numpy(), 4, 5))

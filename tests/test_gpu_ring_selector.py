@@ -165,10 +165,25 @@ def test_selector_invalid_arguments_and_the_empty_call():
     for bad in (0, -1, 65537):
         assert call(n=bad) == -1 and b"n_src" in L.rs_last_error() and b"outside 1 .. 65536" in L.rs_last_error()
     assert call(k=vp(key.data_ptr() + 4)) == -1 and b"16-byte aligned" in L.rs_last_error()
+    # a sel that shares a byte with an input is refused: the kernels add into it with atomics after an init kernel has zeroed it.
+    # Every range named below lies inside one allocation of sixteen ring samples (sel is twelve) or inside the key (132)
+    arena = _dev(_words(rng, 16, 2, N))
+    held, held_key = arena.cpu().numpy(), key.cpu().numpy()
+    A, K, row, ring = arena.data_ptr(), key.data_ptr(), 4 * (n_src + 1), 8 * N
+    for o in (A, A + row, A + depth * l * row - 4):                           # sel == ct, one sample into ct, on its last word
+        assert call(o=vp(o), c=vp(A)) == -1 and b"sel overlaps ct" in L.rs_last_error()
+    assert call(o=vp(A), c=vp(A + 12 * ring - 4)) == -1 and b"sel overlaps ct" in L.rs_last_error()   # sel's last word is ct's first
+    for o in (K, K + ring, K + 120 * ring):                                   # sel on the key's first, second and last twelve samples
+        assert call(o=vp(o)) == -1 and b"sel overlaps sel_key" in L.rs_last_error()
+    with pytest.raises(ValueError, match="sel overlaps ct"):
+        be.ring_selector(arena.view(-1)[:depth * l * (n_src + 1)].view(depth * l, n_src + 1), 4, l, key, 4, ks_t, out=arena[:12])
+    with pytest.raises(ValueError, match="sel overlaps sel_key"):
+        be.ring_selector(ct, 4, l, key, 4, ks_t, out=key.view(-1, 2, N)[120:])
     # nothing above launched anything; depth = 0 is a no-op
     assert call(d=0) == 0
     torch.cuda.synchronize()
     assert bool((out == 7).all())
+    assert np.array_equal(arena.cpu().numpy(), held) and np.array_equal(key.cpu().numpy(), held_key)
     assert call() == 0
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), keygen.ring_selector_switch(ct.cpu().numpy(), 4, l, key.cpu().numpy(), 4, ks_t))
@@ -182,6 +197,28 @@ def test_selector_invalid_arguments_and_the_empty_call():
     big = other.selector_key(8, 1, MASK_SEED, NOISE_SEED, stdev=2.0 ** -31)
     with pytest.raises(ValueError, match="N = 4096"):
         be.upload_selector_key(big)
+    # the composed call refuses the same overlaps and those of its scratch (3,282 words here). It looks at them behind the check
+    # for a loaded key, so the context gets one of random words; nothing below launches anything else
+    be.load_synthetic_keys(5)
+    key16 = _dev(_words(rng, 2, be.W, ks_t, 2, N))                           # a key of the context's n = 16
+    out.fill_(7)
+    torch.cuda.synchronize()
+    words = scratch.numel()
+    assert words == l * N + depth * l * (2 * be.W + 1)
+    for o in (A, A + 4 * be.W, A + 4 * (depth * be.W - 1)):                   # sel == bits, one bit into them, on their last word
+        assert boot(o=vp(o), c=vp(A), k=P(key16)) == -1 and b"sel overlaps bits" in L.rs_last_error()
+    assert boot(o=P(key16), k=P(key16)) == -1 and b"sel overlaps sel_key" in L.rs_last_error()
+    assert boot(o=vp(A), sc=vp(A), k=P(key16)) == -1 and b"sel overlaps scratch" in L.rs_last_error()
+    assert boot(o=vp(A), sc=vp(A + 12 * ring - 4), k=P(key16)) == -1 and b"sel overlaps scratch" in L.rs_last_error()   # sel's last word
+    assert boot(o=vp(A + 4 * (words - 1)), sc=vp(A), k=P(key16)) == -1 and b"sel overlaps scratch" in L.rs_last_error()  # scratch's last word
+    assert boot(c=vp(A + 4 * (words - 1)), sc=vp(A), k=P(key16)) == -1 and b"scratch overlaps bits" in L.rs_last_error()
+    assert boot(sc=P(key16), k=P(key16)) == -1 and b"scratch overlaps sel_key" in L.rs_last_error()
+    with pytest.raises(ValueError, match="sel overlaps bits"):
+        be.circuit_bootstrap(arena.view(-1)[:depth * be.W].view(depth, be.W), 4, l, key16, 4, ks_t, out=arena[:12])
+    with pytest.raises(ValueError, match="sel overlaps sel_key"):
+        be.circuit_bootstrap(bits, 4, l, key16, 4, ks_t, out=key16.view(-1, 2, N)[:12])
+    torch.cuda.synchronize()
+    assert bool((out == 7).all()) and np.array_equal(arena.cpu().numpy(), held)
 
 
 @pytest.fixture(scope="module")
