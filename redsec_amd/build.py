@@ -73,9 +73,9 @@ HIP_OBJECTS = [
     ("rs_api_client", "rs_api_client.cpp", []),
 ]
 HIP_SOURCES = [src for _, src, _ in HIP_OBJECTS]
-HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
+HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
 EMU_SOURCES = ["rs_emulate.cpp"]
-EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
+EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
 
 
 def _abs(paths):

@@ -46,10 +46,7 @@ constexpr bool kHalfExchangeSwaps = (kBits & 64) == 0;
 constexpr bool kHalfKeyProbe = (kBits & 128) != 0;
 constexpr bool kKsSampleProbe = (kBits & 512) != 0;
 constexpr bool kWrongOnPurpose = kNoKeyProbe || kHalfExchangeProbe || kHalfKeyProbe || kKsSampleProbe;   // timing probes: rs_api.cpp then gates and enforces nothing
-// key rows of CMUX step i: step 0's under the probe
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
+// key rows of CMUX step i: step 0's under the probe (constexpr: callable from host and device code alike under hipcc)
 constexpr int key_step(int i) { return kNoKeyProbe ? 0 : i; }
 constexpr int kStampPhases = 8;
 }  // namespace diag

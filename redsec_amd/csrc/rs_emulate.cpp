@@ -1354,8 +1354,8 @@ int rs_emu_pack_window_word(int N, int k0, int c0, int cpad, int x, int cc) {
 int rs_emu_pack_tile() { return rs::kPaTile; }
 int rs_emu_pack_slots() { return rs::kPaSlots; }
 // pack_init_kernel, then pack_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over (tile,
-// polynomial, slot block, index chunk, ciphertext), the transposed sample words of the chunk, the staged window per key row, a 4-word
-// chunk per thread and four scalar digits, the negated partial sums added into the output
+// polynomial, slot block, index chunk, ciphertext), the transposed sample words of the chunk, the staged window per key row,
+// ring_sweep (rs_ring_sweep.h, the kernel's own) over the block's slots, the negated partial sums added into the output
 void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pack_key, int basebit, int t, int32_t* rlwe) {
   if (count <= 0) return;
   const long R = (count + N - 1) / N;
@@ -1367,10 +1367,10 @@ void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pac
     out[idx] = (w >= N && s < count) ? (uint32_t)ct[(size_t)s * ((size_t)n + 1) + n] : 0u;
   }
   const int tiles = N / rs::kPaTile, sbs = rs::pa_slot_blocks(count, N), chunks = rs::pa_chunks(n);
-  const uint32_t off = rs::pa_offset(basebit, t), mask = (1u << basebit) - 1u;
+  const uint32_t off = rs::pa_offset(basebit, t);
   const uint32_t* key = reinterpret_cast<const uint32_t*>(pack_key);
   std::vector<uint32_t> win((size_t)rs::kPaSlots + rs::kPaTile), sa((size_t)rs::kPaSeg * rs::kPaSlots);
-  std::vector<uint32_t> acc((size_t)rs::kPaTile);
+  uint32_t acc[rs::kPaThreads][rs::kPaKpt];
   for (long blk = 0; blk < rs::pa_groups(count, n, N); ++blk) {
     long g = blk;
     const int tile = (int)(g % tiles); g /= tiles;
@@ -1384,7 +1384,7 @@ void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pac
     const int i0 = chunk * rs::kPaSeg, segn = n - i0 < rs::kPaSeg ? n - i0 : rs::kPaSeg;
     const int k0 = tile * rs::kPaTile, wb = rs::pa_window_base(N, k0, c0, cpad);
     const uint32_t* cts = reinterpret_cast<const uint32_t*>(ct) + ((size_t)r * N + c0) * ((size_t)n + 1);
-    std::fill(acc.begin(), acc.end(), 0u);
+    std::memset(acc, 0, sizeof(acc));
     for (int idx = 0; idx < segn * cpad; ++idx) {
       const int cc = idx / segn, ii = idx - cc * segn;
       sa[(size_t)ii * cpad + cc] = cc < cn ? cts[(size_t)cc * ((size_t)n + 1) + i0 + ii] + off : 0u;
@@ -1392,26 +1392,12 @@ void rs_emu_pack(const int32_t* ct, long count, int n, int N, const int32_t* pac
     for (int ii = 0; ii < segn; ++ii)
       for (int j = 0; j < t; ++j) {
         const uint32_t* p = key + rs::pa_key_offset(N, t, i0 + ii, j, poly);
-        for (int x = 0; x < cpad + rs::kPaTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
-        const int shift = 32 - (j + 1) * basebit;
-        for (int th = 0; th < rs::kPaThreads; ++th) {
-          uint32_t* a4 = &acc[(size_t)rs::kPaKpt * th];
-          int c4 = th + cpad / 4;
-          const uint32_t* hi = &win[4 * (size_t)c4];
-          for (int q4 = 0; q4 < cpad / 4; ++q4) {
-            const uint32_t* av = &sa[(size_t)ii * cpad + 4 * q4];
-            const uint32_t* lo = &win[4 * (size_t)(--c4)];
-            const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            for (int b = 0; b < 4; ++b) {
-              const uint32_t d = (av[b] >> shift) & mask;
-              for (int q = 0; q < rs::kPaKpt; ++q) a4[q] += w[4 + q - b] * d;
-            }
-            hi = lo;
-          }
-        }
+        for (int th = 0; th < rs::kPaThreads; ++th) rs::sweep_stage_window(win.data(), p, N, wb, cpad + rs::kPaTile, th, rs::kPaThreads);
+        for (int th = 0; th < rs::kPaThreads; ++th)
+          rs::ring_sweep(win.data(), &sa[(size_t)ii * cpad], cpad, th, [=](uint32_t abar) { return rs::pa_digit(abar, basebit, j); }, acc[th]);
       }
     uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0;
-    for (int x = 0; x < rs::kPaTile; ++x) o[x] += 0u - acc[x];
+    for (int x = 0; x < rs::kPaTile; ++x) o[x] += 0u - acc[x / rs::kPaKpt][x % rs::kPaKpt];
   }
 }
 
@@ -1513,10 +1499,10 @@ uint32_t rs_emu_ring_rekey_digit(uint32_t abar, int basebit, int j) { return rs:
 int rs_emu_ring_rekey_tile() { return rs::kRrTile; }
 int rs_emu_ring_rekey_slots() { return rs::kRrSlots; }
 long rs_emu_ring_rekey_groups(long R, int N, int t) { return rs::rr_groups(R, N, t); }
-int rs_emu_ring_rekey_window_base(int N, int k0, int c0) { return rs::rr_window_base(N, k0, c0); }
-// ring_rekey_init_kernel, then ring_rekey_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over
-// (tile, polynomial, source block, digit, ciphertext), the staged window of the key row and the block's words a_k + offset, a 4-word
-// chunk per thread and four scalar odd digits, the negated partial sums added into the output
+int rs_emu_ring_rekey_window_base(int N, int k0, int c0) { return rs::ring_window_base(N, k0, c0); }
+// ring_rekey_init_kernel, then ring_rekey_kernel workgroup by workgroup and thread by thread as the kernel places them: ring_place
+// over (tile, polynomial, source block, digit, ciphertext), the staged window of the key row and the block's words a_k + offset,
+// ring_sweep (rs_ring_sweep.h, the kernel's own) with the odd digit, the negated partial sums added into the output
 void rs_emu_ring_rekey(const int32_t* rlwe, long R, int N, const int32_t* ring_key, int basebit, int t, int32_t* out_) {
   if (R <= 0) return;
   uint32_t* out = reinterpret_cast<uint32_t*>(out_);
@@ -1526,38 +1512,21 @@ void rs_emu_ring_rekey(const int32_t* rlwe, long R, int N, const int32_t* ring_k
     const int w = (int)(idx & (2 * (long)N - 1));
     out[idx] = (w >= N ? in[idx] : 0u) - key[rs::rr_key_offset(N, t, 0) + (size_t)w];
   }
-  const int tiles = rs::rr_tiles(N), blocks = rs::rr_blocks(N);
-  const uint32_t off = rs::rr_offset(basebit, t), mask = (1u << basebit) - 1u;
-  std::vector<uint32_t> win((size_t)rs::kRrSlots + rs::kRrTile), sa((size_t)rs::kRrSlots);
+  const uint32_t off = rs::rr_offset(basebit, t);
+  std::vector<uint32_t> win((size_t)rs::kRingWindow), sa((size_t)rs::kRingSlots);
   for (long blk = 0; blk < rs::rr_groups(R, N, t); ++blk) {
-    long g = blk;
-    const int tile = (int)(g % tiles); g /= tiles;
-    const int poly = (int)(g & 1); g >>= 1;
-    const int sb = (int)(g % blocks); g /= blocks;
-    const int j = (int)(g % t);
-    const long r = g / t;
-    const int c0 = sb * rs::kRrSlots, k0 = tile * rs::kRrTile, wb = rs::rr_window_base(N, k0, c0);
-    const int shift = 32 - (j + 1) * basebit;
-    const uint32_t* src = in + (size_t)r * 2 * N + c0;
-    const uint32_t* p = key + rs::rr_key_offset(N, j, poly);
-    for (int x = 0; x < rs::kRrSlots + rs::kRrTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
-    for (int cc = 0; cc < rs::kRrSlots; ++cc) sa[cc] = src[cc] + off;
-    for (int th = 0; th < rs::kRrThreads; ++th) {
-      uint32_t acc[rs::kRrKpt] = {0u, 0u, 0u, 0u};
-      int c4 = th + rs::kRrSlots / 4;
-      const uint32_t* hi = &win[4 * (size_t)c4];
-      for (int q4 = 0; q4 < rs::kRrSlots / 4; ++q4) {
-        const uint32_t* av = &sa[4 * (size_t)q4];
-        const uint32_t* lo = &win[4 * (size_t)(--c4)];
-        const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        for (int b = 0; b < 4; ++b) {
-          const uint32_t d = 2u * ((av[b] >> shift) & mask) - mask;
-          for (int q = 0; q < rs::kRrKpt; ++q) acc[q] += w[4 + q - b] * d;
-        }
-        hi = lo;
-      }
-      uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0 + rs::kRrKpt * th;
-      for (int q = 0; q < rs::kRrKpt; ++q) o[q] += 0u - acc[q];
+    const rs::RingPlace pl = rs::ring_place((unsigned)blk, N, t);
+    const int j = pl.row, c0 = pl.sb * rs::kRingSlots, k0 = pl.tile * rs::kRingTile;
+    const uint32_t* src = in + (size_t)pl.r * 2 * N + c0;
+    const uint32_t* p = key + rs::rr_key_offset(N, j, pl.poly);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      rs::sweep_stage_window(win.data(), p, N, rs::ring_window_base(N, k0, c0), rs::kRingWindow, th, rs::kRingThreads);
+    for (int cc = 0; cc < rs::kRingSlots; ++cc) sa[cc] = src[cc] + off;
+    for (int th = 0; th < rs::kRingThreads; ++th) {
+      uint32_t acc[rs::kSweepKpt] = {0u, 0u, 0u, 0u};
+      rs::ring_sweep(win.data(), sa.data(), rs::kRingSlots, th, [=](uint32_t abar) { return rs::rr_digit(abar, basebit, j); }, acc);
+      uint32_t* o = out + ((size_t)pl.r * 2 + pl.poly) * N + k0 + rs::kSweepKpt * th;
+      for (int q = 0; q < rs::kSweepKpt; ++q) o[q] += 0u - acc[q];
     }
   }
 }
@@ -1567,10 +1536,10 @@ uint32_t rs_emu_ring_cmux_offset(int basebit, int l) { return rs::rc_offset(base
 uint32_t rs_emu_ring_cmux_digit(uint32_t xbar, int basebit, int j) { return rs::rc_digit(xbar, basebit, j); }
 long rs_emu_ring_cmux_groups(long R, int N, int l) { return rs::rc_groups(R, N, l); }
 long rs_emu_ring_lookup_scratch_rows(long entries) { return rs::rc_scratch_rows(entries); }
-// ring_cmux_init_kernel, then ring_cmux_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over
-// (tile, polynomial, source block, selector row, ciphertext), the staged window of the selector row and the block's words
-// d1 - d0 + offset (-d0 + offset under a null d1), a 4-word chunk per thread and four scalar signed digits, the partial sums added
-// into the output
+// ring_cmux_init_kernel, then ring_cmux_kernel workgroup by workgroup and thread by thread as the kernel places them: ring_place
+// over (tile, polynomial, source block, selector row, ciphertext), the staged window of the selector row and the block's words
+// d1 - d0 + offset (-d0 + offset under a null d1), ring_sweep (rs_ring_sweep.h, the kernel's own) with the signed digit, the
+// partial sums added into the output
 void rs_emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long stride, int N, const int32_t* sel_, int basebit, int l,
                       int32_t* out_) {
   if (R <= 0) return;
@@ -1580,39 +1549,22 @@ void rs_emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long strid
   const uint32_t* sel = reinterpret_cast<const uint32_t*>(sel_);
   const long per = 2 * (long)N;
   for (long idx = 0; idx < R * per; ++idx) out[idx] = d0[(size_t)(idx / per) * (size_t)stride * (size_t)per + (size_t)(idx % per)];
-  const int tiles = rs::rc_tiles(N), blocks = rs::rc_blocks(N);
-  const uint32_t off = rs::rc_offset(basebit, l), mask = (1u << basebit) - 1u, half = 1u << (basebit - 1);
-  std::vector<uint32_t> win((size_t)rs::kRcSlots + rs::kRcTile), sx((size_t)rs::kRcSlots);
+  const uint32_t off = rs::rc_offset(basebit, l);
+  std::vector<uint32_t> win((size_t)rs::kRingWindow), sx((size_t)rs::kRingSlots);
   for (long blk = 0; blk < rs::rc_groups(R, N, l); ++blk) {
-    long g = blk;
-    const int tile = (int)(g % tiles); g /= tiles;
-    const int poly = (int)(g & 1); g >>= 1;
-    const int sb = (int)(g % blocks); g /= blocks;
-    const int jr = (int)(g % (2 * l));
-    const long r = g / (2 * l);
-    const int j = jr < l ? jr : jr - l, spoly = jr < l ? 0 : 1;
-    const int c0 = sb * rs::kRcSlots, k0 = tile * rs::kRcTile, wb = rs::rc_window_base(N, k0, c0);
-    const int shift = 32 - (j + 1) * basebit;
-    const size_t src_at = ((size_t)r * (size_t)stride * 2 + (size_t)spoly) * (size_t)N + (size_t)c0;
-    const uint32_t* p = sel + rs::rc_sel_offset(N, jr, poly);
-    for (int x = 0; x < rs::kRcSlots + rs::kRcTile; ++x) win[x] = rs::rl_ext_word(p, N, wb + x);
-    for (int cc = 0; cc < rs::kRcSlots; ++cc) sx[cc] = (d1 ? d1[src_at + cc] : 0u) - d0[src_at + cc] + off;
-    for (int th = 0; th < rs::kRcThreads; ++th) {
-      uint32_t acc[rs::kRcKpt] = {0u, 0u, 0u, 0u};
-      int c4 = th + rs::kRcSlots / 4;
-      const uint32_t* hi = &win[4 * (size_t)c4];
-      for (int q4 = 0; q4 < rs::kRcSlots / 4; ++q4) {
-        const uint32_t* xv = &sx[4 * (size_t)q4];
-        const uint32_t* lo = &win[4 * (size_t)(--c4)];
-        const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        for (int b = 0; b < 4; ++b) {
-          const uint32_t d = ((xv[b] >> shift) & mask) - half;
-          for (int q = 0; q < rs::kRcKpt; ++q) acc[q] += w[4 + q - b] * d;
-        }
-        hi = lo;
-      }
-      uint32_t* o = out + ((size_t)r * 2 + poly) * N + k0 + rs::kRcKpt * th;
-      for (int q = 0; q < rs::kRcKpt; ++q) o[q] += acc[q];
+    const rs::RingPlace pl = rs::ring_place((unsigned)blk, N, 2 * l);
+    const int jr = pl.row, j = jr < l ? jr : jr - l, spoly = jr < l ? 0 : 1;
+    const int c0 = pl.sb * rs::kRingSlots, k0 = pl.tile * rs::kRingTile;
+    const size_t src_at = ((size_t)pl.r * (size_t)stride * 2 + (size_t)spoly) * (size_t)N + (size_t)c0;
+    const uint32_t* p = sel + rs::rc_sel_offset(N, jr, pl.poly);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      rs::sweep_stage_window(win.data(), p, N, rs::ring_window_base(N, k0, c0), rs::kRingWindow, th, rs::kRingThreads);
+    for (int cc = 0; cc < rs::kRingSlots; ++cc) sx[cc] = (d1 ? d1[src_at + cc] : 0u) - d0[src_at + cc] + off;
+    for (int th = 0; th < rs::kRingThreads; ++th) {
+      uint32_t acc[rs::kSweepKpt] = {0u, 0u, 0u, 0u};
+      rs::ring_sweep(win.data(), sx.data(), rs::kRingSlots, th, [=](uint32_t xbar) { return rs::rc_digit(xbar, basebit, j); }, acc);
+      uint32_t* o = out + ((size_t)pl.r * 2 + pl.poly) * N + k0 + rs::kSweepKpt * th;
+      for (int q = 0; q < rs::kSweepKpt; ++q) o[q] += acc[q];
     }
   }
 }

@@ -13,7 +13,7 @@
 
 #include <cstdint>
 
-#include "rs_rlwe.h"
+#include "rs_ring_sweep.h"
 
 namespace rs {
 
@@ -21,11 +21,12 @@ enum { kKgPackMask = 14, kKgPackNoise = 15 };
 
 // Placement of pack_kernel: a workgroup of kPaThreads threads owns kPaTile = 4 kPaThreads consecutive output coefficients of one
 // polynomial of one ciphertext (thread t the four coefficients k0 + 4t .. k0 + 4t + 3, in registers), a block of at most kPaSlots
-// slots c and a chunk of kPaSeg consecutive LWE indices i (all t digits of each; the last chunk has n mod kPaSeg). The grid runs
+// slots c and a chunk of kPaSeg consecutive LWE indices i (all t digits of each; the last chunk has n mod kPaSeg); per key row it
+// runs the sweep of rs_ring_sweep.h over the block's slots. The grid runs
 // over (tile, polynomial, slot block, index chunk, ciphertext); the partial sums meet in the output by atomic adds. The chunk has
 // ONE size, so there is one path and one split per n: a workgroup stages its samples' words once, and more indices per workgroup
 // would save nothing but some of the 4-byte atomic adds (one per output word and workgroup against 4 kPaSeg t slots multiply-adds).
-constexpr int kPaThreads = 128, kPaKpt = 4, kPaTile = kPaThreads * kPaKpt;
+constexpr int kPaThreads = 128, kPaKpt = kSweepKpt, kPaTile = kPaThreads * kPaKpt;
 constexpr int kPaMinN = 1024, kPaMaxN = 8192;
 constexpr int kPaSlots = 1024;          // slots of a slot block: bounds the LDS of a workgroup on every ring
 constexpr int kPaSeg = 8;               // LWE indices of a chunk: their sample words are staged (transposed) in LDS, 32 bytes a sample

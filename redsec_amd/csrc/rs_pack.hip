@@ -9,20 +9,19 @@
 // of at most kPaSlots slots c0 .. c0 + cn - 1 and a chunk of kPaSeg = 8 LWE indices (rs_pack.h: one ciphertext alone has only
 // 2 N / 512 tiles, with the chunks default-128 has 316 workgroups per ciphertext). Per key row (i, j) it stages the window of
 // ext = (-p, p) its coefficients and slots read, cpad + kPaTile words with cpad = cn rounded up to 4, so that ten slots stage and sweep
-// ten slots, not N. Thread t keeps coefficients k0 + 4t .. k0 + 4t + 3 in registers over all its rows; four consecutive slots need
-// seven window words, two aligned 16-byte chunks of which the upper one is the previous step's lower one: ONE 16-byte LDS read per
-// thread serves 16 multiply-adds (the compiler splits it into ds_read_b32, ds_read2_b32, ds_read_b32). The sample words of the chunk,
-// kPaSeg consecutive i per sample (32 contiguous bytes), are read once and transposed through LDS into s_a[ii][c] = a_i + offset,
-// zero in the padding: the sweep over c reads them as one 16-byte broadcast (ds_read_b128) per four slots and never walks a column
-// of ct at stride n + 1. The digit of slot c is the same in every lane: the word is
-// made a scalar (readfirstlane) and the digit is cut out by scalar shift and mask.
-// Multiply-add form (tools/isa_scan.py on this object): the compiler emits v_mul_lo_u32 with the scalar digit as one operand and folds
-// the adds pairwise into v_add3_u32 -- 16 v_mul_lo_u32 and 8 v_add3_u32 per four slots and lane; no v_mad_u64_u32, whose 64-bit
-// accumulator would double the registers of acc for the same 4.3-cycle issue (MEASUREMENTS.md section 4.1).
+// ten slots, not N, and runs the sweep of rs_ring_sweep.h (the LDS read pattern, the scalar digit and the multiply-add form are
+// described there) with pa_digit; thread t keeps its four coefficients in registers over all its rows. What is this kernel's own:
+// the sample words of the chunk, kPaSeg consecutive i per sample (32 contiguous bytes), are read once and transposed through LDS
+// into s_a[ii][c] = a_i + offset, zero in the padding, so that the sweep over c reads them as its 16-byte broadcast per four slots
+// and never walks a column of ct at stride n + 1; and the loop over the key rows, each staged between two barriers.
+// THE SWEEP IS WRITTEN OUT HERE, not a call of ring_sweep: with the call this kernel compiled to the same instruction mix in
+// another order and measured 8.2 % slower at 1,024 slots and 3.1 % at 65,536 (profiles/r29/, same box, three runs a side), where
+// ring_rekey_kernel and ring_cmux_kernel kept their times. So this is the ONE copy of ring_sweep left: a change to the loop in
+// rs_ring_sweep.h has to be made below too. rs_emu_pack (rs_emulate.cpp) walks the same workgroups and rows on the CPU and does
+// call ring_sweep, so tests/test_pack_cpu.py pins the shared loop and the placement, not the lines below.
 // The partial sums of the slot blocks and index chunks meet by vector atomicAdd (global_atomic_add_u32, no return) on the words that
 // pack_init_kernel has set on the same stream just before; every call initialises again, so a second call into the same buffer gives
-// the same words. rs_emu_pack (rs_emulate.cpp) walks the same workgroup / row / four-slot loop on the CPU as a second copy,
-// not as shared code: a change to the loop below has to be made there too, or tests/test_pack_cpu.py stops pinning this kernel.
+// the same words.
 // Resources (-Rpass-analysis=kernel-resource-usage): pack_kernel 35 VGPRs, 48 SGPRs, (9 cpad + 512) 4 bytes of dynamic LDS (2.5 KB at
 // ten slots, 38.0 KB at 1,024), no scratch, no static LDS, eight waves per SIMD by registers (four workgroups per CU by LDS at full
 // slot blocks); pack_init_kernel 13 VGPRs, no LDS, no scratch.
@@ -79,6 +78,7 @@ __global__ __launch_bounds__(kPaThreads) void pack_kernel(PackArgs a, int chunks
       __syncthreads();                                    // the previous row's sweep has read the window
       for (int x = t; x < cpad + kPaTile; x += kPaThreads) s_win[x] = rl_ext_word(p, N, wb + x);
       __syncthreads();
+      // ring_sweep(s_win, s_a + ii * cpad, cpad, t, pa_digit(., basebit, j), acc), written out (see the header comment)
       const int shift = 32 - (j + 1) * a.basebit;
       int c4 = t + cpad / 4;                              // chunk of window words 4t + cpad - cc .. + 3, cc = 0
       uint4 hi = win4[c4];

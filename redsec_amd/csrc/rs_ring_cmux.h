@@ -21,15 +21,12 @@
 
 namespace rs {
 
-// Placement of ring_cmux_kernel (ring_rekey_kernel's, the digit source the difference of two ciphertexts): a workgroup of kRcThreads
-// threads owns kRcTile = 4 kRcThreads consecutive output coefficients of one polynomial of one output ciphertext (thread t the four
-// coefficients k0 + 4t .. k0 + 4t + 3, in registers), ONE block of kRcSlots consecutive source coefficients and ONE selector row
-// jr < 2l: row jr takes digit jr mod l of polynomial jr / l of x. The grid runs over (tile, polynomial, source block, row,
-// ciphertext): 2 (N / 512) (N / 1024) 2l workgroups per ciphertext; the partial sums meet in the output by atomic adds on the words
-// ring_cmux_init_kernel has set. N is a power of two in kRcMinN .. kRcMaxN.
-constexpr int kRcThreads = kRrThreads, kRcKpt = kRrKpt, kRcTile = kRrTile;
-constexpr int kRcMinN = kRrMinN, kRcMaxN = kRrMaxN;
-constexpr int kRcSlots = kRrSlots;      // source coefficients of a block: bounds the LDS of a workgroup on every ring
+// Placement of ring_cmux_kernel: the ring placement of rs_ring_sweep.h (kRc* name it here), the key row the selector row jr < 2l,
+// which takes digit jr mod l of polynomial jr / l of x. The grid runs over (tile, polynomial, source block, row, ciphertext):
+// 2 (N / 512) (N / 1024) 2l workgroups per ciphertext; the partial sums meet in the output by atomic adds on the words
+// ring_cmux_init_kernel has set.
+constexpr int kRcThreads = kRingThreads, kRcTile = kRingTile, kRcSlots = kRingSlots;
+constexpr int kRcMinN = kRingMinN, kRcMaxN = kRingMaxN;
 constexpr int kRcInitThreads = 256;     // threads of a workgroup of ring_cmux_init_kernel (one output word each)
 constexpr int kRcMaxBits = 31;          // l basebit <= 31: the half step 2^(31 - l basebit) is an integer
 constexpr int kRcMaxDepth = 30;         // levels of a lookup: 2^depth entries stay below 2^31
@@ -45,17 +42,12 @@ RS_HD uint32_t rc_digit(uint32_t xbar, int basebit, int j) {
   return ((xbar >> (32 - (j + 1) * basebit)) & ((1u << basebit) - 1u)) - (1u << (basebit - 1));
 }
 
-RS_HD int rc_tiles(int N) { return rr_tiles(N); }
-RS_HD int rc_blocks(int N) { return rr_blocks(N); }
 // workgroups of one ciphertext and of a launch
-RS_HD long rc_groups_per_ct(int N, int l) { return 2L * rc_tiles(N) * rc_blocks(N) * 2 * l; }
+RS_HD long rc_groups_per_ct(int N, int l) { return ring_groups_per_ct(N, 2 * l); }
 RS_HD long rc_groups(long R, int N, int l) { return R * rc_groups_per_ct(N, l); }
 
 // polynomial poly of selector row jr of sel [2l][2][N]
 RS_HD size_t rc_sel_offset(int N, int jr, int poly) { return ((size_t)jr * 2 + poly) * (size_t)N; }
-
-// The window of ext = (-p, p) a workgroup stages: rs_ring_rekey.h's, the same tile and block sizes.
-RS_HD int rc_window_base(int N, int k0, int c0) { return rr_window_base(N, k0, c0); }
 
 // rs_ring_lookup_dev: level k halves the rows. rows -> pairs (2r, 2r + 1) and, for an odd count, one unpaired last row
 RS_HD long rc_level_rows(long rows) { return (rows + 1) / 2; }

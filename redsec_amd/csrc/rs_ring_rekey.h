@@ -15,19 +15,16 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "rs_pack.h"
+#include "rs_ring_sweep.h"
 
 namespace rs {
 
-// Placement of ring_rekey_kernel (pack_kernel's, the digit source the input's own a polynomial): a workgroup of kRrThreads threads
-// owns kRrTile = 4 kRrThreads consecutive output coefficients of one polynomial of one ciphertext (thread t the four coefficients
-// k0 + 4t .. k0 + 4t + 3, in registers), ONE block of kRrSlots consecutive source coefficients k and ONE digit j. The grid runs over
-// (tile, polynomial, source block, digit, ciphertext): 2 (N / 512) (N / 1024) t workgroups per ciphertext, 4 t at N = 1024 and
-// 256 t at N = 8192; the partial sums meet in the output by atomic adds on the words ring_rekey_init_kernel has set. N is a power
-// of two in kRrMinN .. kRrMaxN, so a source block is always full and a tile never straddles a polynomial.
-constexpr int kRrThreads = 128, kRrKpt = 4, kRrTile = kRrThreads * kRrKpt;
-constexpr int kRrMinN = 1024, kRrMaxN = 8192;
-constexpr int kRrSlots = 1024;          // source coefficients of a block: bounds the LDS of a workgroup on every ring
+// Placement of ring_rekey_kernel: the ring placement of rs_ring_sweep.h (kRr* and rr_* name it here), the key row the digit j < t
+// and the digit source the input's own a polynomial. The grid runs over (tile, polynomial, source block, digit, ciphertext):
+// 2 (N / 512) (N / 1024) t workgroups per ciphertext, 4 t at N = 1024 and 256 t at N = 8192; the partial sums meet in the output by
+// atomic adds on the words ring_rekey_init_kernel has set.
+constexpr int kRrThreads = kRingThreads, kRrTile = kRingTile, kRrSlots = kRingSlots;
+constexpr int kRrMinN = kRingMinN, kRrMaxN = kRingMaxN;
 constexpr int kRrInitThreads = 256;     // threads of a workgroup of ring_rekey_init_kernel (one output word each)
 constexpr int kRrMaxBits = 31;          // t basebit <= 31: h_j = 2^(31 - (j+1) basebit) is an integer
 
@@ -39,18 +36,11 @@ RS_HD uint32_t rr_digit(uint32_t abar, int basebit, int j) {
   return 2u * ((abar >> (32 - (j + 1) * basebit)) & mask) - mask;
 }
 
-RS_HD int rr_tiles(int N) { return N / kRrTile; }
-RS_HD int rr_blocks(int N) { return N / kRrSlots; }
 // workgroups of one ciphertext and of a call
-RS_HD long rr_groups_per_ct(int N, int t) { return 2L * rr_tiles(N) * rr_blocks(N) * t; }
+RS_HD long rr_groups_per_ct(int N, int t) { return ring_groups_per_ct(N, t); }
 RS_HD long rr_groups(long R, int N, int t) { return R * rr_groups_per_ct(N, t); }
 
 // polynomial poly of key row j of ring_key [t+1][2][N]
 RS_HD size_t rr_key_offset(int N, int j, int poly) { return ((size_t)j * 2 + poly) * (size_t)N; }
-
-// A workgroup with first coefficient k0 and first source coefficient c0 stages the words ext[rr_window_base + i], i < kRrSlots +
-// kRrTile, of ext = (-p, p) (rs_rlwe.h): coefficient k0 + x of X^(c0 + cc) p is window word pa_window_index(kRrSlots, x, cc).
-// 0 <= rr_window_base and rr_window_base + kRrSlots + kRrTile <= 2 N for every tile and block.
-RS_HD int rr_window_base(int N, int k0, int c0) { return pa_window_base(N, k0, c0, kRrSlots); }
 
 }  // namespace rs

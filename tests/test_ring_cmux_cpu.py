@@ -365,6 +365,6 @@ def test_ring_cmux_sources_are_integer_only():
     """As rs_pack.*, rs_rekey.* and rs_ring_rekey.*: the sources name no floating type and include neither a transform nor the
     split-key product."""
     csrc = os.path.join(ROOT, "redsec_amd", "csrc")
-    for f in ("rs_ring_cmux.h", "rs_ring_cmux.hip"):
+    for f in ("rs_ring_cmux.h", "rs_ring_cmux.hip", "rs_ring_sweep.h"):
         code = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, f)).read().splitlines())
         assert not re.search(r"\b(double|float|half|__fp16|_Float16)\b|rs_general\.h|rs_fft\.h|rs_ntt\.h", code), f

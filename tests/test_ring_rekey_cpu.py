@@ -305,6 +305,6 @@ def test_new_kernels_hold_zero_scratch_and_no_static_lds():
 def test_ring_rekey_sources_are_integer_only():
     """As rs_pack.* and rs_rekey.*: the sources name no floating type and include neither a transform nor the split-key product."""
     csrc = os.path.join(ROOT, "redsec_amd", "csrc")
-    for f in ("rs_ring_rekey.h", "rs_ring_rekey.hip"):
+    for f in ("rs_ring_rekey.h", "rs_ring_rekey.hip", "rs_ring_sweep.h"):
         code = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, f)).read().splitlines())
         assert not re.search(r"\b(double|float|half|__fp16|_Float16)\b|rs_general\.h|rs_fft\.h|rs_ntt\.h", code), f
