@@ -346,6 +346,23 @@ int rs_ring_cmux_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t
  * or entries out of range, a null scratch with depth > 1, and those overlaps ("out overlaps scratch"). */
 int rs_ring_lookup_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
                        const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
+/* The alternating form of the two calls above, for selectors made by circuit bootstrapping. Everything
+ * is as in rs_ring_cmux_dev but the digit: the sign of every other source coefficient is flipped before and after the
+ * decomposition,
+ *   eps_k = +1 for even k, -1 for odd k                      (k = 0 .. N-1, the index of the source coefficient)
+ *   dig'_j(x_k) = eps_k dig_j(eps_k x_k)                     (dig_j, off, h_j those of rs_ring_cmux_dev; dig'_j in -B/2 .. B/2)
+ *   Da_j(X) = sum_k dig'_j(x.a_k) X^k,   Db_j(X) = sum_k dig'_j(x.b_k) X^k
+ * sum_j dig'_j(w) h_j is still w rounded to l basebit bits within the same half step, so the SAME selectors select and phase(out)
+ * = phase(d0) + m (phase(d1) - phase(d0)) + noise. The digit at position k has mean -eps_k / 2 instead of -1/2 and the same mean
+ * square (B^2 + 2)/12: under a client's selector (independent row noise) the variance above holds unchanged. Under a produced
+ * selector (rs_ring_selector_dev, rs_circuit_bootstrap_dev), whose level error is one scalar on the whole digit polynomial, the
+ * means no longer add up along S(X): the ramp ((1 - t_c)^2 + N/4)/4 of section 24 becomes (N/4 + [c odd])/4 on every coefficient.
+ * The same arguments, checks, overlap refusals, error codes, level and scratch plan as rs_ring_cmux_dev / rs_ring_lookup_dev;
+ * asynchronous, no allocation, no loaded key. The words differ from the signed form's; both decrypt to the same selection. */
+int rs_ring_cmux_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride,
+                         const int32_t* sel, int32_t basebit, int32_t l, void* stream);
+int rs_ring_lookup_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
+                           const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
 
 /* Circuit bootstrapping (CGGI17 section 4): the selectors of rs_ring_cmux_dev / rs_ring_lookup_dev made
  * on the server from LWE bits it computed itself. rs_ring_selector_dev is the step in the middle, a keyswitch from LWE samples to

@@ -95,17 +95,20 @@ def multiply(be, a, b):
     return _plan(be, "multiplier", bits).run(inputs)
 
 
-def lookup(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks_t=None):
+def lookup(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks_t=None, digits="signed"):
     """table[index] for an index the server holds as encrypted bits -> int32 CUDA tensor [2][N], a ring
     ciphertext under the ring key of the secret that made `key`. index_bits: [depth][W] (or [depth][1][W], one lane of the
     bit-sliced integers above), LSB first, +-1/8 under the loaded key; table: int32 CUDA tensor [entries][2][N], entries <=
     2^depth (keygen.ring_trivial for plaintext rows); key: a client.SelectorKey, or the tensor of Backend.upload_selector_key with
-    explicit ks_basebit and ks_t. basebit, l default to keygen.circuit_bootstrap_default of the backend's set at this depth. One
-    Backend.circuit_bootstrap over the depth bits, then one Backend.ring_lookup: no round trip to the client."""
+    explicit ks_basebit and ks_t. basebit, l default to keygen.circuit_bootstrap_default of the backend's set at this depth and
+    digit form. digits: "signed", or "alternating" (the CMUX form without the ramp of a produced
+    selector's error, which carries finer rows; give it a key of circuit_bootstrap_default(..., digits="alternating")'s ks shape).
+    One Backend.circuit_bootstrap over the depth bits, then one Backend.ring_lookup: no round trip to the client."""
     from . import keygen
+    keygen._check_cmux_form(digits)
     bits = index_bits.reshape(-1, index_bits.shape[-1]).contiguous()
     if basebit is None or l is None:
-        d = keygen.circuit_bootstrap_default(keygen.set_name(be.p), bits.shape[0])
+        d = keygen.circuit_bootstrap_default(keygen.set_name(be.p), bits.shape[0], digits=digits)
         basebit, l = d[0] if basebit is None else basebit, d[1] if l is None else l
     sel = be.circuit_bootstrap(bits, basebit, l, key, ks_basebit, ks_t)
-    return be.ring_lookup(table, sel, basebit, l)
+    return be.ring_lookup(table, sel, basebit, l, digits=digits)

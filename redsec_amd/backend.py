@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "rs_bootstrap_sparse_dev",
     "rs_rekey_dev",
     "rs_ring_rekey_dev",
-    "rs_ring_cmux_dev", "rs_ring_lookup_dev",
+    "rs_ring_cmux_dev", "rs_ring_lookup_dev", "rs_ring_cmux_alt_dev", "rs_ring_lookup_alt_dev",
     "rs_ring_selector_dev", "rs_circuit_bootstrap_dev",
 ]
 
@@ -140,6 +140,8 @@ def load_library(path=None):
     L.rs_ring_rekey_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_ring_cmux_dev.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, vp]
     L.rs_ring_lookup_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.rs_ring_cmux_alt_dev.argtypes = L.rs_ring_cmux_dev.argtypes
+    L.rs_ring_lookup_alt_dev.argtypes = L.rs_ring_lookup_dev.argtypes
     L.rs_ring_selector_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
     L.rs_circuit_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
@@ -612,14 +614,17 @@ class Backend:
         assert depth is None or sel.numel() == depth * per
         return sel, basebit, l, sel.numel() // per
 
-    def ring_cmux(self, d1, d0, sel, basebit=None, l=None, stride=1, out=None):
+    def ring_cmux(self, d1, d0, sel, basebit=None, l=None, stride=1, out=None, digits="signed"):
         """out[r] = d1[r stride] where the selector encrypts 1, d0[r stride] where it encrypts 0 (rs_ring_cmux_dev, on torch's
         current stream) -> int32 CUDA tensor [R][2][N], R = ceil(rows of d0 / stride) (or into `out`; an `out` that overlaps an input is
         refused with ValueError). d0, d1: int32 CUDA tensors [rows][2][N] of packed ciphertexts (Backend.pack, rlwe_pk_encrypt) or trivial ones
         (keygen.ring_trivial); d1 = None is the all-zero ciphertext. sel: a client.RingSelector of depth 1 (uploaded on this
         context's device: keep the tensor of upload_ring_selector for repeated calls) or an int32 CUDA tensor [2l][2][N] with
-        explicit basebit and l. Needs no loaded key."""
+        explicit basebit and l. digits: "signed", or "alternating" (rs_ring_cmux_alt_dev, INTEGRATION.md section 25: the form for
+        selectors made by circuit_bootstrap; the same selector serves either); ValueError for anything else. Needs no loaded key."""
+        from . import keygen
         N = self.p.N
+        call = self.L.rs_ring_cmux_alt_dev if keygen._check_cmux_form(digits) == "alternating" else self.L.rs_ring_cmux_dev
         sel, basebit, l, depth = self._ring_selector(sel, basebit, l)
         assert depth == 1, "ring_cmux takes one selector; ring_lookup takes a tree of them"
         stride = int(stride)
@@ -632,17 +637,19 @@ class Backend:
         assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
         read = ((R - 1) * stride + 1) * 2 * N if R else 0                    # rows 0, stride, .. (R - 1) stride
         _refuse_overlap("out", out, out.numel(), (("d0", d0, read), ("d1", d1, read), ("sel", sel, sel.numel())))
-        _check(self.L, self.L.rs_ring_cmux_dev(self.h, self._ck_dev(out), None if d1 is None else self._ck_dev(d1), self._ck_dev(d0),
-                                               R, stride, self._ck_dev(sel), basebit, l, self._stream()))
+        _check(self.L, call(self.h, self._ck_dev(out), None if d1 is None else self._ck_dev(d1), self._ck_dev(d0),
+                            R, stride, self._ck_dev(sel), basebit, l, self._stream()))
         return out
 
-    def ring_lookup(self, table, sel, basebit=None, l=None, out=None):
+    def ring_lookup(self, table, sel, basebit=None, l=None, out=None, digits="signed"):
         """table[index] for the index encrypted in sel (rs_ring_lookup_dev, on torch's current stream) -> int32 CUDA tensor [2][N]
         (or into `out`). table: int32 CUDA tensor [entries][2][N], entries <= 2^depth; sel: a client.RingSelector (uploaded on this
         context's device) or an int32 CUDA tensor [depth][2l][2][N] with explicit basebit and l. An index at or past `entries`
-        gives an encryption of zero. The scratch of the call, ceil(E/2) + ceil(E/4) ciphertexts, is allocated here. Needs no
-        loaded key."""
+        gives an encryption of zero. The scratch of the call, ceil(E/2) + ceil(E/4) ciphertexts, is allocated here. digits: as
+        ring_cmux ("alternating": rs_ring_lookup_alt_dev). Needs no loaded key."""
+        from . import keygen
         N = self.p.N
+        call = self.L.rs_ring_lookup_alt_dev if keygen._check_cmux_form(digits) == "alternating" else self.L.rs_ring_lookup_dev
         sel, basebit, l, depth = self._ring_selector(sel, basebit, l)
         assert table.numel() and table.numel() % (2 * N) == 0, "table must hold [entries][2][N] words"
         entries = table.numel() // (2 * N)
@@ -653,8 +660,8 @@ class Backend:
         _refuse_overlap("out", out, out.numel(), (("table", table, table.numel()), ("sel", sel, sel.numel())))
         first = (entries + 1) // 2
         scratch = self.empty(first + (first + 1) // 2, 2, N) if depth > 1 else None
-        _check(self.L, self.L.rs_ring_lookup_dev(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
-                                                 basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
+        _check(self.L, call(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
+                            basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
         return out
 
     def upload_ring_selector(self, sel):

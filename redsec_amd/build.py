@@ -53,6 +53,8 @@ HIP_OBJECTS = [
     ("rs_ring_rekey", "rs_ring_rekey.hip", []),
     # encrypted selection (ring_cmux_init_kernel, ring_cmux_kernel), likewise in an object of their own; integer-only sources, as rs_pack
     ("rs_ring_cmux", "rs_ring_cmux.hip", []),
+    # the alternating form of the CMUX (ring_cmux_alt_kernel), likewise in an object of its own: ring_cmux_kernel keeps its instructions
+    ("rs_ring_cmux_alt", "rs_ring_cmux_alt.hip", []),
     # the selector keyswitch of circuit bootstrapping (ring_selector_init_kernel, ring_selector_kernel, circuit_prepare_kernel),
     # likewise in an object of its own; integer-only sources, as rs_pack
     ("rs_ring_selector", "rs_ring_selector.hip", []),

@@ -327,8 +327,9 @@ static int ring_cmux_rows(size_t R, size_t stride, size_t N, int32_t l) {
   return RS_OK;
 }
 
-int rs_ring_cmux_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride, const int32_t* sel,
-                     int32_t basebit, int32_t l, void* stream) {
+// one CMUX of either digit form (rs::kRcSigned, rs::kRcAlternating): the checks, the refusals and the launch are the same
+static int ring_cmux_any(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride, const int32_t* sel,
+                         int32_t basebit, int32_t l, int form, void* stream) {
   int rc = use_device(c);
   if (rc) return rc;
   if (!out || !d0 || !sel) return fail(RS_ERR_INVALID, "null pointer");
@@ -340,15 +341,24 @@ int rs_ring_cmux_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* 
   const size_t ct_bytes = 2 * N * kWord, read_bytes = ((R - 1) * stride + 1) * ct_bytes;     // rows 0, stride, .. (R - 1) stride
   if ((rc = refuse_overlap({"out", out, R * ct_bytes}, {{"d0", d0, read_bytes}, {"d1", d1, read_bytes}, {"sel", sel, (size_t)2 * l * ct_bytes}})) != RS_OK)
     return rc;
-  const rs::RingCmuxArgs a{out, d1, d0, sel, (long)R, (long)stride, (int)N, (int)basebit, (int)l};
+  const rs::RingCmuxArgs a{out, d1, d0, sel, (long)R, (long)stride, (int)N, (int)basebit, (int)l, form};
   RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
   return RS_OK;
+}
+int rs_ring_cmux_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride, const int32_t* sel,
+                     int32_t basebit, int32_t l, void* stream) {
+  return ring_cmux_any(c, out, d1, d0, R, stride, sel, basebit, l, rs::kRcSigned, stream);
+}
+int rs_ring_cmux_alt_dev(rs_ctx* c, int32_t* out, const int32_t* d1, const int32_t* d0, size_t R, size_t stride, const int32_t* sel,
+                         int32_t basebit, int32_t l, void* stream) {
+  return ring_cmux_any(c, out, d1, d0, R, stride, sel, basebit, l, rs::kRcAlternating, stream);
 }
 
 // the CMUX tree: level k pairs rows (2r, 2r + 1) of the previous level under selector k; an unpaired last row meets the all-zero
 // ciphertext. The levels alternate between the two halves of scratch, ceil(E / 2) and ceil(E / 4) rows; the last one writes out.
-int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
-                       int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+// Either digit form: every level's launches carry `form`.
+static int ring_lookup_any(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
+                           int32_t basebit, int32_t l, int32_t* scratch, int form, void* stream) {
   int rc = use_device(c);
   if (rc) return rc;
   if (!out || !table || !sel) return fail(RS_ERR_INVALID, "null pointer");
@@ -372,17 +382,25 @@ int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t ent
     const size_t pairs = rows / 2;
     const int32_t* s = sel + (size_t)k * sel_words;
     if (pairs) {
-      const rs::RingCmuxArgs a{o, in + ct, in, s, (long)pairs, 2, (int)N, (int)basebit, (int)l};
+      const rs::RingCmuxArgs a{o, in + ct, in, s, (long)pairs, 2, (int)N, (int)basebit, (int)l, form};
       RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
     }
     if (rows & 1) {
-      const rs::RingCmuxArgs a{o + pairs * ct, nullptr, in + (rows - 1) * ct, s, 1, 1, (int)N, (int)basebit, (int)l};
+      const rs::RingCmuxArgs a{o + pairs * ct, nullptr, in + (rows - 1) * ct, s, 1, 1, (int)N, (int)basebit, (int)l, form};
       RS_HIP(rs::launch_ring_cmux(a, (hipStream_t)stream));
     }
     in = o;
     rows = (size_t)rs::rc_level_rows((long)rows);
   }
   return RS_OK;
+}
+int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
+                       int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+  return ring_lookup_any(c, out, table, entries, sel, depth, basebit, l, scratch, rs::kRcSigned, stream);
+}
+int rs_ring_lookup_alt_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
+                           int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+  return ring_lookup_any(c, out, table, entries, sel, depth, basebit, l, scratch, rs::kRcAlternating, stream);
 }
 
 // circuit bootstrapping (include/redsec_hip.h; kernels of rs_ring_selector.hip, integer arithmetic only). The checks the two calls

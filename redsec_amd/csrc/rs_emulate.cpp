@@ -1539,9 +1539,10 @@ long rs_emu_ring_lookup_scratch_rows(long entries) { return rs::rc_scratch_rows(
 // ring_cmux_init_kernel, then ring_cmux_kernel workgroup by workgroup and thread by thread as the kernel places them: ring_place
 // over (tile, polynomial, source block, selector row, ciphertext), the staged window of the selector row and the block's words
 // d1 - d0 + offset (-d0 + offset under a null d1), ring_sweep (rs_ring_sweep.h, the kernel's own) with the signed digit, the
-// partial sums added into the output
-void rs_emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long stride, int N, const int32_t* sel_, int basebit, int l,
-                      int32_t* out_) {
+// partial sums added into the output. form = rs::kRcAlternating: ring_cmux_alt_kernel (rs_ring_cmux_alt.hip), which stages
+// eps_k x_k + offset (the parity of k = c0 + cc is that of the slot cc) and sweeps with ring_sweep_parity and rc_digit_alt
+static void emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long stride, int N, const int32_t* sel_, int basebit, int l,
+                          int form, int32_t* out_) {
   if (R <= 0) return;
   uint32_t* out = reinterpret_cast<uint32_t*>(out_);
   const uint32_t* d1 = reinterpret_cast<const uint32_t*>(d1_);
@@ -1559,19 +1560,37 @@ void rs_emu_ring_cmux(const int32_t* d1_, const int32_t* d0_, long R, long strid
     const uint32_t* p = sel + rs::rc_sel_offset(N, jr, pl.poly);
     for (int th = 0; th < rs::kRingThreads; ++th)
       rs::sweep_stage_window(win.data(), p, N, rs::ring_window_base(N, k0, c0), rs::kRingWindow, th, rs::kRingThreads);
-    for (int cc = 0; cc < rs::kRingSlots; ++cc) sx[cc] = (d1 ? d1[src_at + cc] : 0u) - d0[src_at + cc] + off;
+    for (int th = 0; th < rs::kRingThreads; ++th)                      // thread th stages the slots th, th + kRingThreads, ..
+      for (int cc = th; cc < rs::kRingSlots; cc += rs::kRingThreads) {
+        const uint32_t x = (d1 ? d1[src_at + cc] : 0u) - d0[src_at + cc];
+        sx[cc] = form == rs::kRcAlternating ? rs::rc_stage_alt(x, off, th & 1) : x + off;
+      }
     for (int th = 0; th < rs::kRingThreads; ++th) {
       uint32_t acc[rs::kSweepKpt] = {0u, 0u, 0u, 0u};
-      rs::ring_sweep(win.data(), sx.data(), rs::kRingSlots, th, [=](uint32_t xbar) { return rs::rc_digit(xbar, basebit, j); }, acc);
+      if (form == rs::kRcAlternating)
+        rs::ring_sweep_parity(win.data(), sx.data(), rs::kRingSlots, th,
+                              [=](uint32_t xbar, auto slot_odd) { return rs::rc_digit_alt(xbar, basebit, j, decltype(slot_odd)::value); }, acc);
+      else
+        rs::ring_sweep(win.data(), sx.data(), rs::kRingSlots, th, [=](uint32_t xbar) { return rs::rc_digit(xbar, basebit, j); }, acc);
       uint32_t* o = out + ((size_t)pl.r * 2 + pl.poly) * N + k0 + rs::kSweepKpt * th;
       for (int q = 0; q < rs::kSweepKpt; ++q) o[q] += acc[q];
     }
   }
 }
+void rs_emu_ring_cmux(const int32_t* d1, const int32_t* d0, long R, long stride, int N, const int32_t* sel, int basebit, int l,
+                      int32_t* out) {
+  emu_ring_cmux(d1, d0, R, stride, N, sel, basebit, l, rs::kRcSigned, out);
+}
+void rs_emu_ring_cmux_alt(const int32_t* d1, const int32_t* d0, long R, long stride, int N, const int32_t* sel, int basebit, int l,
+                          int32_t* out) {
+  emu_ring_cmux(d1, d0, R, stride, N, sel, basebit, l, rs::kRcAlternating, out);
+}
+// eps_k dig_j of the staged word xbar = eps_k x_k + offset, odd = k & 1
+uint32_t rs_emu_ring_cmux_digit_alt(uint32_t xbar, int basebit, int j, int odd) { return rs::rc_digit_alt(xbar, basebit, j, odd); }
 // rs_ring_lookup_dev's levels as the host code orders them: pairs at stride 2, an unpaired last row against the null d1, the two
 // halves of scratch in turn, the last level into out
-void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
-                        int32_t* scratch, int32_t* out) {
+static void emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l, int form,
+                            int32_t* scratch, int32_t* out) {
   const size_t ct = 2 * (size_t)N, sel_words = (size_t)2 * l * ct;
   int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::rc_level_rows(entries) * ct : nullptr};
   const int32_t* in = table;
@@ -1580,11 +1599,19 @@ void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t
     int32_t* o = k == depth - 1 ? out : half[k & 1];
     const long pairs = rows / 2;
     const int32_t* s = sel + (size_t)k * sel_words;
-    if (pairs) rs_emu_ring_cmux(in + ct, in, pairs, 2, N, s, basebit, l, o);
-    if (rows & 1) rs_emu_ring_cmux(nullptr, in + (size_t)(rows - 1) * ct, 1, 1, N, s, basebit, l, o + (size_t)pairs * ct);
+    if (pairs) emu_ring_cmux(in + ct, in, pairs, 2, N, s, basebit, l, form, o);
+    if (rows & 1) emu_ring_cmux(nullptr, in + (size_t)(rows - 1) * ct, 1, 1, N, s, basebit, l, form, o + (size_t)pairs * ct);
     in = o;
     rows = rs::rc_level_rows(rows);
   }
+}
+void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
+                        int32_t* scratch, int32_t* out) {
+  emu_ring_lookup(table, entries, N, sel, depth, basebit, l, rs::kRcSigned, scratch, out);
+}
+void rs_emu_ring_lookup_alt(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
+                            int32_t* scratch, int32_t* out) {
+  emu_ring_lookup(table, entries, N, sel, depth, basebit, l, rs::kRcAlternating, scratch, out);
 }
 // ---- the refusal of an out that overlaps an input (rs_api_client.cpp refuse_overlap) through rs_host.h first_overlap ----
 // written = (address, bytes); others [count][2] the same pairs -> the index of the first one that shares a byte with it, or -1.

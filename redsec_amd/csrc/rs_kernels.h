@@ -205,8 +205,10 @@ struct RingCmuxArgs {
   const int32_t* sel;                                 // [2l][2][N]: one RGSW sample
   long R, stride;
   int N, basebit, l;
+  int form = 0;                                       // kRcSigned (rs_ring_cmux.h) or kRcAlternating: the digit
 };
-hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st);
+hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st);      // ring_cmux_init_kernel, then the kernel of a.form
+hipError_t launch_ring_cmux_alt(const RingCmuxArgs& a, hipStream_t st);  // ring_cmux_alt_kernel alone (rs_ring_cmux_alt.hip): launch_ring_cmux calls it
 // the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev; placement and index arithmetic of rs_ring_selector.h)
 struct RingSelectorArgs {
   int32_t* sel;                                       // [rows / l][2l][2][N]

@@ -42,6 +42,21 @@ RS_HD uint32_t rc_digit(uint32_t xbar, int basebit, int j) {
   return ((xbar >> (32 - (j + 1) * basebit)) & ((1u << basebit) - 1u)) - (1u << (basebit - 1));
 }
 
+// The alternating form (rs_ring_cmux_alt_dev, rs_ring_lookup_alt_dev; ring_cmux_alt_kernel, rs_ring_cmux_alt.hip): the sign of
+// every other source coefficient is flipped before and after the decomposition,
+//     eps_k = +1 for even k, -1 for odd k,    dig'_j(x_k) = eps_k dig_j(eps_k x_k),
+// with dig_j, off and h_j those above. sum_j dig'_j(x_k) h_j is still x_k rounded to l basebit bits within the same half step, so
+// the same RGSW samples select; the digit at position k has mean -eps_k / 2 instead of -1/2, and the digits lie in -B/2 .. B/2.
+// The forms of RingCmuxArgs (rs_kernels.h); zero, the value-initialised one, is the signed digit.
+constexpr int kRcSigned = 0, kRcAlternating = 1;
+// the word staged for source coefficient k of x = d1 - d0: eps_k x + off (odd: the parity of k, 0 or 1)
+RS_HD uint32_t rc_stage_alt(uint32_t x, uint32_t off, int odd) { return (odd ? 0u - x : x) + off; }
+// digit j of that staged word: eps_k dig_j
+RS_HD uint32_t rc_digit_alt(uint32_t xbar, int basebit, int j, int odd) {
+  const uint32_t d = rc_digit(xbar, basebit, j);
+  return odd ? 0u - d : d;
+}
+
 // workgroups of one ciphertext and of a launch
 RS_HD long rc_groups_per_ct(int N, int l) { return ring_groups_per_ct(N, 2 * l); }
 RS_HD long rc_groups(long R, int N, int l) { return R * rc_groups_per_ct(N, l); }

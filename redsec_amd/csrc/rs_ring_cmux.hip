@@ -64,6 +64,7 @@ hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(ring_cmux_init_kernel, dim3((unsigned)init_groups), dim3(kRcInitThreads), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
+  if (a.form == kRcAlternating) return launch_ring_cmux_alt(a, st);      // the alternating digit: a kernel in an object of its own
   const size_t lds = ((size_t)2 * kRcSlots + kRcTile) * sizeof(uint32_t);
   hipLaunchKernelGGL(ring_cmux_kernel, dim3((unsigned)rc_groups(a.R, a.N, a.l)), dim3(kRcThreads), lds, st, a);
   return hipGetLastError();

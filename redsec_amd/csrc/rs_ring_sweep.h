@@ -2,7 +2,8 @@
 // ring_cmux_kernel (rs_ring_cmux.hip) and the lane emulators rs_emu_pack, rs_emu_ring_rekey and rs_emu_ring_cmux (rs_emulate.cpp)
 // all compile the functions below, so the CPU tests run the loop that the device runs. pack_kernel (rs_pack.hip) keeps ring_sweep
 // written out, the one copy left: as a call it measured slower there (see that file's header).
-// Integer only: a digit times a 32-bit word, accumulated mod 2^32, exact in any order.
+// Integer only: a digit times a 32-bit word, accumulated mod 2^32, exact in any order. ring_sweep_parity is the same loop for a
+// digit that depends on the parity of its slot: ring_cmux_alt_kernel (rs_ring_cmux_alt.hip) and rs_emu_ring_cmux_alt compile it.
 //
 // The sweep adds D(X) p to four coefficients of a thread, D(X) = sum_cc digit(src[cc]) X^(c0 + cc) over `slots` source words and p
 // one key polynomial mod X^N + 1. The workgroup has staged the window of ext = (-p, p) (rs_rlwe.h) that its tile of coefficients
@@ -21,6 +22,7 @@
 #pragma once
 
 #include <cstdint>
+#include <type_traits>
 
 #include "rs_rlwe.h"
 
@@ -67,6 +69,33 @@ RS_HD void ring_sweep(const uint32_t* win, const uint32_t* src, int slots, int t
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) hi[q] = lo[q];              // the upper chunk of the next step
+  }
+}
+
+// The sibling of ring_sweep for a digit that depends on the parity of its slot: acc[q] += sum_cc win[..] digit(src[cc], cc & 1),
+// the alternating digit of ring_cmux_alt_kernel (rs_ring_cmux_alt.hip) and rs_emu_ring_cmux_alt. The slot index of a step is a
+// constant of the unrolled loop, so the functor receives the parity as a std::integral_constant: the form of the digit is chosen at
+// compile time and costs no select. A second copy of the loop and not ring_sweep as a call of this one: as such a call,
+// ring_rekey_kernel and ring_cmux_kernel changed instructions (tools/codeobj_digest.py), and they are to keep them.
+template <class Digit>
+RS_HD void ring_sweep_parity(const uint32_t* win, const uint32_t* src, int slots, int t, Digit digit, uint32_t (&acc)[kSweepKpt]) {
+  const std::integral_constant<int, 0> even{};
+  const std::integral_constant<int, 1> odd{};
+  int c4 = t + slots / 4;
+  uint32_t lo[4], hi[4], s[4];
+  sweep_load4(win + 4 * c4, hi);
+  for (int q4 = 0; q4 < slots / 4; ++q4) {
+    sweep_load4(src + 4 * q4, s);
+    const uint32_t d[4] = {digit(sweep_uniform(s[0]), even), digit(sweep_uniform(s[1]), odd), digit(sweep_uniform(s[2]), even),
+                           digit(sweep_uniform(s[3]), odd)};
+    sweep_load4(win + 4 * --c4, lo);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+#pragma unroll
+      for (int q = 0; q < kSweepKpt; ++q) acc[q] += (q >= b ? hi[q - b] : lo[4 + q - b]) * d[b];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) hi[q] = lo[q];
   }
 }
 

@@ -113,6 +113,8 @@ The seeded form, row = k 2l + j for sample k (bit k of the index, least signific
 
   Domains 18 and 19 are disjoint from domains 1-17. Equal mask and noise seeds are refused. ring_cmux_digits / ring_cmux /
   ring_lookup / ring_selector_rows / ring_selector_expand / ring_trivial / ring_cmux_sigma / ring_cmux_default restate it.
+  digits="alternating" in ring_cmux_digits / ring_cmux / ring_lookup / circuit_bootstrap_sigma / circuit_bootstrap_default is the
+  second digit form (rs_ring_cmux_alt_dev, rs_ring_lookup_alt_dev): eps_k dig_j(eps_k x_k), eps_k = (-1)^k.
 
 Circuit bootstrapping (rs_ring_selector_dev, rs_circuit_bootstrap_dev; include/redsec_hip.h): the
 selectors of the section above made by the server from LWE bits. Bit k is bootstrapped at the l levels to phase +-h_j/2, and a
@@ -1045,21 +1047,38 @@ def ring_cmux_offset(basebit, l):
     return (sum(1 << (31 - j * basebit) for j in range(l)) + (1 << (31 - l * basebit))) & 0xFFFFFFFF
 
 
-def ring_cmux_digits(x, basebit, l):
+RING_CMUX_DIGITS = ("signed", "alternating")
+
+
+def _check_cmux_form(digits):
+    if digits not in RING_CMUX_DIGITS:
+        raise ValueError("digits = %r: the digit form must be 'signed' or 'alternating'" % (digits,))
+    return digits
+
+
+def ring_cmux_digits(x, basebit, l, digits="signed"):
     """The signed digits dig_j(w) = (((w + off) >> (32-(j+1) basebit)) & (B - 1)) - B/2 of words x int32 [..., N] -> int64
-    [..., l, N], each in -B/2 .. B/2 - 1; sum_j dig_j h_j = w rounded to l basebit bits (mod 2^32)."""
+    [..., l, N], each in -B/2 .. B/2 - 1; sum_j dig_j h_j = w rounded to l basebit bits (mod 2^32).
+    digits="alternating" (rs_ring_cmux_alt_dev): dig'_j(x_k) = eps_k dig_j(eps_k x_k), eps_k = +1 for even and -1 for odd k, the
+    index along the last axis; each in -B/2 .. B/2, the same rounding within the same half step, mean -eps_k / 2."""
     basebit, l = _check_cmux_digits(basebit, l)
-    xbar = (np.asarray(x, np.int32).view(np.uint32).astype(np.int64) + ring_cmux_offset(basebit, l)) & 0xFFFFFFFF
+    x = np.asarray(x, np.int32).view(np.uint32).astype(np.int64)
+    if _check_cmux_form(digits) == "alternating":
+        eps = 1 - 2 * (np.arange(x.shape[-1], dtype=np.int64) & 1)
+        x = (eps * x) & 0xFFFFFFFF
+    xbar = (x + ring_cmux_offset(basebit, l)) & 0xFFFFFFFF
     B = 1 << basebit
-    return np.stack([((xbar >> (32 - (j + 1) * basebit)) & (B - 1)) - B // 2 for j in range(l)], axis=-2)
+    D = np.stack([((xbar >> (32 - (j + 1) * basebit)) & (B - 1)) - B // 2 for j in range(l)], axis=-2)
+    return D * eps if digits == "alternating" else D
 
 
-def ring_cmux(d1, d0, sel, basebit, l):
+def ring_cmux(d1, d0, sel, basebit, l, digits="signed"):
     """rs_ring_cmux_dev restated: d0, d1 int32 [R][2][N] (d1 = None: all zero), sel int32 [2l][2][N] -> int32 [R][2][N], out[r] =
     d0[r] + sum_j Da_j(X) sel[j] + sum_j Db_j(X) sel[l+j] over the digits of d1[r] - d0[r]. Each product is one int64 linear
     convolution folded negacyclically (numpy.convolve): nothing like the device's tiled 32-bit multiply-adds. A stride is the
-    caller's slice (d0[::2], d1[1::2])."""
+    caller's slice (d0[::2], d1[1::2]). digits="alternating": rs_ring_cmux_alt_dev, the digits of ring_cmux_digits in that form."""
     basebit, l = _check_cmux_digits(basebit, l)
+    _check_cmux_form(digits)
     sel = np.ascontiguousarray(sel, np.int32)
     assert sel.ndim == 3 and sel.shape[0] == 2 * l and sel.shape[1] == 2, "sel must hold [2l][2][N] words"
     N = sel.shape[2]
@@ -1067,7 +1086,7 @@ def ring_cmux(d1, d0, sel, basebit, l):
     with np.errstate(over="ignore"):
         x = (np.uint32(0) - d0.view(np.uint32)) if d1 is None else (np.ascontiguousarray(d1, np.int32).reshape(-1, 2, N).view(np.uint32) - d0.view(np.uint32))
     assert x.shape == d0.shape, "d1 and d0 must hold the same number of ciphertexts"
-    D = ring_cmux_digits(x.view(np.int32), basebit, l)            # [R][2][l][N]
+    D = ring_cmux_digits(x.view(np.int32), basebit, l, digits)    # [R][2][l][N]
     su = sel.view(np.uint32).astype(np.int64)
     out = d0.view(np.uint32).astype(np.int64)
     for r in range(d0.shape[0]):
@@ -1077,10 +1096,12 @@ def ring_cmux(d1, d0, sel, basebit, l):
     return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
-def ring_lookup(table, sel, basebit, l):
+def ring_lookup(table, sel, basebit, l, digits="signed"):
     """rs_ring_lookup_dev restated: table int32 [entries][2][N], sel int32 [depth][2l][2][N], entries <= 2^depth -> int32 [2][N]:
-    level k is ring_cmux over the pairs (2r, 2r + 1) of the previous level under sel[k]; an unpaired last row meets d1 = None."""
+    level k is ring_cmux over the pairs (2r, 2r + 1) of the previous level under sel[k]; an unpaired last row meets d1 = None.
+    digits="alternating": rs_ring_lookup_alt_dev, every level in that form."""
     basebit, l = _check_cmux_digits(basebit, l)
+    _check_cmux_form(digits)
     sel = np.ascontiguousarray(sel, np.int32)
     assert sel.ndim == 4 and sel.shape[1:3] == (2 * l, 2), "sel must hold [depth][2l][2][N] words"
     depth, N = sel.shape[0], sel.shape[3]
@@ -1089,9 +1110,9 @@ def ring_lookup(table, sel, basebit, l):
         raise ValueError("depth = %d, entries = %d: depth must lie in 1 .. 30 and entries in 1 .. 2^depth" % (depth, rows.shape[0]))
     for k in range(depth):
         pairs = rows.shape[0] // 2
-        nxt = [ring_cmux(rows[1:2 * pairs:2], rows[0:2 * pairs:2], sel[k], basebit, l)] if pairs else []
+        nxt = [ring_cmux(rows[1:2 * pairs:2], rows[0:2 * pairs:2], sel[k], basebit, l, digits)] if pairs else []
         if rows.shape[0] & 1:
-            nxt.append(ring_cmux(None, rows[-1:], sel[k], basebit, l))
+            nxt.append(ring_cmux(None, rows[-1:], sel[k], basebit, l, digits))
         rows = np.concatenate(nxt)
     return rows[0]
 
@@ -1152,7 +1173,10 @@ def ring_cmux_sigma(N, basebit, l, sigma_row, depth=1, bit=1):
     of one selector row's phase per coefficient.
       sigma^2 = depth (2 l N (B^2 + 2)/12 sigma_row^2  +  (1 + N/2) 2^(-2 l basebit)/12)
     The rounding reaches the phase multiplied by the selected bit: the formula is that of a selector of 1 (and of a lookup whose
-    index has every bit set), the larger of the two. bit=0 leaves the second term out: the error under a selector of 0."""
+    index has every bit set), the larger of the two. bit=0 leaves the second term out: the error under a selector of 0.
+    The formula holds for both digit forms (ring_cmux_digits): the rows of a client's selector carry independent noise, so a digit
+    enters by its mean square alone, and eps_k dig_j(eps_k x_k) has the mean square of dig_j; the rounding error of the alternating
+    form is eps_k times that of the signed form at eps_k x_k, of the same size. Hence no digits= keyword here."""
     basebit, l = _check_cmux_digits(basebit, l)
     B = 2.0 ** basebit
     rounding = (1.0 + N / 2.0) * 2.0 ** (-2 * l * basebit) / 12.0 if bit else 0.0
@@ -1294,7 +1318,7 @@ def selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k):
     return float(np.sqrt(w)), float(np.sqrt(key))
 
 
-def circuit_bootstrap_sigma(N, n_src, basebit, l, ks_basebit, ks_t, sigma_u, sigma_k, depth=1, bit=1, coefficient=0):
+def circuit_bootstrap_sigma(N, n_src, basebit, l, ks_basebit, ks_t, sigma_u, sigma_k, depth=1, bit=1, coefficient=None, digits="signed"):
     """Deviation of the error of coefficient c = `coefficient` after `depth` CMUXes under produced selectors (a lookup of that
     depth), as a real. Both families of a level come from the SAME bootstrapped sample, so its error w_j multiplies the digit
     polynomial Db_j(X) - Da_j(X) S(X), and it is the same w_j on every coefficient. The signed digits of rs_ring_cmux_dev have
@@ -1305,35 +1329,51 @@ def circuit_bootstrap_sigma(N, n_src, basebit, l, ks_basebit, ks_t, sigma_u, sig
     ring_cmux_sigma, and the CMUX's own rounding is unchanged (bit=0 leaves it out):
       sigma^2 = depth (l sigma_w^2 ((1 + N/2)(B^2 - 1)/12 + ((1 - t_c)^2 + N/4)/4)  +  2 l N (B^2 + 2)/12 sigma_key^2  +  (1 + N/2) 2^(-2 l basebit)/12)
     with (sigma_w, sigma_key) = selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k). `coefficient` may be an array. A
-    trivial ciphertext (a = 0, a plaintext table row) has Da_j = 0, and the first term is then far smaller: an upper bound there."""
+    trivial ciphertext (a = 0, a plaintext table row) has Da_j = 0, and the first term is then far smaller: an upper bound there.
+    coefficient=None is the worst coefficient of the form: 0 here.
+    digits="alternating" (rs_ring_cmux_alt_dev): the digit at position k has mean -eps_k / 2, eps_k = (-1)^k, so the mean of
+    Db_j - Da_j S is -V(X)(1 - S(X))/2 with V = sum_k (-1)^k X^k. Coefficient c of V S mod X^N + 1 is (-1)^c (sum_{i <= c}
+    (-1)^i S_i - sum_{i > c} (-1)^i S_i): N independent terms +-S_i of variance 1/4 each, N/4 in all at every c, and of expectation
+    (-1)^c (e_c + e_c)/2 with e_c = sum_{i <= c} (-1)^i = [c even] (the alternating signs of the N positions cancel, so the sum above
+    c is -e_c): 1 at even c, 0 at odd c. Coefficient c of V(1 - S) therefore has expectation (-1)^c - [c even] = -[c odd] and
+    mean square N/4 + [c odd]. The ramp is gone and what is left of c is its parity, one part in N/4:
+      sigma^2 = depth (l sigma_w^2 ((1 + N/2)(B^2 - 1)/12 + (N/4 + [c odd])/4)  +  the same key and rounding terms)
+    coefficient=None is then any odd one."""
     basebit, l = _check_cmux_digits(basebit, l)
     sw, sk = selector_row_sigma(n_src, ks_basebit, ks_t, sigma_u, sigma_k)
     B = 2.0 ** basebit
-    t = np.asarray(coefficient, np.float64) + 1.0 - N / 2.0
-    sample = l * sw * sw * ((1.0 + N / 2.0) * (B * B - 1.0) / 12.0 + ((1.0 - t) ** 2 + N / 4.0) / 4.0)
+    if _check_cmux_form(digits) == "alternating":
+        mean_sq = N / 4.0 + (1.0 if coefficient is None else (np.asarray(coefficient, np.int64) & 1).astype(np.float64))
+    else:
+        t = np.asarray(0 if coefficient is None else coefficient, np.float64) + 1.0 - N / 2.0
+        mean_sq = (1.0 - t) ** 2 + N / 4.0
+    sample = l * sw * sw * ((1.0 + N / 2.0) * (B * B - 1.0) / 12.0 + mean_sq / 4.0)
     rounding = (1.0 + N / 2.0) * 2.0 ** (-2 * l * basebit) / 12.0 if bit else 0.0
     out = np.sqrt(int(depth) * (sample + 2.0 * l * N * (B * B + 2.0) / 12.0 * sk * sk + rounding))
     return float(out) if out.ndim == 0 else out
 
 
-def circuit_bootstrap_default(name, depth=1, step=CIRCUIT_BOOTSTRAP_STEP):
+def circuit_bootstrap_default(name, depth=1, step=CIRCUIT_BOOTSTRAP_STEP, digits="signed"):
     """(basebit, l, ks_basebit, ks_t) of circuit bootstrapping for a lookup of `depth` levels on set `name`: the cheapest shape for
     which 8 circuit_bootstrap_sigma of the worst coefficient stays inside step / 2, the half step of payloads that are multiples of
     `step`, at sigma_u =
     bootstrap_sigma(name) and key rows of ring_selector_default_stdev(name). Cheapest: the smallest l (l bootstraps a bit), for that
     l the smallest ks_t (the key is 2 (n + 1) ks_t ring samples), and for that pair the (basebit, ks_basebit) of the smallest
-    sigma. ValueError where no shape reaches it: default-128, whose bootstrap output noise alone is too large for every shape."""
+    sigma. ValueError where no shape reaches it: default-128, whose bootstrap output noise alone is too large for every shape.
+    digits: the digit form of the CMUX the selectors will drive ("signed": rs_ring_cmux_dev; "alternating": rs_ring_cmux_alt_dev,
+    whose sigma has no ramp); the selectors themselves are the same."""
+    _check_cmux_form(digits)
     sh = _shape(name)
     N, n, su, sk = sh["N"], sh["n"], bootstrap_sigma(name), ring_selector_default_stdev(name)
     for l in range(1, RING_CMUX_MAX_BITS + 1):
         for ks_t in range(1, 33):
-            fits = [(circuit_bootstrap_sigma(N, n, b, l, kb, ks_t, su, sk, depth), b, kb)
+            fits = [(circuit_bootstrap_sigma(N, n, b, l, kb, ks_t, su, sk, depth, digits=digits), b, kb)
                     for b in range(1, 9) if b * l <= RING_CMUX_MAX_BITS for kb in range(1, 9) if kb * ks_t <= 32]
             fits = [f for f in fits if 8 * f[0] <= step / 2.0]
             if fits:
                 _, b, kb = min(fits)
                 return (b, l, kb, ks_t)
-    raise ValueError("no shape keeps 8 sigma inside half of %g on %s at depth %d" % (step, name, depth))
+    raise ValueError("no shape keeps 8 sigma inside half of %g on %s at depth %d with %s digits" % (step, name, depth, digits))
 
 
 # ---- noise audit (rs_audit_keys_dev / rs_audit_compressed_keys_dev restated) ----

@@ -13,7 +13,14 @@ for selectors and ciphertexts: the arithmetic does not depend on the words):
   what = "noise": the decrypted error of a depth-10 lookup of a 1,024-row trivial table under a real seeded selector of the set's
       default shape and deviation: rms and largest error, each over keygen.ring_cmux_sigma(depth = 10)
 
+  --digits: the leg of the alternating form (rs_ring_cmux_alt_dev, rs_ring_lookup_alt_dev) and nothing else:
+      what = "cmux_digits" (R = 1, 64, 1,024) and "lookup_digits" (1,024 entries) at redsec_small_v2 with (4, 6), both forms in this
+      one process on the same buffers, --rounds rounds of --reps calls a form, the forms taking turns within a round: per form the
+      median of the rounds' medians with the least and the largest of them, and alternating_over_signed, the ratio of the two
+      medians. No speed gate: the multiply-add count is the same. windows_overlap says whether min .. max of the two forms meet
+
 usage: python tools/ring_cmux_time.py [--reps 20] [--out profiles/r26/ring_cmux_time.jsonl]
+       python tools/ring_cmux_time.py --digits [--reps 20] [--rounds 5] [--out profiles/r30/ring_cmux_alt_time.jsonl]
 """
 import argparse
 import ctypes as C
@@ -53,6 +60,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--digits", action="store_true", help="time the alternating form beside the signed one, and nothing else")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -72,7 +81,47 @@ def main():
         d.update(mads=mads, mads_per_s=round(r, 1), ceiling_mads_per_s=round(CEILING_MADS_PER_S, 1), fraction_of_ceiling=round(r / CEILING_MADS_PER_S, 4))
         return d
 
-    for name, counts in CMUX_RUNS:
+    def both_forms(run):
+        """run(form)() is one call -> {form: ms, ms_min, ms_max over the rounds' medians}, the ratio and whether the windows meet"""
+        forms = ("signed", "alternating")
+        med = {f: [] for f in forms}
+        for _ in range(args.rounds):
+            for f in forms:
+                med[f].append(_event_ms(run(f), args.reps)["ms"])
+        d = {}
+        for f in forms:
+            d.update({f + "_ms": round(statistics.median(med[f]), 4), f + "_ms_min": min(med[f]), f + "_ms_max": max(med[f])})
+        d["alternating_over_signed"] = round(d["alternating_ms"] / d["signed_ms"], 4)
+        d["windows_overlap"] = bool(d["alternating_ms_min"] <= d["signed_ms_max"] and d["signed_ms_min"] <= d["alternating_ms_max"])
+        d.update(reps=args.reps, rounds=args.rounds)
+        return d
+
+    if args.digits:
+        name = "redsec_small_v2"
+        be = redsec_amd.Backend(redsec_amd.params(name, n=16), device=0)
+        N = be.p.N
+        sel = rand(2 * l, 2, N)
+        for R in (1, 64, 1024):
+            d1, d0, out = rand(R, 2, N), rand(R, 2, N), be.empty(R, 2, N)
+            d = both_forms(lambda f: (lambda: be.ring_cmux(d1, d0, sel, basebit, l, out=out, digits=f)))
+            emit(dict(what="cmux_digits", set=name, N=N, basebit=basebit, l=l, R=R, mads=R * 2 * l * 2 * N * N, **d))
+        E, depth = 1024, 10
+        table, sels, out = rand(E, 2, N), rand(depth, 2 * l, 2, N), be.empty(2, N)
+        scratch = be.empty(E // 2 + E // 4, 2, N)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+
+        def look_of(f):
+            fn = be.L.rs_ring_lookup_alt_dev if f == "alternating" else be.L.rs_ring_lookup_dev
+
+            def look():
+                rc = fn(be.h, vp(out), vp(table), E, vp(sels), depth, basebit, l, vp(scratch), be._stream())
+                assert rc == 0, be.L.rs_last_error()
+            return look
+        emit(dict(what="lookup_digits", set=name, N=N, basebit=basebit, l=l, entries=E, depth=depth, cmuxes=E - 1,
+                  mads=(E - 1) * 2 * l * 2 * N * N, **both_forms(look_of)))
+        be.close()
+
+    for name, counts in (() if args.digits else CMUX_RUNS):
         be = redsec_amd.Backend(redsec_amd.params(name, n=16), device=0)     # the calls need no key: the ring is what matters
         N = be.p.N
         sel = rand(2 * l, 2, N)
