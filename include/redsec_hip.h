@@ -364,6 +364,42 @@ int rs_ring_cmux_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* d1, const int
 int rs_ring_lookup_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
                            const int32_t* sel, int32_t depth, int32_t basebit, int32_t l, int32_t* scratch, void* stream);
 
+/* Encrypted rotation: out[r] = X^(step index_r) in[r stride] for an index the server does not see, the
+ * horizontal half of TFHE's levelled mode beside the vertical lookup above. A chain of `depth` CMUXes whose second input is never
+ * stored: level k selects between acc and X^(e_k) acc under selector sample k. Word-wise mod 2^32 with negacyclic products; the
+ * digits, off and h_j are those of rs_ring_cmux_dev (rs_ring_rotate_alt_dev: those of rs_ring_cmux_alt_dev):
+ *   acc_0[r]     = in[r stride]                        (stride = 0 is allowed: every row starts from in[0])
+ *   e_k          = (step 2^k) mod 2N                   (64-bit product, k < depth; step any int32)
+ *   x_k[r]       = X^(e_k) acc_k[r] - acc_k[r]
+ *   acc_(k+1)[r] = acc_k[r] + sum_{j<l} Da_j(X) S_k[j] + sum_{j<l} Db_j(X) S_k[l+j]         over the digits of x_k[r]
+ *   out[r]       = acc_depth[r]
+ * (X^e v)_c with e = q N + s, 0 <= s < N, is (-1)^q ext_v[c - s + N] for ext_v = (-v, v). S_k is selector sample k of the row's set:
+ * sel DEVICE int32[depth][2l][2][N] with per_row = 0 (one hidden index for all rows), int32[R][depth][2l][2][N] with per_row = 1
+ * (one index per row); the bits least significant first, the samples rs_ring_lookup_dev takes and rs_circuit_bootstrap_dev makes.
+ * phase(out[r]) = X^(step index_r) phase(in[r stride]) + noise: step = -1 brings slot `index` to coefficient 0, step = -w brings
+ * slots w index .. w index + w - 1 to coefficients 0 .. w - 1. The noise is that of `depth` CMUXes (the variance of
+ * rs_ring_cmux_dev times depth; later levels move a level's error to other coefficients and flip signs, they do not grow it).
+ * A level with e_k = 0 leaves the words unchanged (every digit of 0 is 0 in both forms).
+ * scratch DEVICE int32[R][2][N], needed for depth >= 2 (NULL is accepted at depth 1): the levels alternate between scratch and out
+ * so that the last one writes out, and every level sets its target before it adds into it, so a second call into the same buffers
+ * gives the same words. 1 <= depth <= 30. Asynchronous and ordered on `stream`; no allocation; needs no loaded key. R = 0 is a
+ * no-op that returns RS_OK.
+ * RS_ERR_INVALID, before anything is launched: the refusals of rs_ring_cmux_dev with their texts (a null out, in or sel; basebit
+ * outside 1 .. 8; l < 1; l basebit > 31; row arithmetic that overflows; a grid that passes one launch); depth out of range; a null
+ * scratch with depth >= 2; an out that overlaps the rows `in` is read from, sel or scratch ("out overlaps in"); a scratch that
+ * overlaps in or sel. */
+int rs_ring_rotate_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, size_t R, size_t stride,
+                       const int32_t* sel, int32_t depth, int32_t per_row, int32_t step, int32_t basebit, int32_t l,
+                       int32_t* scratch, void* stream);
+int rs_ring_rotate_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, size_t R, size_t stride,
+                           const int32_t* sel, int32_t depth, int32_t per_row, int32_t step, int32_t basebit, int32_t l,
+                           int32_t* scratch, void* stream);
+/* u DEVICE int32[R width][N+1]: sample r width + c is the extraction of coefficient c < width of ciphertext r of rlwe DEVICE
+ * int32[R][2][N], in the convention of rs_rlwe_extract_dev (that call's word formula with the slot index replaced): the step
+ * between a rotated ciphertext and rs_keyswitch_dev. 1 <= width <= N; u must not overlap rlwe ("u overlaps rlwe"). Asynchronous, no
+ * allocation, no loaded key; R = 0 is a no-op. */
+int rs_ring_heads_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t R, size_t width, void* stream);
+
 /* Circuit bootstrapping (CGGI17 section 4): the selectors of rs_ring_cmux_dev / rs_ring_lookup_dev made
  * on the server from LWE bits it computed itself. rs_ring_selector_dev is the step in the middle, a keyswitch from LWE samples to
  * ring samples under two key families, one of them private (the message multiplied by -S(X)). Word-wise mod 2^32 with the

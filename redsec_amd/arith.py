@@ -12,6 +12,10 @@ the index -1, the constant FALSE. Nothing here computes on ciphertext words: tor
 
 select, maximum, equal and multiply go through compiled circuits instead (redsec_amd/circuit.py): the
 generator's netlist is compiled once per (function, bit count) and bound once per backend, and a call is one Backend.circuit_run.
+
+lookup and evaluate leave the gates for the ring pipeline (INTEGRATION.md sections 24 and 26): the encrypted bits become selectors
+by circuit bootstrapping, lookup returns a whole table row under the ring key, and evaluate returns f(index) as LWE samples the
+gates accept again.
 """
 import torch
 
@@ -112,3 +116,63 @@ def lookup(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks
         basebit, l = d[0] if basebit is None else basebit, d[1] if l is None else l
     sel = be.circuit_bootstrap(bits, basebit, l, key, ks_basebit, ks_t)
     return be.ring_lookup(table, sel, basebit, l, digits=digits)
+
+
+CIRCUIT_BOOTSTRAP_BITS = 30   # bits of one Backend.circuit_bootstrap call (rs_circuit_bootstrap_dev: depth <= 30)
+
+
+def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_basebit=None, ks_t=None, digits="signed", keyswitch=True):
+    """f(index) for a function given as a table, of an index the server holds as encrypted bits -> int32
+    CUDA tensor [R width][W] under the loaded key, what the gates accept: rows r width .. r width + width - 1 are the `width` torus
+    words of entry index_r. With keyswitch=False the extracted samples [R width][N+1] under the ring key read as an LWE key.
+    index_bits: [depth][W] or [depth][R][W], LSB first, +-1/8 under the loaded key; values: int32 torus words [2^depth width] (a
+    tensor or an array), entry i at i width .. i width + width - 1; key: a client.SelectorKey, or the tensor of
+    Backend.upload_selector_key with explicit ks_basebit and ks_t. basebit, l default to keygen.circuit_bootstrap_default of the
+    backend's set at the total CMUX depth and digit form; a depth or step that search refuses raises its ValueError unchanged.
+    Where 2^depth width <= N the table is one trivial row: Backend.circuit_bootstrap over all R depth bits (in calls of at most 30
+    bits, what one call takes), the row broadcast with stride 0, one Backend.ring_rotate with per-row selectors and step = -width,
+    Backend.ring_heads, then Backend.keyswitch: l bootstraps per input bit and none per table entry. A longer table is laid out as
+    rows of floor-power-of-two(N / width) entries: the high bits choose the row through Backend.ring_lookup, one call per index
+    (batching the lookup is out of scope here), and the low bits rotate the chosen rows as above."""
+    from . import keygen
+    keygen._check_cmux_form(digits)
+    N, W = be.p.N, index_bits.shape[-1]
+    depth = index_bits.shape[0]
+    bits = index_bits.reshape(depth, -1, W)
+    R, width = bits.shape[1], int(width)
+    if not 1 <= width <= N:
+        raise ValueError("width = %d is outside 1 .. %d" % (width, N))
+    if not 1 <= depth <= keygen.RING_LOOKUP_MAX_DEPTH:
+        raise ValueError("depth = %d is outside 1 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+    values = torch.as_tensor(values, dtype=torch.int32).to(bits.device).reshape(-1)
+    if values.numel() != (width << depth):
+        raise ValueError("values holds %d words, 2^%d entries of %d words are %d" % (values.numel(), depth, width, width << depth))
+    if basebit is None or l is None:
+        d = keygen.circuit_bootstrap_default(keygen.set_name(be.p), depth, digits=digits)
+        basebit, l = d[0] if basebit is None else basebit, d[1] if l is None else l
+    if hasattr(key, "body"):
+        ks_basebit, ks_t, key = key.ks_basebit, key.ks_t, be.upload_selector_key(key)
+    # selectors [R][depth][2l][2][N]: bit k of index r is sample r depth + k
+    flat = bits.permute(1, 0, 2).contiguous().reshape(R * depth, W)
+    sel = be.empty(R, depth, 2 * l, 2, N)
+    rows = sel.view(R * depth, 2 * l, 2, N)
+    for first in range(0, R * depth, CIRCUIT_BOOTSTRAP_BITS):
+        last = min(first + CIRCUIT_BOOTSTRAP_BITS, R * depth)
+        be.circuit_bootstrap(flat[first:last], basebit, l, key, ks_basebit, ks_t, out=rows[first:last])
+    low = min(depth, (N // width).bit_length() - 1)             # 2^low width <= N
+    per = width << low
+    table = torch.zeros(1 << (depth - low), 2, N, dtype=torch.int32, device=bits.device)
+    table[:, 1, :per] = values.view(-1, per)
+    if low == depth:
+        chosen, stride = table, 0
+    else:
+        chosen, stride = be.empty(R, 2, N), 1
+        for r in range(R):
+            be.ring_lookup(table, sel[r, low:], basebit, l, out=chosen[r], digits=digits)
+    if low:
+        turned = be.ring_rotate(chosen, sel if low == depth else sel[:, :low].contiguous(), -width, basebit, l, stride=stride,
+                                per_row=True, digits=digits)
+    else:
+        turned = chosen
+    u = be.ring_heads(turned, width)
+    return be.keyswitch(u) if keyswitch else u

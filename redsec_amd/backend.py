@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "rs_ring_rekey_dev",
     "rs_ring_cmux_dev", "rs_ring_lookup_dev", "rs_ring_cmux_alt_dev", "rs_ring_lookup_alt_dev",
     "rs_ring_selector_dev", "rs_circuit_bootstrap_dev",
+    "rs_ring_rotate_dev", "rs_ring_rotate_alt_dev", "rs_ring_heads_dev",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -142,6 +143,9 @@ def load_library(path=None):
     L.rs_ring_lookup_dev.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.rs_ring_cmux_alt_dev.argtypes = L.rs_ring_cmux_dev.argtypes
     L.rs_ring_lookup_alt_dev.argtypes = L.rs_ring_lookup_dev.argtypes
+    L.rs_ring_rotate_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.rs_ring_rotate_alt_dev.argtypes = L.rs_ring_rotate_dev.argtypes
+    L.rs_ring_heads_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     L.rs_ring_selector_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
     L.rs_circuit_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
@@ -662,6 +666,61 @@ class Backend:
         scratch = self.empty(first + (first + 1) // 2, 2, N) if depth > 1 else None
         _check(self.L, call(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
                             basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
+        return out
+
+    # ---- encrypted rotation ----
+    def ring_rotate(self, rlwe, sel, step=-1, basebit=None, l=None, stride=1, per_row=None, out=None, digits="signed"):
+        """out[r] = X^(step index_r) rlwe[r stride] for the index encrypted in sel (rs_ring_rotate_dev, on torch's current stream)
+        -> int32 CUDA tensor [R][2][N] (or into `out`; an `out` that overlaps an input is refused with ValueError). step = -1 brings
+        slot `index` to coefficient 0, step = -w slots w index .. w index + w - 1 to coefficients 0 .. w - 1. rlwe: int32 CUDA
+        tensor [rows][2][N]; stride >= 1 reads every stride-th row, stride = 0 starts every row from rlwe[0] (R is then the number
+        of selector sets). sel: a client.RingSelector (one hidden index for all rows; uploaded on this context's device) or an int32
+        CUDA tensor with explicit basebit and l: [depth][2l][2][N], or [R][depth][2l][2][N] with one index per row. per_row is
+        inferred from a 5-D tensor where it is None. The scratch of the call, R ciphertexts, is allocated here. digits: as
+        ring_cmux ("alternating": rs_ring_rotate_alt_dev). Needs no loaded key."""
+        from . import keygen
+        N = self.p.N
+        call = self.L.rs_ring_rotate_alt_dev if keygen._check_cmux_form(digits) == "alternating" else self.L.rs_ring_rotate_dev
+        if hasattr(sel, "body"):
+            basebit, l, sel = sel.basebit, sel.l, self.upload_ring_selector(sel)
+        if basebit is None or l is None:
+            raise ValueError("a selector given as a tensor needs explicit basebit and l")
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        per_row = sel.dim() == 5 if per_row is None else bool(per_row)
+        assert sel.dim() == (5 if per_row else 4) and tuple(sel.shape[-3:]) == (2 * l, 2, N), \
+            "sel must hold [depth][2l][2][N] words, or [R][depth][2l][2][N] with one index per row"
+        depth = sel.shape[-4]
+        if not 1 <= depth <= keygen.RING_LOOKUP_MAX_DEPTH:
+            raise ValueError("depth = %d is outside 1 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+        stride = int(stride)
+        if stride < 0:
+            raise ValueError("stride = %d is below 0" % stride)
+        assert rlwe.numel() and rlwe.numel() % (2 * N) == 0, "rlwe must hold [rows][2][N] words"
+        rows = rlwe.numel() // (2 * N)
+        R = (sel.shape[0] if per_row else 1) if stride == 0 else -(-rows // stride)
+        assert not per_row or sel.shape[0] == R, "one selector set per row"
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        read = ((R - 1) * stride + 1) * 2 * N
+        _refuse_overlap("out", out, out.numel(), (("in", rlwe, read), ("sel", sel, sel.numel())))
+        scratch = self.empty(R, 2, N) if depth > 1 else None
+        _check(self.L, call(self.h, self._ck_dev(out), self._ck_dev(rlwe), R, stride, self._ck_dev(sel), depth, int(per_row), int(step),
+                            basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
+        return out
+
+    def ring_heads(self, rlwe, width=1, out=None):
+        """The LWE samples of coefficients 0 .. width - 1 of each ciphertext of rlwe [R][2][N] (rs_ring_heads_dev, on torch's current
+        stream): sample r width + c is coefficient c of ciphertext r in the convention of rlwe_extract -> int32 CUDA tensor
+        [R width][N+1], ready for keyswitch (or into `out`; an `out` that overlaps rlwe is refused with ValueError)."""
+        N, width = self.p.N, int(width)
+        if not 1 <= width <= N:
+            raise ValueError("width = %d is outside 1 .. %d" % (width, N))
+        assert rlwe.numel() % (2 * N) == 0, "rlwe must hold [R][2][N] words"
+        R = rlwe.numel() // (2 * N)
+        out = self.empty(R * width, N + 1) if out is None else out
+        assert out.numel() == R * width * (N + 1), "out must hold [R width][N+1] words"
+        _refuse_overlap("u", out, out.numel(), (("rlwe", rlwe, rlwe.numel()),))
+        _check(self.L, self.L.rs_ring_heads_dev(self.h, self._ck_dev(out), self._ck_dev(rlwe), R, width, self._stream()))
         return out
 
     def upload_ring_selector(self, sel):

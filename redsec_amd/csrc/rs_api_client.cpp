@@ -16,6 +16,7 @@
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
 #include "rs_ring_rekey.h"
+#include "rs_ring_rotate.h"
 #include "rs_ring_selector.h"
 #include "rs_rlwe.h"
 
@@ -71,6 +72,16 @@ int refuse_digits(int32_t basebit, int32_t t, bool digits) {
 int refuse_overlap(const rs::Extent& written, std::initializer_list<rs::Extent> others) {
   const int i = rs::first_overlap(written, others.begin(), (int)others.size());
   if (i >= 0) return fail(RS_ERR_INVALID, "%s overlaps %s", written.name, others.begin()[i].name);
+  return RS_OK;
+}
+// The same refusal, with the same text, for a call that lists its ranges once: the first `n_written` of `ranges` are written (out,
+// then scratch), and each of them shares no byte with any range behind it.
+int refuse_written(std::initializer_list<rs::Extent> ranges, int n_written) {
+  for (int w = 0; w < n_written; ++w) {
+    const rs::Extent* x = ranges.begin() + w;
+    const int i = rs::first_overlap(*x, x + 1, (int)ranges.size() - w - 1);
+    if (i >= 0) return fail(RS_ERR_INVALID, "%s overlaps %s", x->name, x[1 + i].name);
+  }
   return RS_OK;
 }
 constexpr size_t kWord = sizeof(int32_t);
@@ -401,6 +412,63 @@ int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t ent
 int rs_ring_lookup_alt_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
                            int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
   return ring_lookup_any(c, out, table, entries, sel, depth, basebit, l, scratch, rs::kRcAlternating, stream);
+}
+
+// encrypted rotation (include/redsec_hip.h; kernels of rs_ring_rotate.hip): a chain of `depth` CMUXes between acc and X^(e_k) acc,
+// e_k = (step 2^k) mod 2N. The levels alternate between scratch and out so that the last one writes out; level 0 reads `in` at
+// `stride`, the later ones the previous level's rows. Either digit form: every level carries `form`.
+static int ring_rotate_any(rs_ctx* c, int32_t* out, const int32_t* in, size_t R, size_t stride, const int32_t* sel, int32_t depth,
+                           int32_t per_row, int32_t step, int32_t basebit, int32_t l, int32_t* scratch, int form, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !in || !sel) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_cmux_shape(c, basebit, l, &N)) != RS_OK) return rc;
+  if (depth < 1 || depth > rs::kRoMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 1 .. %d", (int)depth, rs::kRoMaxDepth);
+  if (depth > 1 && !scratch) return fail(RS_ERR_INVALID, "null scratch with depth = %d", (int)depth);
+  if ((rc = ring_cmux_rows(R, stride, N, l)) != RS_OK) return rc;
+  const size_t ct = 2 * N, sel_words = rs::ro_sel_words((int)N, (int)l), set_words = (size_t)depth * sel_words;
+  if (per_row && R > (size_t)LONG_MAX / kWord / set_words)
+    return fail(RS_ERR_INVALID, "R = %zu is too large for selector sets of %zu bytes", R, set_words * kWord);
+  if (R == 0) return RS_OK;
+  const rs::Extent x_in{"in", in, ((R - 1) * stride + 1) * ct * kWord}, x_sel{"sel", sel, (per_row ? R : 1) * set_words * kWord};
+  const rs::Extent x_scratch{"scratch", depth > 1 ? scratch : nullptr, R * ct * kWord};
+  if ((rc = refuse_written({{"out", out, R * ct * kWord}, x_scratch, x_in, x_sel}, 2)) != RS_OK) return rc;
+  const int32_t* src = in;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = ((depth - 1 - k) & 1) ? scratch : out;          // the last level writes out
+    const rs::RingRotateArgs a{o, src, sel + (size_t)k * sel_words, (long)R, (long)(k ? 1 : stride), per_row ? set_words : 0,
+                               (int)N, (int)basebit, (int)l, rs::ro_exponent(step, k, (int)N), form};
+    RS_HIP(rs::launch_ring_rotate_level(a, (hipStream_t)stream));
+    src = o;
+  }
+  return RS_OK;
+}
+int rs_ring_rotate_dev(rs_ctx* c, int32_t* out, const int32_t* in, size_t R, size_t stride, const int32_t* sel, int32_t depth,
+                       int32_t per_row, int32_t step, int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+  return ring_rotate_any(c, out, in, R, stride, sel, depth, per_row, step, basebit, l, scratch, rs::kRcSigned, stream);
+}
+int rs_ring_rotate_alt_dev(rs_ctx* c, int32_t* out, const int32_t* in, size_t R, size_t stride, const int32_t* sel, int32_t depth,
+                           int32_t per_row, int32_t step, int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
+  return ring_rotate_any(c, out, in, R, stride, sel, depth, per_row, step, basebit, l, scratch, rs::kRcAlternating, stream);
+}
+
+// the samples of coefficients 0 .. width - 1 of each of R ciphertexts (ring_heads_kernel): what rs_keyswitch_dev takes
+int rs_ring_heads_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t R, size_t width, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!u || !rlwe) return fail(RS_ERR_INVALID, "null pointer");
+  const size_t N = (size_t)c->p.N;
+  if (N < (size_t)rs::kRlMinN || N > (size_t)rs::kRlMaxN) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
+  if (width < 1 || width > N) return fail(RS_ERR_INVALID, "width = %zu is outside 1 .. %zu", width, N);
+  const size_t row_bytes = (N + 1) * sizeof(int32_t);
+  if (R > (size_t)INT32_MAX / width || R * width > (size_t)LONG_MAX / row_bytes)
+    return fail(RS_ERR_INVALID, "R = %zu at width %zu is too large for rows of %zu bytes", R, width, row_bytes);
+  if (R == 0) return RS_OK;
+  if ((rc = refuse_written({{"u", u, R * width * row_bytes}, {"rlwe", rlwe, R * 2 * N * kWord}}, 1)) != RS_OK) return rc;
+  const rs::RingHeadsArgs x{u, rlwe, (long)R, (int)width, (int)N};
+  RS_HIP(rs::launch_ring_heads(x, (hipStream_t)stream));
+  return RS_OK;
 }
 
 // circuit bootstrapping (include/redsec_hip.h; kernels of rs_ring_selector.hip, integer arithmetic only). The checks the two calls

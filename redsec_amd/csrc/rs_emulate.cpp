@@ -19,6 +19,7 @@
 #include "rs_packkey.h"
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
+#include "rs_ring_rotate.h"
 #include "rs_ring_rekey.h"
 #include "rs_ring_selector.h"
 #include "rs_rlwe.h"
@@ -1612,6 +1613,85 @@ void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t
 void rs_emu_ring_lookup_alt(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
                             int32_t* scratch, int32_t* out) {
   emu_ring_lookup(table, entries, N, sel, depth, basebit, l, rs::kRcAlternating, scratch, out);
+}
+// ---- encrypted rotation (rs_ring_rotate_dev, rs_ring_heads_dev) through the functions of rs_ring_rotate.h ----
+int rs_emu_ring_rotate_exponent(int32_t step, int k, int N) { return rs::ro_exponent(step, k, N); }
+// source index of coefficient c of X^e v; *negate: the word is the negated coefficient
+int rs_emu_ring_rotate_source(int N, int e, int c, int* negate) {
+  bool neg;
+  const int idx = rs::ro_source(N, e, c, neg);
+  *negate = neg ? 1 : 0;
+  return idx;
+}
+// one level as launch_ring_rotate_level runs it: ring_rotate_init_kernel, then (e != 0) ring_rotate_kernel or ring_rotate_alt_kernel
+// workgroup by workgroup and thread by thread: ring_place, the staged window of the row's selector sample, the block's words
+// (X^e in)_c - in_c + offset read through ro_rotated_word (rc_stage_alt of the difference in the alternating form, the parity that
+// of the thread), ring_sweep / ring_sweep_parity, the partial sums added into the output
+static void emu_ring_rotate_level(const int32_t* in_, long R, long stride, int N, const int32_t* sel_, size_t sel_stride, int e,
+                                  int basebit, int l, int form, int32_t* out_) {
+  if (R <= 0) return;
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_);
+  const uint32_t* in = reinterpret_cast<const uint32_t*>(in_);
+  const uint32_t* sel = reinterpret_cast<const uint32_t*>(sel_);
+  const long per = 2 * (long)N;
+  for (long idx = 0; idx < R * per; ++idx) out[idx] = in[(size_t)(idx / per) * (size_t)stride * (size_t)per + (size_t)(idx % per)];
+  if (e == 0) return;
+  const uint32_t off = rs::rc_offset(basebit, l);
+  std::vector<uint32_t> win((size_t)rs::kRingWindow), sx((size_t)rs::kRingSlots);
+  for (long blk = 0; blk < rs::rc_groups(R, N, l); ++blk) {
+    const rs::RingPlace pl = rs::ring_place((unsigned)blk, N, 2 * l);
+    const int jr = pl.row, j = jr < l ? jr : jr - l, spoly = jr < l ? 0 : 1;
+    const int c0 = pl.sb * rs::kRingSlots, k0 = pl.tile * rs::kRingTile;
+    const uint32_t* v = in + ((size_t)pl.r * (size_t)stride * 2 + (size_t)spoly) * (size_t)N;
+    const uint32_t* p = sel + (size_t)pl.r * sel_stride + rs::rc_sel_offset(N, jr, pl.poly);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      rs::sweep_stage_window(win.data(), p, N, rs::ring_window_base(N, k0, c0), rs::kRingWindow, th, rs::kRingThreads);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      for (int cc = th; cc < rs::kRingSlots; cc += rs::kRingThreads) {
+        const uint32_t x = rs::ro_rotated_word(v, N, e, c0 + cc) - v[c0 + cc];
+        sx[cc] = form == rs::kRcAlternating ? rs::rc_stage_alt(x, off, th & 1) : x + off;
+      }
+    for (int th = 0; th < rs::kRingThreads; ++th) {
+      uint32_t acc[rs::kSweepKpt] = {0u, 0u, 0u, 0u};
+      if (form == rs::kRcAlternating)
+        rs::ring_sweep_parity(win.data(), sx.data(), rs::kRingSlots, th,
+                              [=](uint32_t xbar, auto slot_odd) { return rs::rc_digit_alt(xbar, basebit, j, decltype(slot_odd)::value); }, acc);
+      else
+        rs::ring_sweep(win.data(), sx.data(), rs::kRingSlots, th, [=](uint32_t xbar) { return rs::rc_digit(xbar, basebit, j); }, acc);
+      uint32_t* o = out + ((size_t)pl.r * 2 + pl.poly) * N + k0 + rs::kSweepKpt * th;
+      for (int q = 0; q < rs::kSweepKpt; ++q) o[q] += acc[q];
+    }
+  }
+}
+// rs_ring_rotate_dev's levels as the host code orders them: level 0 from `in` at `stride`, the later ones from the previous target,
+// scratch and out in turn so that the last level writes out
+static void emu_ring_rotate(const int32_t* in, long R, long stride, int N, const int32_t* sel, int depth, int per_row, int32_t step,
+                            int basebit, int l, int form, int32_t* scratch, int32_t* out) {
+  const size_t sel_words = rs::ro_sel_words(N, l), set_words = (size_t)depth * sel_words;
+  const int32_t* src = in;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = ((depth - 1 - k) & 1) ? scratch : out;
+    emu_ring_rotate_level(src, R, k ? 1 : stride, N, sel + (size_t)k * sel_words, per_row ? set_words : 0, rs::ro_exponent(step, k, N),
+                          basebit, l, form, o);
+    src = o;
+  }
+}
+void rs_emu_ring_rotate(const int32_t* in, long R, long stride, int N, const int32_t* sel, int depth, int per_row, int32_t step,
+                        int basebit, int l, int32_t* scratch, int32_t* out) {
+  emu_ring_rotate(in, R, stride, N, sel, depth, per_row, step, basebit, l, rs::kRcSigned, scratch, out);
+}
+void rs_emu_ring_rotate_alt(const int32_t* in, long R, long stride, int N, const int32_t* sel, int depth, int per_row, int32_t step,
+                            int basebit, int l, int32_t* scratch, int32_t* out) {
+  emu_ring_rotate(in, R, stride, N, sel, depth, per_row, step, basebit, l, rs::kRcAlternating, scratch, out);
+}
+// ring_heads_kernel: rlwe [R][2][N] -> u [R width][N+1], one workgroup per output row
+void rs_emu_ring_heads(const int32_t* rlwe, long R, long width, int N, int32_t* u) {
+  for (long i = 0; i < R * width; ++i) {
+    const long r = i / width;
+    const int c = (int)(i - r * width);
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(rlwe) + (size_t)r * 2 * N;
+    for (int j = 0; j <= N; ++j) u[(size_t)i * (N + 1) + j] = (int32_t)rs::rl_extract_word(a, a + N, N, c, j);
+  }
 }
 // ---- the refusal of an out that overlaps an input (rs_api_client.cpp refuse_overlap) through rs_host.h first_overlap ----
 // written = (address, bytes); others [count][2] the same pairs -> the index of the first one that shares a byte with it, or -1.

@@ -209,6 +209,25 @@ struct RingCmuxArgs {
 };
 hipError_t launch_ring_cmux(const RingCmuxArgs& a, hipStream_t st);      // ring_cmux_init_kernel, then the kernel of a.form
 hipError_t launch_ring_cmux_alt(const RingCmuxArgs& a, hipStream_t st);  // ring_cmux_alt_kernel alone (rs_ring_cmux_alt.hip): launch_ring_cmux calls it
+// encrypted rotation (rs_ring_rotate_dev, rs_ring_heads_dev; index arithmetic of rs_ring_rotate.h): ONE level of a chain
+struct RingRotateArgs {
+  int32_t* out;                                       // [R][2][N], contiguous
+  const int32_t* in;                                  // row r at in + r stride 2 N (stride 0: every row reads in[0])
+  const int32_t* sel;                                 // the level's sample [2l][2][N] of row r at sel + r sel_stride
+  long R, stride;
+  size_t sel_stride;                                  // words between the samples of consecutive rows; 0: one sample for all
+  int N, basebit, l;
+  int e;                                              // the level's exponent, 0 .. 2 N - 1
+  int form;                                           // kRcSigned or kRcAlternating (rs_ring_cmux.h)
+};
+hipError_t launch_ring_rotate_level(const RingRotateArgs& a, hipStream_t st);   // ring_rotate_init_kernel, then the kernel of a.form (e = 0: the copy alone)
+struct RingHeadsArgs {
+  int32_t* u;                                         // [R width][N+1]
+  const int32_t* rlwe;                                // [R][2][N]
+  long R;
+  int width, N;
+};
+hipError_t launch_ring_heads(const RingHeadsArgs& x, hipStream_t st);
 // the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev; placement and index arithmetic of rs_ring_selector.h)
 struct RingSelectorArgs {
   int32_t* sel;                                       // [rows / l][2l][2][N]

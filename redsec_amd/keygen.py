@@ -1124,6 +1124,73 @@ def ring_trivial(values):
     return np.ascontiguousarray(np.stack([np.zeros_like(p), p], axis=-2))
 
 
+# ---- encrypted rotation (rs_ring_rotate_dev / rs_ring_heads_dev restated) ----
+
+def ring_monomial(rlwe, e):
+    """X^e times ring elements int32 [..., N] mod X^N + 1 (both polynomials of a ciphertext [..., 2, N] alike), e any integer: the
+    coefficients move up by e mod 2N and change sign each time they pass the top. A concatenate-and-negate, nothing like the
+    device's indexing (rs_ring_rotate.h ro_source)."""
+    v = np.ascontiguousarray(rlwe, np.int32).view(np.uint32)
+    N = v.shape[-1]
+    e = int(e) % (2 * N)
+    with np.errstate(over="ignore"):
+        ext = np.concatenate([v, np.uint32(0) - v], axis=-1)                 # the coefficients of v as a polynomial mod X^2N - 1
+        return np.ascontiguousarray(np.roll(ext, e, axis=-1)[..., :N]).view(np.int32)
+
+
+def ring_rotate(rlwe, sel, step, basebit, l, digits="signed", per_row=False, stride=1):
+    """rs_ring_rotate_dev restated (digits="alternating": rs_ring_rotate_alt_dev): rlwe int32 [rows][2][N], read at `stride` (0:
+    every row starts from rlwe[0], and R is then the number of selector sets), sel int32 [depth][2l][2][N] (one hidden index for
+    all rows) or, with per_row, [R][depth][2l][2][N] -> int32 [R][2][N]. Level k is ring_cmux between the accumulator and
+    ring_monomial(accumulator, step 2^k) under sample k, least significant bit first, so phase(out[r]) = X^(step index_r)
+    phase(rlwe[r stride]) + noise: step = -1 brings slot `index` to coefficient 0.
+    Noise: that of `depth` CMUXes, ring_cmux_sigma(..., depth) for a client's selectors and circuit_bootstrap_sigma(..., depth,
+    coefficient=None) for produced ones. Later levels move a level's error to other coefficients and flip signs; they do not grow
+    it, so the worst-coefficient deviation per level still bounds every coefficient. There is no formula of its own."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    _check_cmux_form(digits)
+    sel = np.ascontiguousarray(sel, np.int32)
+    assert sel.ndim == (5 if per_row else 4) and sel.shape[-3:-1] == (2 * l, 2), "sel must hold [depth][2l][2][N] words ([R][depth].. per row)"
+    depth, N = sel.shape[-4], sel.shape[-1]
+    if not 1 <= depth <= RING_LOOKUP_MAX_DEPTH:
+        raise ValueError("depth = %d is outside 1 .. %d" % (depth, RING_LOOKUP_MAX_DEPTH))
+    rows = np.ascontiguousarray(rlwe, np.int32).reshape(-1, 2, N)
+    stride = int(stride)
+    if stride < 0:
+        raise ValueError("stride = %d is below 0" % stride)
+    if stride == 0:
+        acc = np.repeat(rows[:1], sel.shape[0] if per_row else 1, axis=0)
+    else:
+        acc = rows[::stride].copy()
+    assert not per_row or sel.shape[0] == acc.shape[0], "one selector set per row"
+    for k in range(depth):
+        turned = ring_monomial(acc, int(step) << k)
+        if per_row:
+            acc = np.concatenate([ring_cmux(turned[r:r + 1], acc[r:r + 1], sel[r, k], basebit, l, digits) for r in range(acc.shape[0])])
+        else:
+            acc = ring_cmux(turned, acc, sel[k], basebit, l, digits)
+    return acc
+
+
+def ring_heads(rlwe, width=1):
+    """rs_ring_heads_dev restated: sample r width + c is the LWE sample of coefficient c < width of ciphertext r (rlwe_extract's
+    formula with the slot index replaced) -> int32 [R width][N+1]."""
+    rlwe = np.ascontiguousarray(rlwe, np.int32)
+    N = rlwe.shape[-1]
+    rlwe = rlwe.reshape(-1, 2, N)
+    width = int(width)
+    if not 1 <= width <= N:
+        raise ValueError("width = %d is outside 1 .. %d" % (width, N))
+    out = np.empty((rlwe.shape[0], width, N + 1), np.int32)
+    j, c = np.arange(N)[None, :], np.arange(width)[:, None]
+    with np.errstate(over="ignore"):
+        for r in range(rlwe.shape[0]):
+            words = rlwe[r, 0].view(np.uint32)[(c - j) % N]
+            out[r, :, :N] = np.where(j > c, np.uint32(0) - words, words).view(np.int32)
+            out[r, :, N] = rlwe[r, 1, :width]
+    return out.reshape(-1, N + 1)
+
+
 def ring_selector_mask(mask_seed, N, rows):
     """The mask polynomials of selector rows: words 0 .. N-1 of stream (18, row) of the mask seed -> int32 [R][N]."""
     rows = np.asarray(rows, np.int64).ravel()
