@@ -435,6 +435,25 @@ int rs_ring_selector_dev(rs_ctx* ctx, int32_t* sel, const int32_t* ct, int32_t d
  * rs_ring_selector_dev, and RS_ERR_INVALID also for a null bits or scratch and for those overlaps ("sel overlaps scratch"). */
 int rs_circuit_bootstrap_dev(rs_ctx* ctx, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
                              const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream);
+/* The batch forms: any number of bits in one call. `count` replaces depth and is bounded only by what
+ * one launch can index; the arithmetic, the key format, the digit rules, the checks and the refusals are those of the two calls
+ * above with the extents computed from count: ct DEVICE int32[count l][n_src+1], bits DEVICE int32[count][n+1], sel DEVICE
+ * int32[count][2l][2][N], scratch DEVICE int32[l N + count l (2 (n + 1) + 1)] in the same layout. Every word of sel equals what the
+ * calls above give for the same bits taken 30 at a time, in all three arithmetic modes. rs_circuit_bootstrap_batch_dev runs the
+ * same steps with ONE rs_bootstrap_lut_dev launch over the count l rows. The keyswitch runs in one of two forms, chosen from the row
+ * count and the context's compute units: the chunked kernel of rs_ring_selector_dev (atomic adds), or, as soon as count l rows
+ * give every compute unit a workgroup of it, a wide kernel that sums all n_src + 1 coordinates in registers and stores each word
+ * once. RS_SEL_FORM=wide|chunked, read once in rs_create, forces a form at any size (diagnostics and tests); rs_ring_selector_dev
+ * always takes the chunked kernel. sel must be 16-byte aligned ("sel must be 16-byte aligned"). A count whose rows pass one launch
+ * is refused with RS_ERR_INVALID ("count l = ... rows are too many for one launch") before anything is launched; count = 0 is a
+ * no-op that returns RS_OK. Asynchronous and ordered on `stream`; no allocation; a second call into the same buffers gives the
+ * same words. */
+int rs_ring_selector_batch_dev(rs_ctx* ctx, int32_t* sel, const int32_t* ct, size_t count, int32_t basebit, int32_t l,
+                               int32_t n_src, const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream);
+int rs_circuit_bootstrap_batch_dev(rs_ctx* ctx, int32_t* sel, const int32_t* bits, size_t count, int32_t basebit, int32_t l,
+                                   const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream);
+/* Form (0 chunked, 1 wide) and workgroups of the context's last selector keyswitch, batch or not; RS_ERR_STATE before the first. */
+int rs_last_selector(rs_ctx* ctx, int32_t* form, int64_t* workgroups);
 
 /* The packing key on the device: generation, expansion on load and (below, rs_audit_pack_key_dev) the
  * exact noise audit, the three steps the evaluation key has. n and N are the context's; row i t + j of the key is K[i][j]. All three

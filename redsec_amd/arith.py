@@ -118,7 +118,8 @@ def lookup(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks
     return be.ring_lookup(table, sel, basebit, l, digits=digits)
 
 
-CIRCUIT_BOOTSTRAP_BITS = 30   # bits of one Backend.circuit_bootstrap call (rs_circuit_bootstrap_dev: depth <= 30)
+CIRCUIT_BOOTSTRAP_BITS = 30   # bits of one Backend.circuit_bootstrap call (rs_circuit_bootstrap_dev: depth <= 30); evaluate itself takes
+                              # Backend.circuit_bootstrap_batch, tools/ring_rotate_time.py restates the route of calls of 30 with this
 
 
 def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_basebit=None, ks_t=None, digits="signed", keyswitch=True):
@@ -129,8 +130,8 @@ def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_base
     tensor or an array), entry i at i width .. i width + width - 1; key: a client.SelectorKey, or the tensor of
     Backend.upload_selector_key with explicit ks_basebit and ks_t. basebit, l default to keygen.circuit_bootstrap_default of the
     backend's set at the total CMUX depth and digit form; a depth or step that search refuses raises its ValueError unchanged.
-    Where 2^depth width <= N the table is one trivial row: Backend.circuit_bootstrap over all R depth bits (in calls of at most 30
-    bits, what one call takes), the row broadcast with stride 0, one Backend.ring_rotate with per-row selectors and step = -width,
+    Where 2^depth width <= N the table is one trivial row: ONE Backend.circuit_bootstrap_batch over all R depth bits (INTEGRATION.md
+    section 27), the row broadcast with stride 0, one Backend.ring_rotate with per-row selectors and step = -width,
     Backend.ring_heads, then Backend.keyswitch: l bootstraps per input bit and none per table entry. A longer table is laid out as
     rows of floor-power-of-two(N / width) entries: the high bits choose the row through Backend.ring_lookup, one call per index
     (batching the lookup is out of scope here), and the low bits rotate the chosen rows as above."""
@@ -155,10 +156,7 @@ def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_base
     # selectors [R][depth][2l][2][N]: bit k of index r is sample r depth + k
     flat = bits.permute(1, 0, 2).contiguous().reshape(R * depth, W)
     sel = be.empty(R, depth, 2 * l, 2, N)
-    rows = sel.view(R * depth, 2 * l, 2, N)
-    for first in range(0, R * depth, CIRCUIT_BOOTSTRAP_BITS):
-        last = min(first + CIRCUIT_BOOTSTRAP_BITS, R * depth)
-        be.circuit_bootstrap(flat[first:last], basebit, l, key, ks_basebit, ks_t, out=rows[first:last])
+    be.circuit_bootstrap_batch(flat, basebit, l, key, ks_basebit, ks_t, out=sel.view(R * depth, 2 * l, 2, N))
     low = min(depth, (N // width).bit_length() - 1)             # 2^low width <= N
     per = width << low
     table = torch.zeros(1 << (depth - low), 2, N, dtype=torch.int32, device=bits.device)

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "rs_ring_cmux_dev", "rs_ring_lookup_dev", "rs_ring_cmux_alt_dev", "rs_ring_lookup_alt_dev",
     "rs_ring_selector_dev", "rs_circuit_bootstrap_dev",
     "rs_ring_rotate_dev", "rs_ring_rotate_alt_dev", "rs_ring_heads_dev",
+    "rs_ring_selector_batch_dev", "rs_circuit_bootstrap_batch_dev", "rs_last_selector",
 ]
 
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -148,6 +149,9 @@ def load_library(path=None):
     L.rs_ring_heads_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     L.rs_ring_selector_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
     L.rs_circuit_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
+    L.rs_ring_selector_batch_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
+    L.rs_circuit_bootstrap_batch_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
+    L.rs_last_selector.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.rs_pack_keygen_dev.argtypes = [vp, vp, _i32p, _i32p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_double]
     L.rs_pack_expand_dev.argtypes = [vp, vp, C.c_char_p, vp, C.c_int32, vp]
     L.rs_audit_pack_key_dev.argtypes = [vp, C.POINTER(RsPackKeyAudit), vp, vp, C.c_char_p, _i32p, _i32p, C.c_int32, C.c_int32, C.c_uint32]
@@ -798,6 +802,54 @@ class Backend:
             _check(self.L, self.L.rs_circuit_bootstrap_dev(self.h, self._ck_dev(out), self._ck_dev(bits), depth, basebit, l,
                                                            self._ck_dev(key), ks_basebit, ks_t, self._ck_dev(scratch), self._stream()))
         return out
+
+    # ---- batched circuit bootstrapping ----
+    def ring_selector_batch(self, ct, basebit, l, key, ks_basebit=None, ks_t=None, n_src=None, out=None):
+        """ring_selector for any number of bits in one call (rs_ring_selector_batch_dev, on torch's current stream): ct int32 CUDA
+        tensor [count l][n_src+1] -> int32 CUDA tensor [count][2l][2][N] (or into `out`, 16-byte aligned; an `out` that overlaps an
+        input is refused with ValueError), the words ring_selector gives for the same rows taken 30 bits at a time. key, ks_basebit,
+        ks_t and n_src as in ring_selector. The library picks the kernel from the row count (last_selector tells which)."""
+        from . import keygen
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        n_src = ct.shape[-1] - 1 if n_src is None else int(n_src)
+        if not 1 <= n_src <= keygen.SELECTOR_MAX_SRC:
+            raise ValueError("n_src = %d is outside 1 .. %d" % (n_src, keygen.SELECTOR_MAX_SRC))
+        key, ks_basebit, ks_t = self._selector_key(key, ks_basebit, ks_t, n_src)
+        assert ct.numel() % ((n_src + 1) * l) == 0, "ct must hold [count l][n_src+1] words"
+        count = ct.numel() // ((n_src + 1) * l)
+        out = self.empty(count, 2 * l, 2, self.p.N) if out is None else out
+        assert out.numel() == count * 2 * l * 2 * self.p.N, "out must hold [count][2l][2][N] words"
+        _refuse_overlap("sel", out, out.numel(), (("ct", ct, ct.numel()), ("sel_key", key, key.numel())))
+        if count:
+            _check(self.L, self.L.rs_ring_selector_batch_dev(self.h, self._ck_dev(out), self._ck_dev(ct), count, basebit, l, n_src,
+                                                             self._ck_dev(key), ks_basebit, ks_t, self._stream()))
+        return out
+
+    def circuit_bootstrap_batch(self, bits, basebit, l, key, ks_basebit=None, ks_t=None, out=None):
+        """circuit_bootstrap for any number of bits in one call (rs_circuit_bootstrap_batch_dev, on torch's current stream): bits
+        int32 CUDA tensor [count][n+1] at +-1/8 under the loaded key -> int32 CUDA tensor [count][2l][2][N], selector k of bit k (or
+        into `out`), the words circuit_bootstrap gives for the same bits taken 30 at a time: ONE bootstrap launch over the count l
+        rows, then one selector keyswitch. key as in ring_selector, of the context's n. The scratch of the call is allocated here.
+        Needs a loaded evaluation key."""
+        from . import keygen
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        key, ks_basebit, ks_t = self._selector_key(key, ks_basebit, ks_t, self.p.n)
+        assert bits.numel() % self.W == 0, "bits must hold [count][n+1] words"
+        count = bits.numel() // self.W
+        out = self.empty(count, 2 * l, 2, self.p.N) if out is None else out
+        assert out.numel() == count * 2 * l * 2 * self.p.N, "out must hold [count][2l][2][N] words"
+        _refuse_overlap("sel", out, out.numel(), (("bits", bits, bits.numel()), ("sel_key", key, key.numel())))
+        if count:
+            scratch = self.empty(l * self.p.N + count * l * (2 * self.W + 1))
+            _check(self.L, self.L.rs_circuit_bootstrap_batch_dev(self.h, self._ck_dev(out), self._ck_dev(bits), count, basebit, l,
+                                                                 self._ck_dev(key), ks_basebit, ks_t, self._ck_dev(scratch), self._stream()))
+        return out
+
+    def last_selector(self):
+        """(form, workgroups) of this context's last selector keyswitch (ring_selector, circuit_bootstrap and their batch forms)."""
+        f, n = C.c_int32(), C.c_int64()
+        _check(self.L, self.L.rs_last_selector(self.h, C.byref(f), C.byref(n)))
+        return {"form": ("chunked", "wide")[f.value], "workgroups": n.value}   # rs_ring_selector.h SeForm
 
     # ---- the packing key on the device (INTEGRATION.md section 19) ----
     def _secrets(self, lwe_key, tlwe_key):

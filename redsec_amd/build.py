@@ -61,6 +61,9 @@ HIP_OBJECTS = [
     # the selector keyswitch of circuit bootstrapping (ring_selector_init_kernel, ring_selector_kernel, circuit_prepare_kernel),
     # likewise in an object of its own; integer-only sources, as rs_pack
     ("rs_ring_selector", "rs_ring_selector.hip", []),
+    # its wide form for batches of thousands of rows (ring_selector_wide_kernel), likewise in an object of its own:
+    # ring_selector_kernel keeps its instructions
+    ("rs_ring_selector_wide", "rs_ring_selector_wide.hip", []),
     # the packing key on the device (pack_keygen_kernel, pack_expand_kernel), likewise; not in rs_pack: its sources stay integer-only
     ("rs_packkey", "rs_packkey.hip", []),
     # device decryption and the key audit (lwe_phase_kernel, audit_bk_kernel, audit_ksk_kernel), likewise in an object of their own

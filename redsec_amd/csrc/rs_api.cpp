@@ -443,6 +443,7 @@ int rs_create(rs_ctx** out, const rs_params* p, int device) {
   c->opts.no_persist = env_on("RS_NO_PERSIST"); c->opts.no_conv_tiled = env_on("RS_NO_CONV_TILED");
   c->opts.no_wg4 = env_on("RS_NO_WG4"); c->opts.no_tail = env_on("RS_NO_TAIL"); c->opts.no_coop8 = env_on("RS_NO_COOP8"); c->opts.no_coop8_listed = env_on("RS_NO_COOP8_LISTED"); c->opts.ks_atomics = env_on("RS_KS_ATOMICS"); c->opts.force_host_staged = env_on("RS_FORCE_HOST_STAGED"); c->opts.no_cohort = env_on("RS_NO_COHORT");
   if (const char* v = getenv("RS_KS_FORM")) c->ks_force = strcmp(v, "wide") == 0 ? rs::kKsWide : strcmp(v, "tiled") == 0 ? rs::kKsTiled : rs::kKsAuto;
+  if (const char* v = getenv("RS_SEL_FORM")) c->sel_force = strcmp(v, "wide") == 0 ? rs::kSeWide : strcmp(v, "chunked") == 0 ? rs::kSeChunked : rs::kSeAuto;
   Lane* ln = nullptr;
   if (lane_of(c, nullptr, &ln) != RS_OK) { destroy_ctx(c); return RS_ERR_HIP; }   // the default stream's lane
   *out = c;

@@ -473,8 +473,7 @@ int rs_ring_heads_dev(rs_ctx* c, int32_t* u, const int32_t* rlwe, size_t R, size
 
 // circuit bootstrapping (include/redsec_hip.h; kernels of rs_ring_selector.hip, integer arithmetic only). The checks the two calls
 // share: digit shapes, ring, depth, source dimension, and the workgroups of the launches. The keyswitch itself needs no key.
-static int ring_selector_shape(const rs_ctx* c, int32_t depth, int32_t basebit, int32_t l, int32_t n_src, const int32_t* sel_key,
-                               int32_t ks_basebit, int32_t ks_t, size_t* N_) {
+static int selector_digits_shape(int32_t basebit, int32_t l, int32_t ks_basebit, int32_t ks_t) {
   if (basebit < 1 || basebit > 8) return fail(RS_ERR_INVALID, "basebit = %d is outside 1 .. 8", (int)basebit);
   if (l < 1) return fail(RS_ERR_INVALID, "l = %d is below 1", (int)l);
   if ((int64_t)l * basebit > rs::kSeMaxBits)
@@ -482,18 +481,59 @@ static int ring_selector_shape(const rs_ctx* c, int32_t depth, int32_t basebit, 
   if (ks_basebit < 1 || ks_basebit > 8) return fail(RS_ERR_INVALID, "ks_basebit = %d is outside 1 .. 8", (int)ks_basebit);
   if (ks_t < 1) return fail(RS_ERR_INVALID, "ks_t = %d is below 1", (int)ks_t);
   if ((int64_t)ks_t * ks_basebit > 32) return fail(RS_ERR_INVALID, "ks_t ks_basebit = %d x %d passes 32 bits", (int)ks_t, (int)ks_basebit);
-  if (depth < 0 || depth > rs::kSeMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 0 .. %d", (int)depth, rs::kSeMaxDepth);
+  return RS_OK;
+}
+// the key's words and the grid of `form` (rs::kSeChunked: the init kernel's workgroups and rs::se_groups; rs::kSeWide: rs::sw_groups),
+// each inside what a launch and a long can index; `what` names the caller's count in the refusal
+static int selector_ring_shape(const rs_ctx* c, size_t rows, int form, const char* what, int32_t n_src, const int32_t* sel_key, int32_t ks_t,
+                               size_t* N_) {
   if (n_src < 1 || n_src > rs::kSeMaxSrc) return fail(RS_ERR_INVALID, "n_src = %d is outside 1 .. %d", (int)n_src, rs::kSeMaxSrc);
   const size_t N = (size_t)c->p.N;
   if (N < (size_t)rs::kSeMinN || N > (size_t)rs::kSeMaxN || (N & (N - 1))) return fail(RS_ERR_INVALID, "unsupported ring N = %zu", N);
   if ((uintptr_t)sel_key & 15u) return fail(RS_ERR_INVALID, "sel_key must be 16-byte aligned");
-  // the key's words, the init kernel's workgroups and rs::se_groups, each inside what a launch and a long can index
-  const size_t rows = (size_t)depth * (size_t)l, key_polys = 2 * ((size_t)n_src + 1) * (size_t)ks_t * 2;
+  const size_t key_polys = 2 * ((size_t)n_src + 1) * (size_t)ks_t * 2;
   if (key_polys > (size_t)LONG_MAX / sizeof(int32_t) / N) return fail(RS_ERR_INVALID, "a key of %zu polynomials is too large", key_polys);
-  if (rows * 4 * N / rs::kSeInitThreads > (size_t)INT32_MAX ||
-      (size_t)rs::se_row_blocks((long)rows) > (size_t)INT32_MAX / (size_t)rs::se_groups_per_block((int)N, (int)n_src))
-    return fail(RS_ERR_INVALID, "depth l = %zu rows are too many for one launch", rows);
+  const bool fits = rows > (size_t)INT32_MAX ? false
+                    : form == rs::kSeWide   ? (size_t)rs::sw_row_blocks((long)rows) <= (size_t)INT32_MAX / (size_t)rs::sw_groups_per_block((int)N)
+                                            : rows * 4 * N / rs::kSeInitThreads <= (size_t)INT32_MAX &&
+                                                  (size_t)rs::se_row_blocks((long)rows) <= (size_t)INT32_MAX / (size_t)rs::se_groups_per_block((int)N, (int)n_src);
+  if (!fits) return fail(RS_ERR_INVALID, "%s l = %zu rows are too many for one launch", what, rows);
   *N_ = N;
+  return RS_OK;
+}
+static int ring_selector_shape(const rs_ctx* c, int32_t depth, int32_t basebit, int32_t l, int32_t n_src, const int32_t* sel_key,
+                               int32_t ks_basebit, int32_t ks_t, size_t* N_) {
+  const int rc = selector_digits_shape(basebit, l, ks_basebit, ks_t);
+  if (rc) return rc;
+  if (depth < 0 || depth > rs::kSeMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 0 .. %d", (int)depth, rs::kSeMaxDepth);
+  return selector_ring_shape(c, (size_t)depth * (size_t)l, rs::kSeChunked, "depth", n_src, sel_key, ks_t, N_);
+}
+// the batch calls: any count whose rows one launch of the planned form can index; *plan = that form and its workgroups
+static int ring_selector_batch_shape(const rs_ctx* c, size_t count, int32_t basebit, int32_t l, int32_t n_src, const int32_t* sel_key,
+                                     int32_t ks_basebit, int32_t ks_t, size_t* N_, rs::SePlan* plan) {
+  const int rc = selector_digits_shape(basebit, l, ks_basebit, ks_t);
+  if (rc) return rc;
+  const size_t rows = count > (size_t)INT32_MAX ? SIZE_MAX : count * (size_t)l;
+  const long plan_rows = rows > (size_t)INT32_MAX ? (long)INT32_MAX : (long)rows;
+  const int N = c->p.N;
+  *plan = rs::selector_form(plan_rows, N >= rs::kSeMinN ? N : rs::kSeMinN, n_src, c->num_cus, c->sel_force);
+  return selector_ring_shape(c, rows, plan->form, "count", n_src, sel_key, ks_t, N_);
+}
+
+// What both forms of a call share behind their shape checks. `batch` = the batch form: sel 16-byte aligned (the wide kernel's
+// stores), the planned kernel; else the chunked kernel, whatever RS_SEL_FORM says.
+static int ring_selector_run(rs_ctx* c, int32_t* sel, const int32_t* ct, size_t rows, size_t N, bool batch, rs::SePlan plan, int32_t basebit,
+                             int32_t l, int32_t n_src, const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream) {
+  const size_t src_words = (size_t)n_src + 1;
+  const int rc = refuse_overlap({"sel", sel, rows * 4 * N * kWord}, {{"ct", ct, rows * src_words * kWord},
+                                                                  {"sel_key", sel_key, 2 * src_words * (size_t)ks_t * 2 * N * kWord}});
+  if (rc != RS_OK) return rc;
+  if (batch && ((uintptr_t)sel & 15u)) return fail(RS_ERR_INVALID, "sel must be 16-byte aligned");
+  const rs::RingSelectorArgs a{sel, ct, sel_key, (long)rows, (int)N, (int)n_src, (int)basebit, (int)l, (int)ks_basebit, (int)ks_t};
+  if (!batch) plan = rs::SePlan{rs::kSeChunked, rs::se_groups(a.rows, a.N, a.n_src)};
+  if (plan.form == rs::kSeWide) RS_HIP(rs::launch_ring_selector_wide(a, (hipStream_t)stream));
+  else RS_HIP(rs::launch_ring_selector(a, (hipStream_t)stream));
+  c->sel_form = plan.form; c->sel_groups = plan.groups;
   return RS_OK;
 }
 
@@ -505,36 +545,39 @@ int rs_ring_selector_dev(rs_ctx* c, int32_t* sel, const int32_t* ct, int32_t dep
   size_t N = 0;
   if ((rc = ring_selector_shape(c, depth, basebit, l, n_src, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
   if (depth == 0) return RS_OK;
-  const size_t rows = (size_t)depth * (size_t)l, src_words = (size_t)n_src + 1;
-  if ((rc = refuse_overlap({"sel", sel, rows * 4 * N * kWord}, {{"ct", ct, rows * src_words * kWord},
-                                                                {"sel_key", sel_key, 2 * src_words * (size_t)ks_t * 2 * N * kWord}})) != RS_OK)
-    return rc;
-  const rs::RingSelectorArgs a{sel, ct, sel_key, (long)depth * l, (int)N, (int)n_src, (int)basebit, (int)l, (int)ks_basebit, (int)ks_t};
-  RS_HIP(rs::launch_ring_selector(a, (hipStream_t)stream));
-  return RS_OK;
+  return ring_selector_run(c, sel, ct, (size_t)depth * (size_t)l, N, false, rs::SePlan{}, basebit, l, n_src, sel_key, ks_basebit, ks_t, stream);
+}
+
+// The batch form: `count` bits instead of depth <= 30, the same arithmetic, checks and refusals with the extents computed from
+// count, and the kernel rs::selector_form plans for count l rows (rs_ring_selector.h; RS_SEL_FORM forces one).
+int rs_ring_selector_batch_dev(rs_ctx* c, int32_t* sel, const int32_t* ct, size_t count, int32_t basebit, int32_t l, int32_t n_src,
+                               const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!sel || !ct || !sel_key) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  rs::SePlan plan{};
+  if ((rc = ring_selector_batch_shape(c, count, basebit, l, n_src, sel_key, ks_basebit, ks_t, &N, &plan)) != RS_OK) return rc;
+  if (count == 0) return RS_OK;
+  return ring_selector_run(c, sel, ct, count * (size_t)l, N, true, plan, basebit, l, n_src, sel_key, ks_basebit, ks_t, stream);
 }
 
 // LWE bit -> l bootstraps at the gadget's levels -> selector keyswitch. The steps are the public calls: the gather that replicates
-// each bit l times, ONE programmable bootstrap over the depth l rows whose test polynomial of level j is the constant h_j / 2, and
-// rs_ring_selector_dev from the context's n. scratch (rs_ring_selector.h se_scratch_*): test polynomials, row index, replicated
-// bits, bootstraps.
-int rs_circuit_bootstrap_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
-                             const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream) {
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!c->keys) return fail(RS_ERR_STATE, "rs_load_keys has not been called");
-  if (!sel || !bits || !sel_key || !scratch) return fail(RS_ERR_INVALID, "null pointer");
-  size_t N = 0;
+// each bit l times, ONE programmable bootstrap over the count l rows whose test polynomial of level j is the constant h_j / 2, and
+// rs_ring_selector_dev (batch: rs_ring_selector_batch_dev) from the context's n. scratch (rs_ring_selector.h se_scratch_*): test
+// polynomials, row index, replicated bits, bootstraps.
+static int circuit_bootstrap_run(rs_ctx* c, int32_t* sel, const int32_t* bits, size_t count, size_t N, bool batch, int32_t basebit, int32_t l,
+                                 const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream) {
+  int rc = RS_OK;
   const int n = c->p.n;
-  if ((rc = ring_selector_shape(c, depth, basebit, l, n, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
-  if (depth == 0) return RS_OK;
-  const long rows = (long)depth * l;
+  const long rows = (long)(count * (size_t)l);
   const size_t src_words = (size_t)n + 1;
-  const rs::Extent x_bits{"bits", bits, (size_t)depth * src_words * kWord};
+  const rs::Extent x_bits{"bits", bits, count * src_words * kWord};
   const rs::Extent x_key{"sel_key", sel_key, 2 * src_words * (size_t)ks_t * 2 * N * kWord};
   const rs::Extent x_scratch{"scratch", scratch, rs::se_scratch_words((int)N, (int)l, rows, n) * kWord};
   if ((rc = refuse_overlap({"sel", sel, (size_t)rows * 4 * N * kWord}, {x_bits, x_key, x_scratch})) != RS_OK) return rc;
   if ((rc = refuse_overlap(x_scratch, {x_bits, x_key})) != RS_OK) return rc;
+  if (batch && ((uintptr_t)sel & 15u)) return fail(RS_ERR_INVALID, "sel must be 16-byte aligned");
   int32_t* lut = scratch;
   int32_t* index = scratch + rs::se_scratch_index((int)N, (int)l, rows);
   int32_t* rep = scratch + rs::se_scratch_bits((int)N, (int)l, rows);
@@ -543,7 +586,41 @@ int rs_circuit_bootstrap_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, int32
   RS_HIP(rs::launch_circuit_prepare(pa, (hipStream_t)stream));
   if ((rc = rs_gather_rows_dev(c, rep, bits, index, (size_t)rows, stream)) != RS_OK) return rc;
   if ((rc = rs_bootstrap_lut_dev(c, boot, rep, lut, (size_t)l, 0, (size_t)rows, stream)) != RS_OK) return rc;
-  return rs_ring_selector_dev(c, sel, boot, depth, basebit, l, n, sel_key, ks_basebit, ks_t, stream);
+  if (batch) return rs_ring_selector_batch_dev(c, sel, boot, count, basebit, l, n, sel_key, ks_basebit, ks_t, stream);
+  return rs_ring_selector_dev(c, sel, boot, (int32_t)count, basebit, l, n, sel_key, ks_basebit, ks_t, stream);
+}
+
+int rs_circuit_bootstrap_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, int32_t depth, int32_t basebit, int32_t l,
+                             const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!c->keys) return fail(RS_ERR_STATE, "rs_load_keys has not been called");
+  if (!sel || !bits || !sel_key || !scratch) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_selector_shape(c, depth, basebit, l, c->p.n, sel_key, ks_basebit, ks_t, &N)) != RS_OK) return rc;
+  if (depth == 0) return RS_OK;
+  return circuit_bootstrap_run(c, sel, bits, (size_t)depth, N, false, basebit, l, sel_key, ks_basebit, ks_t, scratch, stream);
+}
+
+int rs_circuit_bootstrap_batch_dev(rs_ctx* c, int32_t* sel, const int32_t* bits, size_t count, int32_t basebit, int32_t l,
+                                   const int32_t* sel_key, int32_t ks_basebit, int32_t ks_t, int32_t* scratch, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!c->keys) return fail(RS_ERR_STATE, "rs_load_keys has not been called");
+  if (!sel || !bits || !sel_key || !scratch) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  rs::SePlan plan{};
+  if ((rc = ring_selector_batch_shape(c, count, basebit, l, c->p.n, sel_key, ks_basebit, ks_t, &N, &plan)) != RS_OK) return rc;
+  if (count == 0) return RS_OK;
+  return circuit_bootstrap_run(c, sel, bits, count, N, true, basebit, l, sel_key, ks_basebit, ks_t, scratch, stream);
+}
+
+int rs_last_selector(rs_ctx* c, int32_t* form, int64_t* workgroups) {
+  if (!c) return fail(RS_ERR_INVALID, "null context");
+  if (c->sel_form.load() < 0) return fail(RS_ERR_STATE, "no selector keyswitch launched on this context yet");
+  if (form) *form = c->sel_form.load();
+  if (workgroups) *workgroups = (int64_t)c->sel_groups.load();
+  return RS_OK;
 }
 
 // the packing key on the device (include/redsec_hip.h; kernels of rs_packkey.hip): the checks the three calls share. rows = n t.

@@ -25,6 +25,7 @@
 #include "rs_circuit.h"
 #include "rs_host.h"
 #include "rs_kernels.h"
+#include "rs_ring_selector.h"
 
 #define RS_HIP(call)                                                                                  \
   do {                                                                                                \
@@ -80,6 +81,9 @@ struct rs_ctx {
   double cert_limit = RS_CERTIFICATE_LIMIT;
   rs::LaunchOpts opts;
   int ks_force = rs::kKsAuto;      // RS_KS_FORM=wide|tiled (diagnostic, read once in rs_create): rs_host.h keyswitch_form
+  int sel_force = rs::kSeAuto;     // RS_SEL_FORM=wide|chunked (diagnostic, read once in rs_create): rs_ring_selector.h selector_form
+  std::atomic<int> sel_form{-1};   // form and workgroups of the last selector keyswitch of this context (rs_last_selector)
+  std::atomic<long> sel_groups{0};
   double* d_tw = nullptr;          // exact-NTT tables (kTwTotal doubles)
   double* d_tw_fft = nullptr;      // FFT tables (kFftTwDoubles doubles)
   double* d_bk_ntt = nullptr;      // key in the NTT domain

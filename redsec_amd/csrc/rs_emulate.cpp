@@ -1760,6 +1760,75 @@ void rs_emu_ring_selector(const int32_t* ct_, int depth, int basebit, int l, int
     }
   }
 }
+// ---- the wide form of the selector keyswitch (rs_ring_selector_batch_dev) through the functions of rs_ring_selector.h ----
+int rs_emu_ring_selector_wide_rows() { return rs::kSwRows; }
+int rs_emu_ring_selector_wide_piece() { return rs::kSwPiece; }
+int rs_emu_ring_selector_wide_lds_bytes() { return rs::kSwLdsBytes; }
+long rs_emu_ring_selector_wide_groups(long rows, int N) { return rs::sw_groups(rows, N); }
+// selector_form: form + 2 * workgroups; force = -1 (by row count), 0 (chunked), 1 (wide)
+long rs_emu_selector_form(long rows, int N, int n_src, int num_cus, int force) {
+  const rs::SePlan p = rs::selector_form(rows, N, n_src, num_cus, force);
+  return (long)p.form + 2 * p.groups;
+}
+// ring_selector_wide_kernel workgroup by workgroup and thread by thread as the kernel places them: the grid over (tile, polynomial,
+// family, row block), the pieces of kSwPiece coordinates staged as x_i + off (zero where no row or coordinate is), the key
+// polynomials of all coordinates in storage order, four coefficients a thread, the negated sums stored once. sel is not read: words
+// the kernel does not write keep what the caller put there.
+void rs_emu_ring_selector_wide(const int32_t* ct_, long count, int basebit, int l, int n_src, int N, const int32_t* key_, int ks_basebit,
+                               int ks_t, int32_t* sel_) {
+  const long rows = count * l;
+  if (rows <= 0) return;
+  uint32_t* sel = reinterpret_cast<uint32_t*>(sel_);
+  const uint32_t* ct = reinterpret_cast<const uint32_t*>(ct_);
+  const uint32_t* key = reinterpret_cast<const uint32_t*>(key_);
+  const unsigned tiles = (unsigned)rs::se_tiles(N);
+  const uint32_t off = rs::se_offset(ks_basebit, ks_t), mask = (1u << ks_basebit) - 1u;
+  std::vector<uint32_t> sx((size_t)rs::kSwPiece * rs::kSwRows);
+  std::vector<uint32_t> acc((size_t)rs::kSeThreads * rs::kSwRows * rs::kSeKpt);
+  for (long blk = 0; blk < rs::sw_groups(rows, N); ++blk) {
+    unsigned g = (unsigned)blk;
+    const int tile = (int)(g % tiles); g /= tiles;
+    const int p = (int)(g & 1u); g >>= 1;
+    const int f = (int)(g & 1u); g >>= 1;
+    const long r0 = (long)g * rs::kSwRows;
+    const int rn = rows - r0 < (long)rs::kSwRows ? (int)(rows - r0) : rs::kSwRows;
+    std::fill(acc.begin(), acc.end(), 0u);
+    for (int i0 = 0; i0 <= n_src; i0 += rs::kSwPiece) {
+      const int cn = n_src + 1 - i0 < rs::kSwPiece ? n_src + 1 - i0 : rs::kSwPiece;
+      for (int s = 0; s < rs::kSwPiece * rs::kSwRows; ++s) {
+        const int r = s / rs::kSwPiece, ii = s - r * rs::kSwPiece;
+        uint32_t x = 0u;
+        if (ii < cn && r < rn) {
+          const int i = i0 + ii;
+          x = ct[(size_t)(r0 + r) * ((size_t)n_src + 1) + (size_t)i] + off;
+          if (i == n_src) x += rs::se_half_step(basebit, (int)((r0 + r) % l));
+        }
+        sx[(size_t)ii * rs::kSwRows + r] = x;
+      }
+      for (int t = 0; t < rs::kSeThreads; ++t) {
+        const int k0 = tile * rs::kSeTile + rs::kSeKpt * t;
+        uint32_t* a = acc.data() + (size_t)t * rs::kSwRows * rs::kSeKpt;
+        for (int ii = 0; ii < cn; ++ii)
+          for (int q = 0; q < ks_t; ++q) {
+            const uint32_t* kw = key + rs::se_key_offset(N, n_src, ks_t, f, i0 + ii, q, p) + k0;
+            const int shift = 32 - (q + 1) * ks_basebit;
+            for (int r = 0; r < rs::kSwRows; ++r) {
+              const uint32_t d = (sx[(size_t)ii * rs::kSwRows + r] >> shift) & mask;
+              for (int c = 0; c < rs::kSeKpt; ++c) a[r * rs::kSeKpt + c] += kw[c] * d;
+            }
+          }
+      }
+    }
+    for (int t = 0; t < rs::kSeThreads; ++t) {
+      const int k0 = tile * rs::kSeTile + rs::kSeKpt * t;
+      const uint32_t* a = acc.data() + (size_t)t * rs::kSwRows * rs::kSeKpt;
+      for (int r = 0; r < rn; ++r) {
+        uint32_t* o = sel + rs::se_out_offset(N, l, (int)(r0 + r), f, p) + k0;
+        for (int c = 0; c < rs::kSeKpt; ++c) o[c] = 0u - a[r * rs::kSeKpt + c];
+      }
+    }
+  }
+}
 // ---- device decryption and the key audit (rs_phase_dev, rs_audit_keys_dev, rs_audit_compressed_keys_dev) through the functions of
 // rs_audit.h, as the kernels of rs_audit.hip place them: a wave of 64 lanes per LWE sample, a workgroup of kAuThreads per bk row ----
 static std::vector<uint32_t> emu_pack_bits(const int32_t* key, int count) {

@@ -237,6 +237,9 @@ struct RingSelectorArgs {
   int N, n_src, basebit, l, ks_basebit, ks_t;
 };
 hipError_t launch_ring_selector(const RingSelectorArgs& a, hipStream_t st);
+// the same words from ring_selector_wide_kernel (rs_ring_selector_wide.hip): all coordinates in one workgroup, plain 16-byte stores;
+// sel 16-byte aligned. Which of the two a batch call takes: selector_form (rs_ring_selector.h)
+hipError_t launch_ring_selector_wide(const RingSelectorArgs& a, hipStream_t st);
 // rs_circuit_bootstrap_dev: lut[j] = the constant polynomial h_j / 2, index[r] = r / l (the gather that replicates each bit l times)
 struct CircuitPrepareArgs {
   int32_t* lut;                                       // [l][N]

@@ -57,6 +57,42 @@ RS_HD size_t se_out_offset(int N, int l, int r, int f, int p) {
   return ((((size_t)k * 2 + (size_t)f) * (size_t)l + (size_t)j) * 2 + (size_t)p) * (size_t)N;
 }
 
+// Placement of ring_selector_wide_kernel (rs_ring_selector_wide.hip; rs_ring_selector_batch_dev, rs_circuit_bootstrap_batch_dev): the
+// same kSeThreads threads on the same kSeTile coefficients of one polynomial of one family, but ALL n_src + 1 coordinates and one
+// block of kSwRows consecutive sample rows: 4 x kSwRows accumulators per thread over the whole key stream, stored once. The words
+// x_i + off of the block are staged in LDS kSwPiece coordinates at a time. The grid runs over (tile, polynomial, family, row block),
+// the first three fastest: at N = 1024 they are the 8 residues of the workgroup index, so the workgroups that share key words follow
+// each other at a distance of 8.
+constexpr int kSwRows = 16;             // sample rows of a register block (the arithmetic: header of rs_ring_selector_wide.hip)
+constexpr int kSwPiece = 64;            // coordinates staged at a time: kSwPiece x kSwRows words = 4 KB of LDS
+constexpr int kSwPre = 4;               // key words (16 bytes each) a thread keeps in flight, across the pieces
+constexpr int kSwLdsBytes = kSwPiece * kSwRows * 4;
+static_assert(kSwPiece % kSwPre == 0, "a full piece holds whole rounds of the key ring, so every piece starts at ring slot 0");
+static_assert((kSwPiece * kSwRows) % kSeThreads == 0 && kSwRows % 4 == 0, "staging and the 16-byte reads of the staged words");
+
+RS_HD long sw_row_blocks(long rows) { return (rows + kSwRows - 1) / kSwRows; }
+RS_HD long sw_groups_per_block(int N) { return 4L * se_tiles(N); }
+RS_HD long sw_groups(long rows, int N) { return sw_row_blocks(rows) * sw_groups_per_block(N); }
+RS_HD int sw_pieces(int n_src) { return (n_src + 1 + kSwPiece - 1) / kSwPiece; }
+
+// ---- which kernel a batch selector keyswitch runs (rs_ring_selector_batch_dev only dispatches on this; CPU-tested through the
+// emulator library) ----
+//   kSeChunked  ring_selector_kernel: chunks of kSeChunk coordinates that meet by atomic adds, ceil((n_src+1)/8) adds per output word
+//   kSeWide     ring_selector_wide_kernel: every output word stored once
+// Wide as soon as its own grid gives every CU of the context a workgroup: below that the chunks are what keeps the device busy, from
+// there on the rows do and the atomic adds (n_src + 1) / 8 times the size of the result are pure cost. Derived; the sweep that
+// confirms it is in INTEGRATION.md section 27. `force` is the diagnostic switch RS_SEL_FORM read once in rs_create.
+enum SeForm { kSeAuto = -1, kSeChunked = 0, kSeWide = 1 };
+struct SePlan { int form; long groups; };
+RS_HD SePlan selector_form(long rows, int N, int n_src, int num_cus, int force) {
+  SePlan p = {kSeChunked, 0};
+  if (rows <= 0) return p;
+  const long wide = sw_groups(rows, N);
+  if (force == kSeWide || (force == kSeAuto && wide >= (long)num_cus)) { p.form = kSeWide; p.groups = wide; }
+  else p.groups = se_groups(rows, N, n_src);
+  return p;
+}
+
 // rs_circuit_bootstrap_dev's scratch, in words: the l test polynomials [l][N], the row index [rows] of the gather, the replicated
 // bits [rows][n+1] and their bootstraps [rows][n+1], rows = depth l
 RS_HD size_t se_scratch_index(int N, int l, long) { return (size_t)l * (size_t)N; }
