@@ -400,6 +400,38 @@ int rs_ring_rotate_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* in, size_t 
  * allocation, no loaded key; R = 0 is a no-op. */
 int rs_ring_heads_dev(rs_ctx* ctx, int32_t* u, const int32_t* rlwe, size_t R, size_t width, void* stream);
 
+/* Batched encrypted lookup: out DEVICE int32[R][2][N], out[q] = table_q[index_q], R of the trees of
+ * rs_ring_lookup_dev side by side with ONE init and ONE sweep launch per level for all rows. Entry e < entries of row q's table is
+ * the ciphertext at table + (q row_stride + e entry_stride) 2N words:
+ *   row_stride = 0                              every row reads one shared table
+ *   row_stride = entries, entry_stride = 1      R tables stored one after another
+ *   row_stride = 1, entry_stride = R            the layout [entries][R][2][N] of entries that are R ciphertexts wide
+ * and any row_stride >= 0, entry_stride >= 1 is accepted; the tables are only read and may overlap each other. sel DEVICE
+ * int32[depth][2l][2][N] with per_row = 0 (one hidden index for all rows), int32[R][depth][2l][2][N] with per_row = 1: the layouts
+ * rs_ring_rotate_dev takes and rs_circuit_bootstrap_batch_dev writes. The arithmetic is that of rs_ring_lookup_dev
+ * (rs_ring_lookup_rows_alt_dev: of rs_ring_lookup_alt_dev) row by row: level k pairs rows (2i, 2i + 1) of row q's previous level
+ * under sample k of row q's set, an unpaired last row meets the all-zero ciphertext (inside the same launch), entries at or past
+ * `entries` count as zero, and every word of out[q] equals what the single call gives for row q's table and selectors. Integer
+ * arithmetic mod 2^32, exact in any order; the noise is that of rs_ring_lookup_dev.
+ * scratch DEVICE int32[R (ceil(E/2) + ceil(E/4))][2][N], E = entries: two ping-pong halves of R ceil(E/2) and R ceil(E/4)
+ * ciphertexts. Level k writes [R][P_k][2][N] contiguously from the start of half k & 1, P_k the rows its trees leave; the next
+ * level reads that with row stride P_k and entry stride 1; the last level writes out. NULL is accepted at depth 1. Every level
+ * sets its target before it adds into it, so a second call into the same buffers gives the same words. 1 <= depth <= 30.
+ * Asynchronous and ordered on `stream`; no allocation; needs no loaded key. R = 0 is a no-op that returns RS_OK.
+ * RS_ERR_INVALID, before anything is launched: a null out, table or sel; the digit-shape and ring refusals of rs_ring_cmux_dev;
+ * depth outside 1 .. 30; entries outside 1 .. 2^depth; entry_stride = 0; a null scratch with depth > 1; row arithmetic that
+ * overflows (the read extent of (R - 1) row_stride + (entries - 1) entry_stride + 1 ciphertexts, the selector sets, the scratch);
+ * a level whose workgroups pass one launch; an out that overlaps the table extent, sel or scratch ("out overlaps table"); a
+ * scratch that overlaps table or sel. Without a device or context it fails as rs_ring_cmux_dev does. */
+int rs_ring_lookup_rows_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
+                            size_t row_stride, size_t entry_stride, size_t R,
+                            const int32_t* sel, int32_t depth, int32_t per_row,
+                            int32_t basebit, int32_t l, int32_t* scratch, void* stream);
+int rs_ring_lookup_rows_alt_dev(rs_ctx* ctx, int32_t* out, const int32_t* table, size_t entries,
+                                size_t row_stride, size_t entry_stride, size_t R,
+                                const int32_t* sel, int32_t depth, int32_t per_row,
+                                int32_t basebit, int32_t l, int32_t* scratch, void* stream);
+
 /* Circuit bootstrapping (CGGI17 section 4): the selectors of rs_ring_cmux_dev / rs_ring_lookup_dev made
  * on the server from LWE bits it computed itself. rs_ring_selector_dev is the step in the middle, a keyswitch from LWE samples to
  * ring samples under two key families, one of them private (the message multiplied by -S(X)). Word-wise mod 2^32 with the

@@ -13,9 +13,9 @@ the index -1, the constant FALSE. Nothing here computes on ciphertext words: tor
 select, maximum, equal and multiply go through compiled circuits instead (redsec_amd/circuit.py): the
 generator's netlist is compiled once per (function, bit count) and bound once per backend, and a call is one Backend.circuit_run.
 
-lookup and evaluate leave the gates for the ring pipeline (INTEGRATION.md sections 24 and 26): the encrypted bits become selectors
-by circuit bootstrapping, lookup returns a whole table row under the ring key, and evaluate returns f(index) as LWE samples the
-gates accept again.
+lookup, lookup_rows and evaluate leave the gates for the ring pipeline (INTEGRATION.md sections 24, 26 and 28): the encrypted bits
+become selectors by circuit bootstrapping, lookup returns a whole table row under the ring key (lookup_rows: one row per index, R
+indices in one call), and evaluate returns f(index) as LWE samples the gates accept again.
 """
 import torch
 
@@ -118,6 +118,28 @@ def lookup(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks
     return be.ring_lookup(table, sel, basebit, l, digits=digits)
 
 
+def lookup_rows(be, index_bits, table, key, basebit=None, l=None, ks_basebit=None, ks_t=None, digits="signed"):
+    """table[index_r] for R indices the server holds as encrypted bits -> int32 CUDA tensor [R][2][N],
+    ring ciphertexts under the ring key of the secret that made `key`. index_bits: [depth][R][W], LSB first, +-1/8 under the loaded
+    key; table, key, basebit, l, ks_basebit, ks_t and digits as in lookup; the table is shared by all rows. ONE
+    Backend.circuit_bootstrap_batch over the R depth bits (selectors [R][depth][2l][2][N]: bit k of index r is sample r depth + k),
+    then ONE Backend.ring_lookup_rows: no round trip to the client and no loop over the indices."""
+    from . import keygen
+    keygen._check_cmux_form(digits)
+    assert index_bits.dim() == 3, "index_bits must be [depth][R][W]"
+    depth, R, W = index_bits.shape
+    if basebit is None or l is None:
+        d = keygen.circuit_bootstrap_default(keygen.set_name(be.p), depth, digits=digits)
+        basebit, l = d[0] if basebit is None else basebit, d[1] if l is None else l
+    if hasattr(key, "body"):
+        ks_basebit, ks_t, key = key.ks_basebit, key.ks_t, be.upload_selector_key(key)
+    N = be.p.N
+    flat = index_bits.permute(1, 0, 2).contiguous().reshape(R * depth, W)
+    sel = be.empty(R, depth, 2 * l, 2, N)
+    be.circuit_bootstrap_batch(flat, basebit, l, key, ks_basebit, ks_t, out=sel.view(R * depth, 2 * l, 2, N))
+    return be.ring_lookup_rows(table, sel, basebit=basebit, l=l, digits=digits)
+
+
 CIRCUIT_BOOTSTRAP_BITS = 30   # bits of one Backend.circuit_bootstrap call (rs_circuit_bootstrap_dev: depth <= 30); evaluate itself takes
                               # Backend.circuit_bootstrap_batch, tools/ring_rotate_time.py restates the route of calls of 30 with this
 
@@ -133,8 +155,9 @@ def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_base
     Where 2^depth width <= N the table is one trivial row: ONE Backend.circuit_bootstrap_batch over all R depth bits (INTEGRATION.md
     section 27), the row broadcast with stride 0, one Backend.ring_rotate with per-row selectors and step = -width,
     Backend.ring_heads, then Backend.keyswitch: l bootstraps per input bit and none per table entry. A longer table is laid out as
-    rows of floor-power-of-two(N / width) entries: the high bits choose the row through Backend.ring_lookup, one call per index
-    (batching the lookup is out of scope here), and the low bits rotate the chosen rows as above."""
+    rows of floor-power-of-two(N / width) entries: the high bits choose the row through ONE Backend.ring_lookup_rows over the shared
+    table with per-row selectors (one pair of launches per level for all R indices; R = 1 keeps
+    Backend.ring_lookup, which gives the same words), and the low bits rotate the chosen rows as above."""
     from . import keygen
     keygen._check_cmux_form(digits)
     N, W = be.p.N, index_bits.shape[-1]
@@ -165,8 +188,10 @@ def evaluate(be, index_bits, values, key, width=1, basebit=None, l=None, ks_base
         chosen, stride = table, 0
     else:
         chosen, stride = be.empty(R, 2, N), 1
-        for r in range(R):
-            be.ring_lookup(table, sel[r, low:], basebit, l, out=chosen[r], digits=digits)
+        if R == 1:
+            be.ring_lookup(table, sel[0, low:], basebit, l, out=chosen[0], digits=digits)
+        else:
+            be.ring_lookup_rows(table, sel[:, low:].contiguous(), basebit=basebit, l=l, out=chosen, digits=digits)
     if low:
         turned = be.ring_rotate(chosen, sel if low == depth else sel[:, :low].contiguous(), -width, basebit, l, stride=stride,
                                 per_row=True, digits=digits)

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "rs_ring_cmux_dev", "rs_ring_lookup_dev", "rs_ring_cmux_alt_dev", "rs_ring_lookup_alt_dev",
     "rs_ring_selector_dev", "rs_circuit_bootstrap_dev",
     "rs_ring_rotate_dev", "rs_ring_rotate_alt_dev", "rs_ring_heads_dev",
+    "rs_ring_lookup_rows_dev", "rs_ring_lookup_rows_alt_dev",
     "rs_ring_selector_batch_dev", "rs_circuit_bootstrap_batch_dev", "rs_last_selector",
 ]
 
@@ -147,6 +148,8 @@ def load_library(path=None):
     L.rs_ring_rotate_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.rs_ring_rotate_alt_dev.argtypes = L.rs_ring_rotate_dev.argtypes
     L.rs_ring_heads_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    L.rs_ring_lookup_rows_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    L.rs_ring_lookup_rows_alt_dev.argtypes = L.rs_ring_lookup_rows_dev.argtypes
     L.rs_ring_selector_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
     L.rs_circuit_bootstrap_dev.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
     L.rs_ring_selector_batch_dev.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
@@ -670,6 +673,63 @@ class Backend:
         scratch = self.empty(first + (first + 1) // 2, 2, N) if depth > 1 else None
         _check(self.L, call(self.h, self._ck_dev(out), self._ck_dev(table), entries, self._ck_dev(sel), depth,
                             basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
+        return out
+
+    def ring_lookup_rows(self, table, sel, entries=None, R=None, row_stride=0, entry_stride=1, per_row=None, basebit=None, l=None,
+                         out=None, digits="signed"):
+        """out[q] = table_q[index_q] for R hidden indices in one call (rs_ring_lookup_rows_dev, on torch's current stream;
+        INTEGRATION.md section 28) -> int32 CUDA tensor [R][2][N] (or into `out`; an `out` that overlaps an input is refused with
+        ValueError). table: int32 CUDA tensor of ciphertexts [..][2][N]; entry e of row q is ciphertext q row_stride + e entry_stride
+        of it: (0, 1) one shared table (entries defaults to the table's rows), (entries, 1) R tables one after another, (1, R) the
+        layout [entries][R][2][N]. sel: a client.RingSelector (one hidden index for all rows; uploaded on this context's device) or
+        an int32 CUDA tensor with explicit basebit and l: [depth][2l][2][N], or [R][depth][2l][2][N] with one index per row; per_row
+        is inferred from a 5-D tensor where it is None. R defaults to the number of selector sets. A selector of another ring or
+        digit shape raises ValueError. The scratch of the call, R (ceil(E/2) + ceil(E/4)) ciphertexts, is allocated here. digits:
+        as ring_cmux ("alternating": rs_ring_lookup_rows_alt_dev). Needs no loaded key."""
+        from . import keygen
+        N = self.p.N
+        call = self.L.rs_ring_lookup_rows_alt_dev if keygen._check_cmux_form(digits) == "alternating" else self.L.rs_ring_lookup_rows_dev
+        if hasattr(sel, "body"):
+            basebit, l, sel = sel.basebit, sel.l, self.upload_ring_selector(sel)
+        if basebit is None or l is None:
+            raise ValueError("a selector given as a tensor needs explicit basebit and l")
+        basebit, l = keygen._check_cmux_digits(basebit, l)
+        per_row = sel.dim() == 5 if per_row is None else bool(per_row)
+        if sel.dim() != (5 if per_row else 4) or tuple(sel.shape[-3:]) != (2 * l, 2, N):
+            raise ValueError("sel must hold [depth][2l][2][N] words of the context's ring N = %d, or [R][depth][2l][2][N] with one "
+                             "index per row; got %s" % (N, tuple(sel.shape)))
+        depth = sel.shape[-4]
+        if not 1 <= depth <= keygen.RING_LOOKUP_MAX_DEPTH:
+            raise ValueError("depth = %d is outside 1 .. %d" % (depth, keygen.RING_LOOKUP_MAX_DEPTH))
+        row_stride, entry_stride = int(row_stride), int(entry_stride)
+        if row_stride < 0 or entry_stride < 1:
+            raise ValueError("row_stride = %d, entry_stride = %d: row_stride must be at least 0 and entry_stride at least 1" % (row_stride, entry_stride))
+        assert table.numel() and table.numel() % (2 * N) == 0, "table must hold ciphertexts of [2][N] words"
+        held = table.numel() // (2 * N)
+        if entries is None:
+            if (row_stride, entry_stride) != (0, 1):
+                raise ValueError("entries must be given with row_stride = %d, entry_stride = %d" % (row_stride, entry_stride))
+            entries = held
+        entries = int(entries)
+        if not 1 <= entries <= 1 << depth:
+            raise ValueError("entries = %d is outside 1 .. 2^%d" % (entries, depth))
+        if R is None:
+            R = sel.shape[0] if per_row else 1
+        R = int(R)
+        if R < 0 or (per_row and sel.shape[0] != R):
+            raise ValueError("R = %d with %d selector sets" % (R, sel.shape[0] if per_row else 1))
+        out = self.empty(R, 2, N) if out is None else out
+        assert out.numel() == R * 2 * N, "out must hold [R][2][N] words"
+        if R == 0:
+            return out
+        read = (R - 1) * row_stride + (entries - 1) * entry_stride + 1
+        if read > held:
+            raise ValueError("the table holds %d ciphertexts, the strides read %d" % (held, read))
+        _refuse_overlap("out", out, out.numel(), (("table", table, read * 2 * N), ("sel", sel, sel.numel())))
+        first = (entries + 1) // 2
+        scratch = self.empty(R * (first + (first + 1) // 2), 2, N) if depth > 1 else None
+        _check(self.L, call(self.h, self._ck_dev(out), self._ck_dev(table), entries, row_stride, entry_stride, R, self._ck_dev(sel), depth,
+                            int(per_row), basebit, l, None if scratch is None else self._ck_dev(scratch), self._stream()))
         return out
 
     # ---- encrypted rotation (INTEGRATION.md section 26) ----

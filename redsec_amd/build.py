@@ -58,6 +58,9 @@ HIP_OBJECTS = [
     # encrypted rotation (ring_rotate_init_kernel, ring_rotate_kernel, ring_rotate_alt_kernel, ring_heads_kernel), likewise in an
     # object of its own: the CMUX kernels keep their instructions; integer-only sources, as rs_pack
     ("rs_ring_rotate", "rs_ring_rotate.hip", []),
+    # batched encrypted lookup (ring_lookup_init_kernel, ring_lookup_level_kernel, ring_lookup_level_alt_kernel), likewise in an
+    # object of its own: the CMUX and rotation kernels keep their instructions; integer-only sources, as rs_pack
+    ("rs_ring_lookup", "rs_ring_lookup.hip", []),
     # the selector keyswitch of circuit bootstrapping (ring_selector_init_kernel, ring_selector_kernel, circuit_prepare_kernel),
     # likewise in an object of its own; integer-only sources, as rs_pack
     ("rs_ring_selector", "rs_ring_selector.hip", []),
@@ -81,9 +84,9 @@ HIP_OBJECTS = [
     ("rs_api_client", "rs_api_client.cpp", []),
 ]
 HIP_SOURCES = [src for _, src, _ in HIP_OBJECTS]
-HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_rotate.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
+HIP_DEPS = HIP_SOURCES + ["rs_bootstrap.h", "rs_kernels.h", "rs_cohort.h", "rs_diag.h", "rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_rotate.h", "rs_ring_lookup.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h", "rs_api_internal.h", os.path.join(INCLUDE, "redsec_hip.h")]
 EMU_SOURCES = ["rs_emulate.cpp"]
-EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_rotate.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
+EMU_DEPS = EMU_SOURCES + ["rs_launch_plan.h", "rs_lds_plan.h", "rs_ntt.h", "rs_fft.h", "rs_general.h", "rs_keygen.h", "rs_rlwe.h", "rs_ring_sweep.h", "rs_pack.h", "rs_rekey.h", "rs_ring_rekey.h", "rs_ring_cmux.h", "rs_ring_rotate.h", "rs_ring_lookup.h", "rs_ring_selector.h", "rs_packkey.h", "rs_audit.h", "rs_rows.h", "rs_circuit.h", "rs_sparse.h", "rs_host.h"]
 
 
 def _abs(paths):

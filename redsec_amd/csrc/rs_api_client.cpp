@@ -15,6 +15,7 @@
 #include "rs_packkey.h"
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
+#include "rs_ring_lookup.h"
 #include "rs_ring_rekey.h"
 #include "rs_ring_rotate.h"
 #include "rs_ring_selector.h"
@@ -412,6 +413,75 @@ int rs_ring_lookup_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t ent
 int rs_ring_lookup_alt_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, const int32_t* sel, int32_t depth,
                            int32_t basebit, int32_t l, int32_t* scratch, void* stream) {
   return ring_lookup_any(c, out, table, entries, sel, depth, basebit, l, scratch, rs::kRcAlternating, stream);
+}
+
+// R of those trees side by side (include/redsec_hip.h; kernels of rs_ring_lookup.hip): one init and one sweep launch per level for
+// all rows, the unpaired last row of every table inside the same launch. Level 0 reads the tables at the caller's strides; level k
+// writes [R][P_k] ciphertexts into half k & 1 of scratch, which the next level reads with row stride P_k and entry stride 1; the
+// last level writes out. Either digit form: every level carries `form`.
+static int ring_lookup_rows_any(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, size_t row_stride, size_t entry_stride,
+                                size_t R, const int32_t* sel, int32_t depth, int32_t per_row, int32_t basebit, int32_t l,
+                                int32_t* scratch, int form, void* stream) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!out || !table || !sel) return fail(RS_ERR_INVALID, "null pointer");
+  size_t N = 0;
+  if ((rc = ring_cmux_shape(c, basebit, l, &N)) != RS_OK) return rc;
+  if (depth < 1 || depth > rs::kLkMaxDepth) return fail(RS_ERR_INVALID, "depth = %d is outside 1 .. %d", (int)depth, rs::kLkMaxDepth);
+  if (entries < 1 || entries > ((size_t)1 << depth))
+    return fail(RS_ERR_INVALID, "entries = %zu is outside 1 .. 2^%d", entries, (int)depth);
+  if (entry_stride == 0) return fail(RS_ERR_INVALID, "entry_stride = 0");
+  if (depth > 1 && !scratch) return fail(RS_ERR_INVALID, "null scratch with depth = %d", (int)depth);
+  // the extents in bytes, each below LONG_MAX; `over` collects an overflow of the row arithmetic itself
+  const size_t ct = 2 * N, ct_bytes = ct * kWord, set_words = (size_t)depth * rs::lk_sel_words((int)N, (int)l);
+  bool over = false;
+  auto mul = [&over](size_t a, size_t b) { size_t r; over |= __builtin_mul_overflow(a, b, &r); return r; };
+  auto add = [&over](size_t a, size_t b) { size_t r; over |= __builtin_add_overflow(a, b, &r); return r; };
+  const size_t read_bytes = mul(add(add(mul(R ? R - 1 : 0, row_stride), mul(entries - 1, entry_stride)), 1), ct_bytes);
+  if (over || read_bytes > (size_t)LONG_MAX)
+    return fail(RS_ERR_INVALID, "R = %zu at row_stride %zu with %zu entries at entry_stride %zu is too large for ciphertexts of %zu bytes",
+                R, row_stride, entries, entry_stride, ct_bytes);
+  const size_t sel_bytes = mul(per_row ? R : 1, set_words * kWord);
+  if (over || sel_bytes > (size_t)LONG_MAX)
+    return fail(RS_ERR_INVALID, "R = %zu is too large for selector sets of %zu bytes", R, set_words * kWord);
+  const size_t scratch_rows = (size_t)rs::rc_scratch_rows((long)entries), scratch_bytes = mul(mul(R, scratch_rows), ct_bytes);
+  if (over || scratch_bytes > (size_t)LONG_MAX)
+    return fail(RS_ERR_INVALID, "R = %zu is too large for a scratch of %zu ciphertexts of %zu bytes per row", R, scratch_rows, ct_bytes);
+  // level 0, the largest launch: R ceil(entries / 2) output ciphertexts
+  const size_t P0 = (size_t)rs::lk_level_rows((long)entries);
+  const size_t per_out = std::max((size_t)rs::rc_groups_per_ct((int)N, (int)l), 2 * N / rs::kLkInitThreads);
+  if (mul(mul(R, P0), per_out) > (size_t)INT32_MAX || over)
+    return fail(RS_ERR_INVALID, "R = %zu with %zu pairs per row is too large for one launch", R, P0);
+  if (R == 0) return RS_OK;
+  const rs::Extent x_table{"table", table, read_bytes}, x_sel{"sel", sel, sel_bytes};
+  const rs::Extent x_scratch{"scratch", depth > 1 ? scratch : nullptr, scratch_bytes};
+  if ((rc = refuse_written({{"out", out, R * ct_bytes}, x_scratch, x_table, x_sel}, 2)) != RS_OK) return rc;
+  int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::lk_scratch_half((long)R, (long)entries, 1) * ct : nullptr};
+  const int32_t* in = table;
+  size_t rows = entries;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = k == depth - 1 ? out : half[k & 1];
+    const rs::RingLookupArgs a{o, in, sel, (long)R, (long)rows, row_stride, entry_stride, per_row ? set_words : 0, k,
+                               (int)N, (int)basebit, (int)l, form};
+    RS_HIP(rs::launch_ring_lookup_level(a, (hipStream_t)stream));
+    in = o;
+    rows = (size_t)rs::lk_level_rows((long)rows);
+    row_stride = rows;                                           // the level wrote [R][rows] ciphertexts
+    entry_stride = 1;
+  }
+  return RS_OK;
+}
+int rs_ring_lookup_rows_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, size_t row_stride, size_t entry_stride,
+                            size_t R, const int32_t* sel, int32_t depth, int32_t per_row, int32_t basebit, int32_t l,
+                            int32_t* scratch, void* stream) {
+  return ring_lookup_rows_any(c, out, table, entries, row_stride, entry_stride, R, sel, depth, per_row, basebit, l, scratch,
+                              rs::kRcSigned, stream);
+}
+int rs_ring_lookup_rows_alt_dev(rs_ctx* c, int32_t* out, const int32_t* table, size_t entries, size_t row_stride, size_t entry_stride,
+                                size_t R, const int32_t* sel, int32_t depth, int32_t per_row, int32_t basebit, int32_t l,
+                                int32_t* scratch, void* stream) {
+  return ring_lookup_rows_any(c, out, table, entries, row_stride, entry_stride, R, sel, depth, per_row, basebit, l, scratch,
+                              rs::kRcAlternating, stream);
 }
 
 // encrypted rotation (include/redsec_hip.h; kernels of rs_ring_rotate.hip): a chain of `depth` CMUXes between acc and X^(e_k) acc,

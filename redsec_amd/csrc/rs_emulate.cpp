@@ -19,6 +19,7 @@
 #include "rs_packkey.h"
 #include "rs_rekey.h"
 #include "rs_ring_cmux.h"
+#include "rs_ring_lookup.h"
 #include "rs_ring_rotate.h"
 #include "rs_ring_rekey.h"
 #include "rs_ring_selector.h"
@@ -1613,6 +1614,90 @@ void rs_emu_ring_lookup(const int32_t* table, long entries, int N, const int32_t
 void rs_emu_ring_lookup_alt(const int32_t* table, long entries, int N, const int32_t* sel, int depth, int basebit, int l,
                             int32_t* scratch, int32_t* out) {
   emu_ring_lookup(table, entries, N, sel, depth, basebit, l, rs::kRcAlternating, scratch, out);
+}
+// ---- batched encrypted lookup (rs_ring_lookup_rows_dev) through the functions of rs_ring_lookup.h ----
+long rs_emu_ring_lookup_level_rows(long rows) { return rs::lk_level_rows(rows); }
+long rs_emu_ring_lookup_rows_groups(long R, long rows, int N, int l) { return rs::lk_groups(R, rs::lk_level_rows(rows), N, l); }
+long rs_emu_ring_lookup_rows_scratch_rows(long R, long entries) { return rs::lk_scratch_rows(R, entries); }
+// (q, i) of output ciphertext g of a level that leaves P ciphertexts per row
+void rs_emu_ring_lookup_rows_place(long g, long P, long* q, long* i) {
+  const rs::LkPlace at = rs::lk_place(g, P);
+  *q = at.q;
+  *i = at.i;
+}
+// one level as launch_ring_lookup_level runs it: ring_lookup_init_kernel, then ring_lookup_level_kernel or
+// ring_lookup_level_alt_kernel workgroup by workgroup and thread by thread: ring_place, (q, i) from the output ciphertext, the
+// staged window of sample k of row q's set, the block's words d1 - d0 + offset, or -d0 + offset where the pair has no second row
+// (rc_stage_alt in the alternating form, the parity that of the thread), ring_sweep / ring_sweep_parity, the partial sums added
+// into the output
+static void emu_ring_lookup_level(const int32_t* in_, long R, long rows, size_t row_stride, size_t entry_stride, int N,
+                                  const int32_t* sel_, size_t sel_row_stride, int k, int basebit, int l, int form, int32_t* out_) {
+  if (R <= 0) return;
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_);
+  const uint32_t* in = reinterpret_cast<const uint32_t*>(in_);
+  const uint32_t* sel = reinterpret_cast<const uint32_t*>(sel_);
+  const long P = rs::lk_level_rows(rows);
+  const size_t ct = 2 * (size_t)N;
+  for (long g = 0; g < R * P; ++g) {
+    const rs::LkPlace at = rs::lk_place(g, P);
+    for (size_t w = 0; w < ct; ++w) out[(size_t)g * ct + w] = in[rs::lk_source(at.q, at.i, row_stride, entry_stride) * ct + w];
+  }
+  const uint32_t off = rs::rc_offset(basebit, l);
+  std::vector<uint32_t> win((size_t)rs::kRingWindow), sx((size_t)rs::kRingSlots);
+  for (long blk = 0; blk < rs::lk_groups(R, P, N, l); ++blk) {
+    const rs::RingPlace pl = rs::ring_place((unsigned)blk, N, 2 * l);
+    const rs::LkPlace at = rs::lk_place(pl.r, P);
+    const int jr = pl.row, j = jr < l ? jr : jr - l, spoly = jr < l ? 0 : 1;
+    const int c0 = pl.sb * rs::kRingSlots, k0 = pl.tile * rs::kRingTile;
+    const size_t src_at = (rs::lk_source(at.q, at.i, row_stride, entry_stride) * 2 + (size_t)spoly) * (size_t)N + (size_t)c0;
+    const uint32_t* s0 = in + src_at;
+    const uint32_t* s1 = rs::lk_paired(at.i, rows) ? s0 + entry_stride * 2 * (size_t)N : nullptr;
+    const uint32_t* p = sel + rs::lk_sel_offset(at.q, sel_row_stride, k, N, l) + rs::rc_sel_offset(N, jr, pl.poly);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      rs::sweep_stage_window(win.data(), p, N, rs::ring_window_base(N, k0, c0), rs::kRingWindow, th, rs::kRingThreads);
+    for (int th = 0; th < rs::kRingThreads; ++th)
+      for (int cc = th; cc < rs::kRingSlots; cc += rs::kRingThreads) {
+        const uint32_t x = (s1 ? s1[cc] : 0u) - s0[cc];
+        sx[cc] = form == rs::kRcAlternating ? rs::rc_stage_alt(x, off, th & 1) : x + off;
+      }
+    for (int th = 0; th < rs::kRingThreads; ++th) {
+      uint32_t acc[rs::kSweepKpt] = {0u, 0u, 0u, 0u};
+      if (form == rs::kRcAlternating)
+        rs::ring_sweep_parity(win.data(), sx.data(), rs::kRingSlots, th,
+                              [=](uint32_t xbar, auto slot_odd) { return rs::rc_digit_alt(xbar, basebit, j, decltype(slot_odd)::value); }, acc);
+      else
+        rs::ring_sweep(win.data(), sx.data(), rs::kRingSlots, th, [=](uint32_t xbar) { return rs::rc_digit(xbar, basebit, j); }, acc);
+      uint32_t* o = out + ((size_t)pl.r * 2 + pl.poly) * N + k0 + rs::kSweepKpt * th;
+      for (int q = 0; q < rs::kSweepKpt; ++q) o[q] += acc[q];
+    }
+  }
+}
+// rs_ring_lookup_rows_dev's levels as the host code orders them: level 0 from the tables at the caller's strides, the later ones
+// from the previous target [R][P] at row stride P and entry stride 1, the two halves of scratch in turn, the last level into out
+static void emu_ring_lookup_rows(const int32_t* table, long entries, size_t row_stride, size_t entry_stride, long R, int N,
+                                 const int32_t* sel, int depth, int per_row, int basebit, int l, int form, int32_t* scratch, int32_t* out) {
+  const size_t ct = 2 * (size_t)N, set_words = (size_t)depth * rs::lk_sel_words(N, l);
+  int32_t* half[2] = {scratch, scratch ? scratch + (size_t)rs::lk_scratch_half(R, entries, 1) * ct : nullptr};
+  const int32_t* in = table;
+  long rows = entries;
+  for (int k = 0; k < depth; ++k) {
+    int32_t* o = k == depth - 1 ? out : half[k & 1];
+    emu_ring_lookup_level(in, R, rows, row_stride, entry_stride, N, sel, per_row ? set_words : 0, k, basebit, l, form, o);
+    in = o;
+    rows = rs::lk_level_rows(rows);
+    row_stride = (size_t)rows;
+    entry_stride = 1;
+  }
+}
+void rs_emu_ring_lookup_rows(const int32_t* table, long entries, long row_stride, long entry_stride, long R, int N, const int32_t* sel,
+                             int depth, int per_row, int basebit, int l, int32_t* scratch, int32_t* out) {
+  emu_ring_lookup_rows(table, entries, (size_t)row_stride, (size_t)entry_stride, R, N, sel, depth, per_row, basebit, l, rs::kRcSigned,
+                       scratch, out);
+}
+void rs_emu_ring_lookup_rows_alt(const int32_t* table, long entries, long row_stride, long entry_stride, long R, int N,
+                                 const int32_t* sel, int depth, int per_row, int basebit, int l, int32_t* scratch, int32_t* out) {
+  emu_ring_lookup_rows(table, entries, (size_t)row_stride, (size_t)entry_stride, R, N, sel, depth, per_row, basebit, l,
+                       rs::kRcAlternating, scratch, out);
 }
 // ---- encrypted rotation (rs_ring_rotate_dev, rs_ring_heads_dev) through the functions of rs_ring_rotate.h ----
 int rs_emu_ring_rotate_exponent(int32_t step, int k, int N) { return rs::ro_exponent(step, k, N); }

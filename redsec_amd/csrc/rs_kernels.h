@@ -228,6 +228,19 @@ struct RingHeadsArgs {
   int width, N;
 };
 hipError_t launch_ring_heads(const RingHeadsArgs& x, hipStream_t st);
+// batched encrypted lookup (rs_ring_lookup_rows_dev; index arithmetic of rs_ring_lookup.h): ONE level of R CMUX trees
+struct RingLookupArgs {
+  int32_t* out;                                       // [R][ceil(rows / 2)][2][N], contiguous
+  const int32_t* in;                                  // entry e < rows of row q at in + (q row_stride + e entry_stride) 2 N
+  const int32_t* sel;                                 // sample k [2l][2][N] of row q at sel + q sel_row_stride + k 2l 2 N
+  long R, rows;                                       // tables, and the ciphertexts of each that enter this level (1 .. 2^30)
+  size_t row_stride, entry_stride;                    // in ciphertexts
+  size_t sel_row_stride;                              // words between the sets of consecutive rows; 0: one set for all
+  int k;                                              // the level
+  int N, basebit, l;
+  int form;                                           // kRcSigned or kRcAlternating (rs_ring_cmux.h)
+};
+hipError_t launch_ring_lookup_level(const RingLookupArgs& a, hipStream_t st);   // ring_lookup_init_kernel, then the kernel of a.form
 // the selector keyswitch of circuit bootstrapping (rs_ring_selector_dev; placement and index arithmetic of rs_ring_selector.h)
 struct RingSelectorArgs {
   int32_t* sel;                                       // [rows / l][2l][2][N]

@@ -1117,6 +1117,30 @@ def ring_lookup(table, sel, basebit, l, digits="signed"):
     return rows[0]
 
 
+def ring_lookup_rows(table, sel, basebit, l, entries, R, row_stride=0, entry_stride=1, per_row=None, digits="signed"):
+    """rs_ring_lookup_rows_dev restated (digits="alternating": rs_ring_lookup_rows_alt_dev) as a loop over
+    ring_lookup: table int32 ciphertexts [..][2][N], entry e of row q the ciphertext q row_stride + e entry_stride; sel int32
+    [depth][2l][2][N] (one hidden index for all rows) or, with per_row (inferred from five dimensions where None),
+    [R][depth][2l][2][N] -> int32 [R][2][N], out[q] = ring_lookup of row q's entries under row q's selectors. Nothing like the
+    device's levels of all rows at once."""
+    basebit, l = _check_cmux_digits(basebit, l)
+    _check_cmux_form(digits)
+    sel = np.ascontiguousarray(sel, np.int32)
+    per_row = sel.ndim == 5 if per_row is None else bool(per_row)
+    assert sel.ndim == (5 if per_row else 4) and sel.shape[-3:-1] == (2 * l, 2), "sel must hold [depth][2l][2][N] words ([R][depth].. per row)"
+    N = sel.shape[-1]
+    entries, R, row_stride, entry_stride = int(entries), int(R), int(row_stride), int(entry_stride)
+    if row_stride < 0 or entry_stride < 1:
+        raise ValueError("row_stride = %d, entry_stride = %d: row_stride must be at least 0 and entry_stride at least 1" % (row_stride, entry_stride))
+    assert not per_row or sel.shape[0] == R, "one selector set per row"
+    cts = np.ascontiguousarray(table, np.int32).reshape(-1, 2, N)
+    out = np.zeros((R, 2, N), np.int32)
+    for q in range(R):
+        rows = cts[[q * row_stride + e * entry_stride for e in range(entries)]]
+        out[q] = ring_lookup(rows, sel[q] if per_row else sel, basebit, l, digits)
+    return out
+
+
 def ring_trivial(values):
     """Plaintext torus polynomials int32 [..., N] as trivial ring ciphertexts (0, p) -> int32 [..., 2, N]: the rows of a server-held
     plaintext table."""
